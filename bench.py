@@ -2,16 +2,18 @@
 """Headline benchmark: images/sec of the HTD-R50 train step (fwd + losses + bwd + gradient all-reduce +
 SGD update) on synthetic 1333x800 COCO-shaped batches, fp32, B=4 per MI355X (BASELINE.json configs[1]).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N > 1 started plainly: this process touches no GPU, starts `python -m torch.distributed.run --nnodes=1
 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py <same arguments>` as a CHILD (one rank per GPU over RCCL, the
 launch of tools/dist_train.sh:7-9) and exits with its code.  Started under torch.distributed.run already (WORLD_SIZE
 in the environment) it is a rank; WORLD_SIZE != --gpus is an error, never a silent one-GPU run.
 
-Prints ONE JSON line on rank 0 (see the driver contract): whole-job images/sec, plus
+Prints ONE JSON line on rank 0 (see the driver contract): whole-job images/sec and ms_per_step of the K timed steps.
+A plain run does nothing else.  --dump-outputs DIR writes what the last timed step returned (dump_outputs).  --full adds
   roofline     -- the dominant hand-written kernel of the step, timed live with device events on the stream
                   it is launched on, priced against its algorithmic FLOPs / bytes (DESIGN.md section 5);
+  trained_like -- more timed steps with trained-like proposals after the headline ones (config.trained_like);
   cpu_baseline -- the CPU oracle (reference semantics) timed on this host on a bounded sample (rank 0, N=1).
 Nothing here reads /root/reference.
 """
@@ -46,7 +48,10 @@ def parse():
                     'data pipeline (Resize 1333x800 keep-ratio / RandomFlip / Normalize / Pad 32) inside the timed region')
     ap.add_argument('--height', type=int, default=800)
     ap.add_argument('--width', type=int, default=1344)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true', help='also the roofline of the dominant kernel (device events on every 4th '
+                    'timed step), the trained-like steps and the CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='after the timed steps: what the last one returned, as DIR/<name>.npy')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
     ap.add_argument('--infer', action='store_true', help='inference-only throughput (BASELINE configs[4] shape): '
                     'simple_test with --proposals RoIs per image into the RoI head')
     ap.add_argument('--proposals', type=int, default=512)
@@ -55,7 +60,7 @@ def parse():
     ap.add_argument('--trained-like', action='store_true', help='force 128 stage-2 positives per image (what a trained '
                     'detector yields) so the HTD regression branch (1.24 GFLOP per positive RoI) is inside the timed region; '
                     'random-init weights give ~6 per image')
-    ap.add_argument('--trained-like-steps', type=int, default=8, help='after the timed region: this many more timed steps with '
+    ap.add_argument('--trained-like-steps', type=int, default=8, help='with --full, after the timed region: this many more timed steps with '
                     'trained-like proposals, reported as config.trained_like (0 = skip)')
     ap.add_argument('--cpu-baseline-full', action='store_true', help='ONLY the CPU baseline, by the BASELINE.md section 3 protocol '
                     '(3 warm-up + 10 timed steps, B=4 @ 800x1344); prints its JSON object; no GPU needed')
@@ -115,7 +120,7 @@ def cpu_baseline(depth, H, W, full=False, dcn=False, batch=4, infer=False, propo
     """The CPU oracle (oracle/detector.py, pinned against reference-generated fixtures): train step = forward + losses
     + backward, fp32, all host threads, the synthetic inputs of the GPU run.
 
-    Default (every bench.py run): a BOUNDED sample -- one untimed warm-up step on a 256x320 image (thread pools, allocator,
+    Default (every `bench.py --full` run): a BOUNDED sample -- one untimed warm-up step on a 256x320 image (thread pools, allocator,
     lazy kernels), then 2 timed steps on ONE 800x1344 image; value = images / mean step time, the two samples are
     reported.  full=True (`--cpu-baseline-full`, run once per round and kept under profiles/): the protocol of
     BASELINE.md section 3 / tools/benchmark.py:70-96 -- 3 warm-up + 10 timed steps at B = 4 @ 800x1344 (~10 minutes)."""
@@ -190,6 +195,78 @@ def pipeline_batch(batch, dev, rank):
     stager = DeviceBatchStager(dev)
     resident, plan = stager.upload([s['img'] for s in samples])
     return data, lambda: stager.run(resident, plan)
+
+
+DUMP_SAMPLE = 1 << 21          # elements drawn from each flat parameter-sized buffer: 2 x 8 MB of the 64 MB allowed
+
+
+def dump_outputs(path, result, trainer):
+    """--dump-outputs: what the last timed step returned to its caller, as float32 / float64 DIR/<name>.npy.
+    Train step: every logged scalar (losses, accuracies, `loss`), and the same seeded sample of indices (fixed for a
+    configuration) of the flat weights after the SGD update and of the gradients that update applied: the full buffers
+    are 374 MB each for R50.  Inference: every detection as rows (image, class, x1, y1, x2, y2, score)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {}
+    if isinstance(result, dict):
+        for k, v in result['log_vars'].items():
+            arrays[k] = np.array(v, dtype=np.float64)
+        flat = trainer.flat
+        g = torch.Generator().manual_seed(0)
+        idx = torch.randint(0, flat.total, (min(DUMP_SAMPLE, flat.total), ), generator=g).sort().values.to(flat.flat.device)
+        arrays['weights_sample'] = flat.flat[idx].float().cpu().numpy()
+        arrays['grads_sample'] = flat.grad[idx].float().cpu().numpy()
+    else:
+        rows = [np.concatenate([np.full((len(d), 1), i), np.full((len(d), 1), c), d[:, :5]], 1)
+                for i, per_class in enumerate(result) for c, d in enumerate(per_class)]
+        arrays['detections'] = np.concatenate(rows).astype(np.float32) if rows else np.zeros((0, 7), np.float32)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name.replace('/', '_') + '.npy'), a)
+
+
+def roofline(prof, args):
+    """The `roofline` object of --full (and --profile-kernels / --profile-detail) from the timed region's device events."""
+    from htd_amd import capi, dense
+    # fp32 convolutions run as six bf16 MFMA products per fp32 product (exact three-way bf16 splits of both operands,
+    # fp32 accumulation: conv_fwd.hip "X3"): the roof of that algorithm is the bf16 matrix peak / 6 in algorithmic fp32
+    # FLOP/s; with HTD_CONV_MATH=0 (fp32-input MFMA) it is the fp32 matrix peak
+    x3 = capi.lib().htd_conv2d_set_math(-1) == 1
+    roof = dense.roofline_report(prof, PEAK_BF16_MFMA_TFLOPS / 6.0 if x3 else PEAK_F32_MFMA_TFLOPS, PEAK_HBM_GBS,
+                                 PEAK_BF16_MFMA_TFLOPS)
+    if roof and roof.get('bound') == 'mfma' and 'bf16' not in roof['kernel']:
+        roof['peak'] = round(roof['peak'], 1)
+        h2 = 'H2 form' in roof['kernel']
+        if h2:
+            roof['math'] = ('fp32 = 3 x v_mfma_f32_32x32x16_f16 on two block-scaled fp16 pieces per operand (a0 b0 + a0 b1 + a1 b0), fp32 '
+                            'accumulate; peak = 2500 / 3 algorithmic TFLOP/s.  Under the socket power cap the matrix pipe alone sustains '
+                            '539 algorithmic TFLOP/s in this form and 284 in the six-product bf16 form (tools/micro/mfma_split_products.hip, '
+                            'profiles/r04_mfma_split_products.txt)')
+            roof['power_capped_matrix_pipe_tflops'] = 539.2
+            roof['frac_of_power_capped_matrix_pipe'] = round(roof['achieved'] / 539.2, 4)
+            roof['frac_of_six_product_bf16_roof'] = round(roof['achieved'] / (PEAK_BF16_MFMA_TFLOPS / 6.0), 4)    # rounds 2-3's yardstick
+        else:
+            roof['math'] = ('fp32 = 6 x v_mfma_f32_32x32x16_bf16 on exact 3-way bf16 splits, fp32 accumulate; peak = 2500 / 6 '
+                            'algorithmic TFLOP/s (the fp32-input MFMA peak, 157.3, is not the bound of this kernel)') if x3 else \
+                'v_mfma_f32_32x32x2_f32'
+        roof['issued_bf16_tflops'] = round(roof['achieved'] * (3.0 if h2 else 6.0), 1) if x3 else None
+        roof['frac_of_fp32_input_mfma_peak'] = round(roof['achieved'] / PEAK_F32_MFMA_TFLOPS, 4)      # 157.3: round 1's yardstick
+    # HBM bytes per launch of the dominant kernel class come from separate rocprofv3 PMC passes (FETCH_SIZE,
+    # WRITE_SIZE; gfx950 read correction applied) whose summary is committed under profiles/
+    try:
+        # passes taken on the kernels of that arithmetic: the newest round that has them
+        names = ['r04_hbm_traffic.json', 'r03_hbm_traffic.json', 'r02_hbm_traffic.json'] if x3 else ['r01_hbm_traffic.json']
+        cls = 'conv_wgrad' if 'wgrad' in roof['kernel'] else ('conv_x3p' if 'x3p' in roof['kernel'] else 'conv_igemm')
+        for name in names:
+            path = os.path.join(ROOT, 'profiles', name)
+            tr = json.load(open(path))['kernels'] if os.path.exists(path) else {}
+            if cls in tr and 'conv' in roof['kernel'] and 'bf16' not in roof['kernel'] and args.depth == 50 and not args.infer \
+                    and args.batch == 4 and not args.trained_like:
+                roof['traffic'] = tr[cls]['hbm_bytes_per_launch_corrected']
+                roof['traffic_unit'] = f'bytes/launch (rocprofv3 PMC passes of this command, profiles/{name})'
+                break
+    except Exception:
+        pass
+    return roof
 
 
 def dry_launch(args, world, rank):
@@ -301,14 +378,16 @@ def main():
     for _ in range(args.warmup):
         trainer.train_step(data)
     sync()
-    # live device-event timing of the matrix-core entry points (the roofline kernels); every entry point with
+    # live device-event timing of the matrix-core entry points (the roofline kernels) with --full; every entry point with
     # --profile-kernels (costs ~6 % of the step)
     everything = args.profile_kernels or args.profile_detail
-    capi.profile_begin(detail=args.profile_detail, only=None if everything else (
-        'htd_conv2d_fwd', 'htd_conv2d_bwd_data', 'htd_conv2d_fwd_x3p', 'htd_conv2d_bwd_data_x3p', 'htd_conv2d_bwd_weight',
-        'htd_conv2d_fwd_x3h', 'htd_conv2d_bwd_data_x3h', 'htd_conv2d_bwd_weight_h2',
-        'htd_bgemm_nt', 'htd_conv2d_fwd_bf16',
-        'htd_conv2d_dgrad_bf16', 'htd_conv2d_bwd_weight_bf16'))
+    profiled = args.full or everything
+    if profiled:
+        capi.profile_begin(detail=args.profile_detail, only=None if everything else (
+            'htd_conv2d_fwd', 'htd_conv2d_bwd_data', 'htd_conv2d_fwd_x3p', 'htd_conv2d_bwd_data_x3p', 'htd_conv2d_bwd_weight',
+            'htd_conv2d_fwd_x3h', 'htd_conv2d_bwd_data_x3h', 'htd_conv2d_bwd_weight_h2',
+            'htd_bgemm_nt', 'htd_conv2d_fwd_bf16',
+            'htd_conv2d_dgrad_bf16', 'htd_conv2d_bwd_weight_bf16'))
     exchange = getattr(trainer, 'exchange', None)
     if exchange is not None:
         exchange.stats_begin()
@@ -318,11 +397,13 @@ def main():
         # kernel events on every 4th step of the timed region (all steps with --profile-kernels): their queue
         # barriers cost ~2 ms per timed step, which would otherwise be charged to the throughput being measured
         capi.profile_pause(not everything and i % 4 != 0)
-        trainer.train_step(data)
+        result = trainer.train_step(data)
     sync()
     elapsed = time.perf_counter() - t0
     print(f'# timed region: {elapsed:.3f} s for {args.steps} steps', file=sys.stderr)
     prof = capi.profile_end()
+    if args.dump_outputs and rank == 0 and args.steps > 0:
+        dump_outputs(args.dump_outputs, result, trainer)
     comm = exchange.stats() if exchange is not None else None
     if not args.infer and hasattr(model.roi_head, '_last_static'):
         npos_headline = int(model.roi_head._last_static[1].npos.sum())
@@ -340,7 +421,7 @@ def main():
     # positive RoI) all but vanishes from the step above.  A few more steps with jittered gt boxes injected into the proposal
     # lists (both stages then sample their 128 positives per image); reported beside the headline, never as `value`.
     trained = None
-    if not args.infer and not args.trained_like and args.trained_like_steps > 0:
+    if args.full and not args.infer and not args.trained_like and args.trained_like_steps > 0:
         trained_like_proposals(model, data, args.batch)
         TL_WARMUP = 4          # (the regression branch's tensors are new sizes for the allocator: two steps did not always cover them)
         for _ in range(TL_WARMUP):
@@ -367,46 +448,6 @@ def main():
     world = n_ranks
     value = args.batch * world * args.steps / elapsed
 
-    from htd_amd import dense
-    # fp32 convolutions run as six bf16 MFMA products per fp32 product (exact three-way bf16 splits of both operands,
-    # fp32 accumulation: conv_fwd.hip "X3"): the roof of that algorithm is the bf16 matrix peak / 6 in algorithmic fp32
-    # FLOP/s; with HTD_CONV_MATH=0 (fp32-input MFMA) it is the fp32 matrix peak
-    x3 = capi.lib().htd_conv2d_set_math(-1) == 1
-    roof = dense.roofline_report(prof, PEAK_BF16_MFMA_TFLOPS / 6.0 if x3 else PEAK_F32_MFMA_TFLOPS, PEAK_HBM_GBS,
-                                 PEAK_BF16_MFMA_TFLOPS)
-    if roof and roof.get('bound') == 'mfma' and 'bf16' not in roof['kernel']:
-        roof['peak'] = round(roof['peak'], 1)
-        h2 = 'H2 form' in roof['kernel']
-        if h2:
-            roof['math'] = ('fp32 = 3 x v_mfma_f32_32x32x16_f16 on two block-scaled fp16 pieces per operand (a0 b0 + a0 b1 + a1 b0), fp32 '
-                            'accumulate; peak = 2500 / 3 algorithmic TFLOP/s.  Under the socket power cap the matrix pipe alone sustains '
-                            '539 algorithmic TFLOP/s in this form and 284 in the six-product bf16 form (tools/micro/mfma_split_products.hip, '
-                            'profiles/r04_mfma_split_products.txt)')
-            roof['power_capped_matrix_pipe_tflops'] = 539.2
-            roof['frac_of_power_capped_matrix_pipe'] = round(roof['achieved'] / 539.2, 4)
-            roof['frac_of_six_product_bf16_roof'] = round(roof['achieved'] / (PEAK_BF16_MFMA_TFLOPS / 6.0), 4)    # rounds 2-3's yardstick
-        else:
-            roof['math'] = ('fp32 = 6 x v_mfma_f32_32x32x16_bf16 on exact 3-way bf16 splits, fp32 accumulate; peak = 2500 / 6 '
-                            'algorithmic TFLOP/s (the fp32-input MFMA peak, 157.3, is not the bound of this kernel)') if x3 else \
-                'v_mfma_f32_32x32x2_f32'
-        roof['issued_bf16_tflops'] = round(roof['achieved'] * (3.0 if h2 else 6.0), 1) if x3 else None
-        roof['frac_of_fp32_input_mfma_peak'] = round(roof['achieved'] / PEAK_F32_MFMA_TFLOPS, 4)      # 157.3: round 1's yardstick
-    # HBM bytes per launch of the dominant kernel class come from separate rocprofv3 PMC passes (FETCH_SIZE,
-    # WRITE_SIZE; gfx950 read correction applied) whose summary is committed under profiles/
-    try:
-        # passes taken on the kernels of that arithmetic: the newest round that has them
-        names = ['r04_hbm_traffic.json', 'r03_hbm_traffic.json', 'r02_hbm_traffic.json'] if x3 else ['r01_hbm_traffic.json']
-        cls = 'conv_wgrad' if 'wgrad' in roof['kernel'] else ('conv_x3p' if 'x3p' in roof['kernel'] else 'conv_igemm')
-        for name in names:
-            path = os.path.join(ROOT, 'profiles', name)
-            tr = json.load(open(path))['kernels'] if os.path.exists(path) else {}
-            if cls in tr and 'conv' in roof['kernel'] and 'bf16' not in roof['kernel'] and args.depth == 50 and not args.infer \
-                    and args.batch == 4 and not args.trained_like:
-                roof['traffic'] = tr[cls]['hbm_bytes_per_launch_corrected']
-                roof['traffic_unit'] = f'bytes/launch (rocprofv3 PMC passes of this command, profiles/{name})'
-                break
-    except Exception:
-        pass
     if args.profile_kernels or args.profile_detail:
         for name, (n, tot_ms, kind, work, _) in sorted(prof.items(), key=lambda kv: -kv[1][1])[:60]:
             rate = (work / (tot_ms * 1e-3) / 1e12) if (kind and tot_ms > 0) else 0.0
@@ -426,8 +467,9 @@ def main():
                                 f'{args.width - 11}x{args.height} (padded {args.width}x{args.height}), '
                                 'random-init weights, 2000 RPN proposals/img, 512 RoIs/img/stage'),
                    'global_batch': args.batch * world, 'parallelism': f'dp{world}'},
-        'roofline': roof,
     }
+    if profiled:
+        out['roofline'] = roofline(prof, args)
     if backend != 'nccl' and world > 1:
         out['rehearsal'] = f'{backend} backend' + (f', {world} ranks sharing cuda:0' if share_gpu else '') + \
             ': exercises the rank protocol, NOT a multi-GPU measurement'
@@ -450,7 +492,7 @@ def main():
             ver = None
         out['comm'] = dict(comm or {}, rccl_version=ver, process_group_ranks=n_ranks)
         out['ms_per_step_per_rank'] = rank_ms
-    if world == 1 and not args.no_cpu_baseline and not args.infer:
+    if args.full and world == 1 and not args.no_cpu_baseline and not args.infer:
         out['cpu_baseline'] = cpu_baseline(args.depth, args.height, args.width, dcn=args.dcn)
     print(json.dumps(out))
 

@@ -749,6 +749,20 @@ def gen_pipeline():
     print('pipeline: flips', [int(out[f's{i}.flip']) for i in range(4)], 'tta', out['tta.img_shapes'].tolist())
 
 
+def gen_config():
+    """configs/htd/htd_resnet50_1x.py with its `_base_` chain merged: the model / train_cfg / test_cfg dicts that
+    tests/test_host_logic.py builds through this package's registry, stored as JSON data."""
+    import json
+    from htd_amd import Config
+    cfg = Config.fromfile(os.path.join(REF, 'configs', 'htd', 'htd_resnet50_1x.py'))
+    out = {k: cfg[k].to_dict() for k in ('model', 'train_cfg', 'test_cfg')}
+    path = os.path.join(HERE, 'htd_resnet50_1x_cfg.json')
+    with open(path, 'w') as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+        f.write('\n')
+    print(f'wrote {path}')
+
+
 def aug_inputs():
     """One image under two test-time augmentations (scale 1.0 unflipped, scale 1.25 flipped): the recipe shared by
     this generator, tests/test_oracle_golden.py and tests/test_gpu_detector.py."""
@@ -818,6 +832,8 @@ def main():
         gen_resnext()
     if 'pipeline' in which:
         gen_pipeline()
+    if 'config' in which:
+        gen_config()
 
 
 if __name__ == '__main__':

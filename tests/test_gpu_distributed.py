@@ -210,7 +210,7 @@ def test_bench_rank_path_rehearsal_two_ranks_one_gpu(extra):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, HTD_BENCH_BACKEND='gloo', HTD_BENCH_SHARE_GPU='1', HSA_ENABLE_IPC_MODE_LEGACY='0')
     cmd = [sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1', '--batch', '2',
-           '--height', '256', '--width', '320', '--no-cpu-baseline'] + extra
+           '--height', '256', '--width', '320', '--full', '--no-cpu-baseline'] + extra
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]
