@@ -702,6 +702,49 @@ int htd_pgraph_scatter(const float *g, const int64_t *rows, const unsigned char 
 int htd_rows_gather(const float *x, const int64_t *rows, float *out, int64_t n, int64_t N, int F, void *stream);
 int htd_rows_add(const float *g, const int64_t *rows, float *gx, int64_t n, int64_t N, int F, void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * COCO bbox / proposal evaluation (csrc/coco_eval.hip).  Replaces pycocotools' COCOeval.evaluate / accumulate as
+ * called by CocoDataset.evaluate (datasets/coco.py:448-452); htd_amd/core/evaluation.py sorts and groups, and
+ * summarises on the host.  All arithmetic is IEEE double, as in pycocotools (maskApi.c bbIou; cocoeval.py).
+ *   match       one workgroup per non-empty (category, image) pair, or per image when useCats = 0: the IoU and the
+ *               greedy matching of COCOeval.evaluateImg for all A area ranges x T IoU thresholds at once.
+ *               gt_box [n_gt][4] xywh, gt_area (annotation 'area'), gt_crowd, gt_id [n_gt], grouped by pair in
+ *               COCOeval's order; dt_box [n_dt][4] xywh grouped by pair, score-descending and cut to maxDets[-1];
+ *               pair_gt / pair_dt [P+1] row offsets; area_rng [A][2] (both ends inclusive); iou_thrs [T].
+ *               dt_flags [n_dt][A][T]: bit 0 = matched to a ground truth of non-zero id, bit 1 = ignored;
+ *               npig [P][A]: non-ignored ground truths.  workspace: htd_coco_match_workspace_bytes(n_gt, A, T).
+ *   accumulate  one workgroup per (category, area, maxDet): COCOeval.accumulate.  order [n_dt]: the pair-sorted
+ *               detections of category k at cat_dt[k]..cat_dt[k+1], by score descending, then image, then rank;
+ *               dt_rank [n_dt] rank within the pair; cat_pair [K+1] the pairs of category k; max_dets [M] and
+ *               rec_thrs [R] device arrays.  precision / scores [T][R][K][A][M], recall [T][K][A][M] float64,
+ *               written in full (-1 where pycocotools leaves -1).
+ *               workspace: htd_coco_accumulate_workspace_bytes(n_dt, A, M).
+ * ---------------------------------------------------------------------------------- */
+int64_t htd_coco_match_workspace_bytes(int64_t n_gt, int A, int T);
+int htd_coco_match(const double *gt_box, const double *gt_area, const uint8_t *gt_crowd, const int64_t *gt_id,
+                   const double *dt_box, const int64_t *pair_gt, const int64_t *pair_dt, int P, const double *area_rng,
+                   int A, const double *iou_thrs, int T, uint8_t *dt_flags, int32_t *npig, void *workspace,
+                   void *stream);
+int64_t htd_coco_accumulate_workspace_bytes(int64_t n_dt, int A, int M);
+int htd_coco_accumulate(const uint8_t *dt_flags, const int64_t *order, const int32_t *dt_rank, const double *dt_score,
+                        const int64_t *cat_dt, const int64_t *cat_pair, const int32_t *npig, int K, int A,
+                        const int32_t *max_dets, int M, int T, const double *rec_thrs, int R, double *precision,
+                        double *recall, double *scores, void *workspace, void *stream);
+
+/* ------------------------------------------------------------------------------------
+ * Proposal recall of eval_recalls (core/evaluation/recall.py:eval_recalls / _recalls): one workgroup per (image,
+ * proposal count).  float32 bbox_overlaps (core/evaluation/bbox_overlaps.py, eps = 1e-6) of the image's gts [G][4]
+ * xyxy against its first min(P, prop_nums[k]) proposals [P][4] (already in score order), then the greedy assignment:
+ * the largest IoU left (first row, then first column, on ties) is recorded and its row and column retired.
+ *   gt_off / prop_off [n_img+1] row offsets; prop_nums [n_nums] device int32;
+ *   gt_ious [n_nums][n_gt]: the j-th assignment of the image in its j-th slot, -1 once rows or columns run out,
+ *   0 for an image without proposals.  workspace: htd_eval_recalls_workspace_bytes(n_gt, n_prop, n_nums).
+ * ---------------------------------------------------------------------------------- */
+int64_t htd_eval_recalls_workspace_bytes(int64_t n_gt, int64_t n_prop, int n_nums);
+int htd_eval_recalls(const float *gts, const int64_t *gt_off, const float *props, const int64_t *prop_off, int n_img,
+                     int64_t n_gt, int64_t n_prop, const int32_t *prop_nums, int n_nums, float *gt_ious,
+                     void *workspace, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
