@@ -74,11 +74,42 @@ def htd_test_cfg(soft_nms=False):
                 rcnn=dict(score_thr=0.05, nms=nms, max_per_img=100))
 
 
+IMG_NORM_CFG = dict(mean=[123.675, 116.28, 103.53], std=[58.395, 57.12, 57.375], to_rgb=True)
+
+
+def htd_data(depth=50, resnext=False, data_root='data/coco/'):
+    """The `data` section: R50 1x trains at (1333, 800); the 2x(-mstrain) configs train at a random scale in
+    [(1600, 400), (1600, 1400)]; every config tests at (1333, 800) but the ResNeXt one, at (1600, 800)."""
+    if depth == 50 and not resnext:
+        train_resize = dict(type='Resize', img_scale=(1333, 800), keep_ratio=True)
+    else:
+        train_resize = dict(type='Resize', img_scale=[(1600, 400), (1600, 1400)], multiscale_mode='range',
+                            keep_ratio=True)
+    train_pipeline = [
+        dict(type='LoadImageFromFile'), dict(type='LoadAnnotations', with_bbox=True), train_resize,
+        dict(type='RandomFlip', flip_ratio=0.5), dict(type='Normalize', **IMG_NORM_CFG),
+        dict(type='Pad', size_divisor=32), dict(type='DefaultFormatBundle'),
+        dict(type='Collect', keys=['img', 'gt_bboxes', 'gt_labels'])]
+    test_pipeline = [
+        dict(type='LoadImageFromFile'),
+        dict(type='MultiScaleFlipAug', img_scale=(1600, 800) if resnext else (1333, 800), flip=False,
+             transforms=[dict(type='Resize', keep_ratio=True), dict(type='RandomFlip'),
+                         dict(type='Normalize', **IMG_NORM_CFG), dict(type='Pad', size_divisor=32),
+                         dict(type='ImageToTensor', keys=['img']), dict(type='Collect', keys=['img'])])]
+
+    def split(name, pipeline):
+        return dict(type='CocoDataset', ann_file=data_root + f'annotations/instances_{name}2017.json',
+                    img_prefix=data_root + f'{name}2017/', pipeline=copy.deepcopy(pipeline))
+    return dict(samples_per_gpu=2, workers_per_gpu=2, train=split('train', train_pipeline),
+                val=split('val', test_pipeline), test=split('val', test_pipeline))
+
+
 def htd_config(depth=50, dcn=False, soft_nms=None, resnext=False):
-    """-> ConfigDict(model=..., train_cfg=..., test_cfg=..., optimizer=..., lr_config=...)."""
+    """-> ConfigDict(model=..., train_cfg=..., test_cfg=..., data=..., evaluation=..., optimizer=..., lr_config=...)."""
     soft_nms = (depth == 101) if soft_nms is None else soft_nms        # htd_resnet101_2x.py:298
     return ConfigDict(
         model=htd_model(depth, dcn, resnext), train_cfg=htd_train_cfg(), test_cfg=htd_test_cfg(soft_nms),
+        data=htd_data(depth, resnext), evaluation=dict(interval=1 if depth == 50 else 24, metric='bbox'),
         optimizer=dict(type='SGD', lr=0.02 if depth == 50 else 0.015, momentum=0.9, weight_decay=0.0001),
         optimizer_config=dict(grad_clip=None),
         lr_config=dict(policy='step', warmup='linear', warmup_iters=500, warmup_ratio=0.001,

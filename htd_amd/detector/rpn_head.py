@@ -431,7 +431,8 @@ class RPNHead(nn.Module):
         if flat_ok:
             # the levels' candidates through ONE gather each: rank inside (image, level) + the level's first anchor = index into
             # the flat per-anchor tensors and the level-concatenated anchors (constants of the map sizes: cached)
-            ck = (tuple(Ns), tuple(ks), str(dev))
+            # keyed on the map sizes, not on their products: transposed (portrait / landscape) maps have equal Ns
+            ck = (tuple(tuple(int(v) for v in f) for f in featmap_sizes), tuple(ks), str(dev))
             cache = self.__dict__.setdefault('_prop_cache', {})
             if ck not in cache:
                 if len(cache) > 32:
