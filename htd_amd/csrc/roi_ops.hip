@@ -1104,6 +1104,31 @@ extern "C" int htd_sgd_momentum_step(float *param, const float *grad, float *mom
     return htd::check_launch("sgd");
 }
 
+// One wavefront: lane i adds weight * packed[i] (exact in fp64: two 24-bit mantissas) to acc[i]; lane 0 adds the weight to
+// the count and latches the first non-finite total loss.  Explicit _rn operations: no contraction whatever the flags.
+__global__ __launch_bounds__(64) void log_accumulate_kernel(const float *__restrict__ packed, int n, int loss_index,
+                                                            float weight, int64_t iter, double *__restrict__ acc)
+{
+    const double w = (double)weight;
+    for (int i = threadIdx.x; i < n; i += 64)
+        acc[i] = __dadd_rn(acc[i], __dmul_rn(w, (double)packed[i]));
+    if (threadIdx.x == 0) {
+        acc[n] = __dadd_rn(acc[n], w);
+        if (!isfinite(packed[loss_index]) && acc[n + 1] < 0.0) acc[n + 1] = (double)iter;
+    }
+}
+
+extern "C" int htd_log_accumulate(const float *packed, int n, int loss_index, float weight, int64_t iter, double *acc,
+                                  void *stream)
+{
+    HTD_REQUIRE(n > 0 && loss_index >= 0 && loss_index < n, "log_accumulate: n=%d loss_index=%d", n, loss_index);
+    HTD_REQUIRE(iter >= 0, "log_accumulate: iter=%lld", (long long)iter);
+    HTD_REQUIRE(packed && acc, "log_accumulate: null pointer");
+    hipLaunchKernelGGL(log_accumulate_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, packed, n, loss_index, weight,
+                       iter, acc);
+    return htd::check_launch("log_accumulate");
+}
+
 extern "C" int htd_bn_fold_fwd(const float *w, const float *gamma, const float *beta, const float *mean,
                                const float *var, float eps, float *w_folded, float *b_folded, int Co, int K,
                                void *stream)

@@ -863,6 +863,34 @@ def sgd_momentum_step_(flat_param, flat_grad, flat_momentum, lr_dev, momentum, w
               _P(lr_dev), float(momentum), float(weight_decay), float(grad_scale), _S())
 
 
+# ====================================================================== log buffer (epoch runner)
+def log_accumulator(n, device):
+    """The fp64 running state of log_accumulate_ for n packed scalars: n sums, the summed weight, the first bad iteration."""
+    acc = torch.zeros(n + 2, dtype=torch.float64, device=device)
+    acc[n + 1] = -1.0
+    return acc
+
+
+def log_accumulate_(acc, packed, weight, it, loss_index=-1):
+    """mmcv LogBuffer.update(log_vars, num_samples) on the device: acc[:n] += weight * packed (fp64), acc[n] += weight,
+    acc[n + 1] = it if packed[loss_index] is the first non-finite total loss since acc was reset (log_accumulator).
+    One htd_log_accumulate launch on the GPU; CPU tensors (the gloo rehearsal of the runner) take the same arithmetic in
+    torch."""
+    n = packed.numel()
+    loss_index = loss_index % n
+    if acc.dtype != torch.float64 or acc.numel() != n + 2 or packed.dtype != torch.float32 or not packed.is_contiguous():
+        raise ValueError(f'log_accumulate: acc must be fp64 [{n + 2}] and packed contiguous fp32, got {acc.dtype} '
+                         f'[{acc.numel()}] / {packed.dtype}')
+    if packed.is_cuda:
+        capi.call('htd_log_accumulate', _P(packed), n, loss_index, float(weight), int(it), _P(acc), _S())
+        return acc
+    acc[:n] += packed.double() * float(weight)
+    acc[n] += float(weight)
+    if float(acc[n + 1]) < 0 and not bool(torch.isfinite(packed[loss_index])):
+        acc[n + 1] = float(it)
+    return acc
+
+
 # ====================================================================== segmented top-k (RPN level ranking, samplers)
 TOPK_CHUNK, TOPK_KMAX = 4096, 2048
 _TOPK_PLANS = {}       # (segments, numel, device) -> device tables: built once per shape, never per call

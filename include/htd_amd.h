@@ -32,7 +32,7 @@ extern "C" {
 const char *htd_last_error(void);
 /* ABI version, bumped on any signature change (added entry points do not bump it).  A binding compares
  * htd_abi_version() of the loaded library with the HTD_ABI_VERSION of the header it was written against. */
-#define HTD_ABI_VERSION 3
+#define HTD_ABI_VERSION 4
 int htd_abi_version(void);
 
 /* ------------------------------------------------------------------------------------
@@ -672,6 +672,17 @@ int htd_image_batch_pipeline(const uint8_t *src, const int64_t *src_off, const i
 int htd_sgd_momentum_step(float *param, const float *grad, float *momentum_buf, int64_t n,
                           const float *lr_dev, float momentum, float weight_decay,
                           float grad_scale, void *stream);
+
+/* ------------------------------------------------------------------------------------
+ * Running log sums of the epoch runner: what mmcv's LogBuffer.update(log_vars, num_samples) records each iteration
+ * (runner/hooks/logger: average = sum(value * n) / sum(n) in float64) for the scalars that detectors/base.py:
+ * _parse_losses:196-223 reports, packed into one device vector by BaseDetector._parse_losses.  One launch, one wavefront:
+ *   acc[i] += (double)weight * packed[i] for i < n;  acc[n] += weight;
+ *   acc[n + 1] = iter if packed[loss_index] is not finite and acc[n + 1] < 0 (the first non-finite total loss).
+ *   packed   fp32 [n] (device)       acc  fp64 [n + 2] (device; zeros, then -1 at n + 1, when a log interval starts)
+ * The host reads acc once per log interval.
+ * ---------------------------------------------------------------------------------- */
+int htd_log_accumulate(const float *packed, int n, int loss_index, float weight, int64_t iter, double *acc, void *stream);
 
 /* ----------------------------------------------------------------------------------
  * PGraph adjacency (HTDBBoxHead.forward, mmdet/models/roi_heads/bbox_heads/htd_bbox_head.py:198-219), batched over the
