@@ -104,10 +104,38 @@ def htd_data(depth=50, resnext=False, data_root='data/coco/'):
                 val=split('val', test_pipeline), test=split('val', test_pipeline))
 
 
-def htd_config(depth=50, dcn=False, soft_nms=None, resnext=False):
-    """-> ConfigDict(model=..., train_cfg=..., test_cfg=..., data=..., evaluation=..., optimizer=..., lr_config=...)."""
+def voc0712_data(data_root='data/VOCdevkit/'):
+    """configs/_base_/datasets/voc0712.py: train on VOC2007 + VOC2012 trainval (a list ann_file) repeated 3 times,
+    test on VOC2007 test, at (1000, 600)."""
+    train_pipeline = [
+        dict(type='LoadImageFromFile'), dict(type='LoadAnnotations', with_bbox=True),
+        dict(type='Resize', img_scale=(1000, 600), keep_ratio=True), dict(type='RandomFlip', flip_ratio=0.5),
+        dict(type='Normalize', **IMG_NORM_CFG), dict(type='Pad', size_divisor=32), dict(type='DefaultFormatBundle'),
+        dict(type='Collect', keys=['img', 'gt_bboxes', 'gt_labels'])]
+    test_pipeline = [
+        dict(type='LoadImageFromFile'),
+        dict(type='MultiScaleFlipAug', img_scale=(1000, 600), flip=False,
+             transforms=[dict(type='Resize', keep_ratio=True), dict(type='RandomFlip'),
+                         dict(type='Normalize', **IMG_NORM_CFG), dict(type='Pad', size_divisor=32),
+                         dict(type='ImageToTensor', keys=['img']), dict(type='Collect', keys=['img'])])]
+
+    def test_split():
+        return dict(type='VOCDataset', ann_file=data_root + 'VOC2007/ImageSets/Main/test.txt',
+                    img_prefix=data_root + 'VOC2007/', pipeline=copy.deepcopy(test_pipeline))
+    return dict(samples_per_gpu=2, workers_per_gpu=2,
+                train=dict(type='RepeatDataset', times=3, dataset=dict(
+                    type='VOCDataset', ann_file=[data_root + 'VOC2007/ImageSets/Main/trainval.txt',
+                                                 data_root + 'VOC2012/ImageSets/Main/trainval.txt'],
+                    img_prefix=[data_root + 'VOC2007/', data_root + 'VOC2012/'], pipeline=train_pipeline)),
+                val=test_split(), test=test_split())
+
+
+def htd_config(depth=50, dcn=False, soft_nms=None, resnext=False, dataset='coco'):
+    """-> ConfigDict(model=..., train_cfg=..., test_cfg=..., data=..., evaluation=..., optimizer=..., lr_config=...).
+    dataset='voc0712': both bbox heads with 20 classes, the voc0712 data section, mAP evaluation every epoch and the
+    4-epoch schedule of the reference's VOC configs (lr step at 3)."""
     soft_nms = (depth == 101) if soft_nms is None else soft_nms        # htd_resnet101_2x.py:298
-    return ConfigDict(
+    cfg = ConfigDict(
         model=htd_model(depth, dcn, resnext), train_cfg=htd_train_cfg(), test_cfg=htd_test_cfg(soft_nms),
         data=htd_data(depth, resnext), evaluation=dict(interval=1 if depth == 50 else 24, metric='bbox'),
         optimizer=dict(type='SGD', lr=0.02 if depth == 50 else 0.015, momentum=0.9, weight_decay=0.0001),
@@ -115,6 +143,16 @@ def htd_config(depth=50, dcn=False, soft_nms=None, resnext=False):
         lr_config=dict(policy='step', warmup='linear', warmup_iters=500, warmup_ratio=0.001,
                        step=[8, 11] if depth == 50 else [16, 22]),
         total_epochs=12 if depth == 50 else 24)
+    if dataset == 'voc0712':
+        for head in cfg.model.roi_head.bbox_head:
+            head.num_classes = 20
+        cfg.data = ConfigDict(voc0712_data())
+        cfg.evaluation = ConfigDict(interval=1, metric='mAP')
+        cfg.lr_config.step = [3]
+        cfg.total_epochs = 4
+    elif dataset != 'coco':
+        raise ValueError(f"htd_config: dataset must be 'coco' or 'voc0712', got {dataset!r}")
+    return cfg
 
 
 def build_htd_detector(depth=50, dcn=False, cfg=None, bf16=False, resnext=False):

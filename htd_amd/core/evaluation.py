@@ -1,10 +1,12 @@
-"""COCO bbox / proposal evaluation and proposal recall on the device.
+"""COCO bbox / proposal evaluation, Pascal VOC mean AP and proposal recall on the device.
 
 coco_eval() is pycocotools' COCOeval.evaluate + accumulate + summarize as CocoDataset.evaluate drives them
 (datasets/coco.py:363-545): the greedy matching and the accumulation run as HIP kernels (csrc/coco_eval.hip), the sort
 and grouping of the detections is a few stable device sorts here, and the 12 summary numbers are taken on the host
 from the device arrays with pycocotools' own slices.  eval_recalls() is core/evaluation/recall.py:eval_recalls with
-the IoU and the greedy assignment on the device.  pycocotools is not needed.
+the IoU and the greedy assignment on the device.  pycocotools is not needed.  eval_map() is
+core/evaluation/mean_ap.py:eval_map in process (no worker pool): TP/FP and the precision / recall accumulation run as
+HIP kernels (csrc/voc_eval.hip), and the host sums each class's 'area' terms in numpy's order.
 """
 from collections.abc import Sequence
 
@@ -294,3 +296,266 @@ def eval_recalls(gts, proposals, proposal_nums=None, iou_thrs=0.5, logger=None, 
     recalls = counts / float(n_gt)
     print_recall_summary(recalls, proposal_nums, iou_thrs, logger=logger)
     return recalls
+
+
+# ------------------------------------------------------------------------------------------------ eval_map (VOC)
+def voc_classes():
+    """class_names.py:voc_classes."""
+    return ['aeroplane', 'bicycle', 'bird', 'boat', 'bottle', 'bus', 'car', 'cat', 'chair', 'cow', 'diningtable',
+            'dog', 'horse', 'motorbike', 'person', 'pottedplant', 'sheep', 'sofa', 'train', 'tvmonitor']
+
+
+def coco_classes():
+    """class_names.py:coco_classes: the COCO names with '_' for ' '."""
+    from ..coco import COCO_CLASSES
+    return [c.replace(' ', '_') for c in COCO_CLASSES]
+
+
+_VOC_ALIASES = ('voc', 'pascal_voc', 'voc07', 'voc12')
+_COCO_ALIASES = ('coco', 'mscoco', 'ms_coco')
+_OTHER_ALIASES = ('det', 'imagenet_det', 'ilsvrc_det', 'vid', 'imagenet_vid', 'ilsvrc_vid', 'WIDERFaceDataset',
+                  'wider_face', 'WDIERFace', 'cityscapes')
+
+
+def get_classes(dataset):
+    """class_names.py:get_classes for the Pascal VOC and COCO aliases; the reference's other aliases raise
+    NotImplementedError."""
+    if not isinstance(dataset, str):
+        raise TypeError(f'dataset must a str, but got {type(dataset)}')
+    if dataset in _VOC_ALIASES:
+        return voc_classes()
+    if dataset in _COCO_ALIASES:
+        return coco_classes()
+    if dataset in _OTHER_ALIASES:
+        raise NotImplementedError(f'get_classes: the class names of {dataset!r} are not included')
+    raise ValueError(f'Unrecognized dataset: {dataset}')
+
+
+def _f32_bound(v):
+    """The float32 t such that, for every float32 x, x >= t (and x < t) exactly when numpy's `x >= v` (`x < v`) holds
+    for a float32 array x: a Python number is cast to float32 (NEP 50); a 64-bit numpy scalar makes the comparison
+    float64, which the next float32 up reproduces."""
+    if isinstance(v, np.generic) and np.result_type(np.float32, v) != np.float32:
+        t = np.float32(v)
+        if float(t) < float(v):
+            t = np.nextafter(t, np.float32(np.inf))
+        return t
+    return np.float32(v)
+
+
+def _as_np(a):
+    return a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+
+
+def _map_gts(annotations, K):
+    """-> host arrays: gts [n, 4] float32 grouped by pair (class * I + image), non-ignored before ignored, each in
+    annotation order; gt_off [K * I + 1]; n_keep [K * I]."""
+    I = len(annotations)
+    boxes, keys, ign = [], [], []
+    for i, ann in enumerate(annotations):
+        parts = [(ann['bboxes'], ann['labels'], 0)]
+        if ann.get('labels_ignore', None) is not None:
+            parts.append((ann['bboxes_ignore'], ann['labels_ignore'], 1))
+        for b, lab, flag in parts:
+            lab = _as_np(lab).reshape(-1).astype(np.int64)
+            b = _as_np(b).astype(np.float32).reshape(-1, 4)
+            ok = (lab >= 0) & (lab < K)
+            boxes.append(b[ok])
+            keys.append(lab[ok] * I + i)
+            ign.append(np.full(int(ok.sum()), flag, np.int64))
+    boxes = np.concatenate(boxes) if boxes else np.zeros((0, 4), np.float32)
+    keys = np.concatenate(keys) if keys else np.zeros(0, np.int64)
+    ign = np.concatenate(ign) if ign else np.zeros(0, np.int64)
+    order = np.argsort(keys * 2 + ign, kind='stable')
+    keys = keys[order]
+    gt_off = np.searchsorted(keys, np.arange(K * I + 1), side='left').astype(np.int64)
+    n_keep = np.bincount(keys[ign[order] == 0], minlength=K * I).astype(np.int32)
+    return np.ascontiguousarray(boxes[order]), gt_off, n_keep
+
+
+def _map_dets(det_results, I, K, dev):
+    """-> device dets [n, 5] float32 grouped by pair (class * I + image) in row order, det_off [K * I + 1], and a
+    device flag (or None) set when a label or image index of the triple form lies out of range.  Out-of-range rows
+    are clamped into range so that every kernel stays in bounds; the caller raises once the flag is read back with
+    the results."""
+    if isinstance(det_results, (tuple, list)) and len(det_results) == 3 and isinstance(det_results[0], torch.Tensor):
+        dets, labels, index = det_results
+        dets = dets.to(dev, torch.float32).reshape(-1, 5)
+        labels, index = labels.to(dev, torch.int64).reshape(-1), index.to(dev, torch.int64).reshape(-1)
+        bad = ((labels < 0) | (labels >= K) | (index < 0) | (index >= I)).any().to(torch.uint8).reshape(1)
+        key = labels.clamp(0, K - 1) * I + index.clamp(0, I - 1)
+        order = torch.argsort(key, stable=True)
+        key = key[order]
+        det_off = torch.searchsorted(key, torch.arange(K * I + 1, device=dev, dtype=torch.int64))
+        return dets[order].contiguous(), det_off.contiguous(), bad
+    if len(det_results) != I:
+        raise ValueError(f'eval_map: {len(det_results)} results for {I} images')
+    arrs, lens = [], np.zeros(K * I, np.int64)
+    for c in range(K):
+        for i in range(I):
+            a = _as_np(det_results[i][c])
+            if a.size:
+                a = a.reshape(-1, 5)
+                arrs.append(a)
+                lens[c * I + i] = a.shape[0]
+    dets = np.concatenate(arrs).astype(np.float32, copy=False) if arrs else np.zeros((0, 5), np.float32)
+    det_off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    return torch.from_numpy(np.ascontiguousarray(dets)).to(dev), torch.from_numpy(det_off).to(dev), None
+
+
+def map_device_arrays(det_results, annotations, num_classes, area_ranges=None, iou_thr=0.5, device=None):
+    """The device part of eval_map: -> dict of host numpy arrays, all read back in one copy:
+    cls_off [K+1], recall [S][n] float64 and precision [S][n] float32 (class k at cls_off[k]..cls_off[k+1], score
+    descending, ties in (image, row) order), terms [S][n + K] float64 ('area' terms of class k from cls_off[k] + k),
+    n_terms / num_gts [K][S] int32, ap11 [K][S] float32."""
+    dev = _device(device)
+    I, K = len(annotations), int(num_classes)
+    S = 1 if area_ranges is None else len(area_ranges)
+    if K <= 0 or I <= 0 or S <= 0:
+        raise ValueError(f'eval_map: {K} classes, {I} images, {S} scale ranges')
+    P_, S_ = capi.ptr, capi.current_stream_ptr
+    with torch.cuda.device(dev):
+        dets, det_off, bad = _map_dets(det_results, I, K, dev)
+        gts, gt_off, n_keep = _map_gts(annotations, K)
+        gts, gt_off, n_keep = (torch.from_numpy(x).to(dev) for x in (gts, gt_off, n_keep))
+        rng = None
+        if area_ranges is not None:
+            rng = torch.from_numpy(np.array([[_f32_bound(lo), _f32_bound(hi)] for lo, hi in area_ranges],
+                                            np.float32)).to(dev)
+        n = dets.shape[0]
+        flags = torch.empty((n, S), dtype=torch.uint8, device=dev)
+        pair_gts = torch.empty((K * I, S), dtype=torch.int32, device=dev)
+        ws = torch.empty(capi.lib().htd_voc_tpfp_workspace_bytes(n), dtype=torch.uint8, device=dev)
+        capi.call('htd_voc_tpfp', P_(dets), P_(det_off), P_(gts), P_(gt_off), P_(n_keep), K * I, P_(rng), S,
+                  float(_f32_bound(iou_thr)), P_(flags), P_(pair_gts), P_(ws), S_())
+
+        # the class's rows by score descending, ties in (image, row) order; -score + 0 sorts -0.0 with +0.0
+        cls_off = det_off[::I].contiguous()
+        cls = torch.repeat_interleave(torch.arange(K, device=dev), cls_off[1:] - cls_off[:-1], output_size=n)
+        order = torch.argsort(-dets[:, 4] + 0.0, stable=True)
+        order = order[torch.argsort(cls[order], stable=True)].contiguous()
+        thr11 = torch.from_numpy(np.arange(0, 1 + 1e-3, 0.1)).to(dev)
+        sizes = [('recall', S * n, np.float64), ('terms', S * (n + K), np.float64), ('precision', S * n, np.float32),
+                 ('ap11', K * S, np.float32), ('n_terms', K * S, np.int32), ('num_gts', K * S, np.int32),
+                 ('cls_off', K + 1, np.int64), ('bad', 1, np.uint8)]
+        offs, total = {}, 0
+        for name, count, dt in sizes:
+            offs[name] = (total, count, dt)
+            total += -(-count * np.dtype(dt).itemsize // 8) * 8
+        out = torch.empty(total, dtype=torch.uint8, device=dev)
+        view = {name: out[o:o + c * np.dtype(dt).itemsize] for name, (o, c, dt) in offs.items()}
+        view['cls_off'].view(torch.int64).copy_(cls_off)
+        if bad is not None:
+            view['bad'].copy_(bad)
+        else:
+            view['bad'].zero_()
+        env = torch.empty(capi.lib().htd_voc_accumulate_workspace_bytes(n, S), dtype=torch.uint8, device=dev)
+        capi.call('htd_voc_accumulate', P_(flags), P_(order), P_(cls_off), P_(pair_gts), K, I, S, n, P_(thr11),
+                  P_(view['recall']), P_(view['precision']), P_(view['terms']), P_(view['n_terms']),
+                  P_(view['num_gts']), P_(view['ap11']), P_(env), S_())
+        host = out.cpu().numpy()
+    res = {name: host[o:o + c * np.dtype(dt).itemsize].view(dt) for name, (o, c, dt) in offs.items()}
+    if res.pop('bad')[0]:
+        raise ValueError(f'eval_map: labels must lie in [0, {K}) and image indices in [0, {I})')
+    res['recall'] = res['recall'].reshape(S, n)
+    res['precision'] = res['precision'].reshape(S, n)
+    res['terms'] = res['terms'].reshape(S, n + K)
+    for k in ('ap11', 'n_terms', 'num_gts'):
+        res[k] = res[k].reshape(K, S)
+    return res
+
+
+def _num_classes(det_results, dataset, num_classes):
+    if num_classes is not None:
+        return int(num_classes)
+    if isinstance(det_results, (tuple, list)) and len(det_results) == 3 and isinstance(det_results[0], torch.Tensor):
+        if isinstance(dataset, str):
+            return len(get_classes(dataset))
+        if dataset is not None:
+            return len(dataset)
+        raise ValueError('eval_map: the (dets, labels, index) form needs num_classes= or a dataset naming the classes')
+    return len(det_results[0])
+
+
+def eval_map(det_results, annotations, scale_ranges=None, iou_thr=0.5, dataset=None, logger=None, tpfp_fn=None,
+             nproc=4, num_classes=None, device=None):
+    """mean_ap.py:eval_map on the device, in process: -> (mean_ap, [per-class dict(num_gts, num_dets, recall,
+    precision, ap)]) with the reference's types and dtypes.
+
+    det_results: bbox2result lists (one list of (n, 5) arrays per image), or the (dets (N, 5), labels (N,), image index
+    (N,)) triple of apis.results_to_tensors (then num_classes=, or `dataset` naming the classes, gives the class count).
+    annotations: per image dict(bboxes, labels[, bboxes_ignore, labels_ignore]).  Comparisons follow numpy 2 (NEP 50):
+    the float32 IoU maximum against float32(iou_thr) and float32 areas against float32 range ends, so iou_thr=0.7
+    matches an IoU of float32(0.7) = 0.69999999, which numpy 1.x compared in float64 would not.  Score ties, which the
+    reference leaves to numpy's unstable argsort, keep (image, row) order.  nproc is accepted and ignored; tpfp_fn and
+    the ImageNet protocols ('det', 'vid') raise NotImplementedError."""
+    if tpfp_fn is not None:
+        raise NotImplementedError('eval_map: a custom tpfp_fn is not supported, the device runs tpfp_default')
+    if isinstance(dataset, str) and dataset in ('det', 'vid'):
+        raise NotImplementedError('eval_map: the ImageNet protocol (tpfp_imagenet) is not supported')
+    num_imgs = len(annotations)
+    K = _num_classes(det_results, dataset, num_classes)
+    num_scales = len(scale_ranges) if scale_ranges is not None else 1
+    area_ranges = [(rg[0] ** 2, rg[1] ** 2) for rg in scale_ranges] if scale_ranges is not None else None
+    r = map_device_arrays(det_results, annotations, K, area_ranges, iou_thr, device)
+    mode = 'area' if not (isinstance(dataset, str) and dataset == 'voc07') else '11points'
+    eval_results = []
+    for c in range(K):
+        lo, hi = int(r['cls_off'][c]), int(r['cls_off'][c + 1])
+        recalls = r['recall'][:, lo:hi].copy()
+        precisions = r['precision'][:, lo:hi].copy()
+        num_gts = r['num_gts'][c].astype(int)
+        if mode == 'area':
+            ap = np.zeros(num_scales, dtype=np.float32)
+            for s in range(num_scales):
+                ap[s] = np.sum(r['terms'][s, lo + c:lo + c + int(r['n_terms'][c, s])])
+        else:
+            ap = r['ap11'][c].copy()
+        if scale_ranges is None:
+            recalls, precisions, num_gts, ap = recalls[0], precisions[0], num_gts.item(), ap[0]
+        eval_results.append(dict(num_gts=num_gts, num_dets=hi - lo, recall=recalls, precision=precisions, ap=ap))
+    if scale_ranges is not None:
+        all_ap = np.vstack([x['ap'] for x in eval_results])
+        all_num_gts = np.vstack([x['num_gts'] for x in eval_results])
+        mean_ap = [all_ap[all_num_gts[:, i] > 0, i].mean() if np.any(all_num_gts[:, i] > 0) else 0.0
+                   for i in range(num_scales)]
+    else:
+        aps = [x['ap'] for x in eval_results if x['num_gts'] > 0]
+        mean_ap = np.array(aps).mean().item() if aps else 0.0
+    print_map_summary(mean_ap, eval_results, dataset, area_ranges, logger=logger)
+    return mean_ap, eval_results
+
+
+def print_map_summary(mean_ap, results, dataset=None, scale_ranges=None, logger=None):
+    """mean_ap.py:print_map_summary: per scale range, a table of gts / dets / recall / ap per class and the mAP."""
+    if logger == 'silent':
+        return
+    num_scales = len(results[0]['ap']) if isinstance(results[0]['ap'], np.ndarray) else 1
+    if scale_ranges is not None:
+        assert len(scale_ranges) == num_scales
+    num_classes = len(results)
+    recalls = np.zeros((num_scales, num_classes), dtype=np.float32)
+    aps = np.zeros((num_scales, num_classes), dtype=np.float32)
+    num_gts = np.zeros((num_scales, num_classes), dtype=int)
+    for i, cls_result in enumerate(results):
+        if cls_result['recall'].size > 0:
+            recalls[:, i] = np.array(cls_result['recall'], ndmin=2)[:, -1]
+        aps[:, i] = cls_result['ap']
+        num_gts[:, i] = cls_result['num_gts']
+    if dataset is None:
+        label_names = [str(i) for i in range(num_classes)]
+    elif isinstance(dataset, str):
+        label_names = get_classes(dataset)
+    else:
+        label_names = dataset
+    if not isinstance(mean_ap, list):
+        mean_ap = [mean_ap]
+    for i in range(num_scales):
+        if scale_ranges is not None:
+            print_log(f'Scale range {scale_ranges[i]}', logger=logger)
+        rows = [['class', 'gts', 'dets', 'recall', 'ap']]
+        for j in range(num_classes):
+            rows.append([str(label_names[j]), str(num_gts[i, j]), str(results[j]['num_dets']), f'{recalls[i, j]:.3f}',
+                         f'{aps[i, j]:.3f}'])
+        rows.append(['mAP', '', '', '', f'{mean_ap[i]:.3f}'])
+        print_log('\n' + format_table(rows), logger=logger)

@@ -15,7 +15,8 @@ COMMON = ['--offload-arch=' + ARCH, '-O3', '-fPIC', '-std=c++17', '-Wall', '-Wno
           '-fhip-fp32-correctly-rounded-divide-sqrt'] + os.environ.get('HTD_EXTRA_HIPCC', '').split()      # experiment builds (-D...)
 # per-file extra flags: NMS keeps the CPU path's unfused arithmetic (bit-exact keep sets)
 EXTRA = {'nms.hip': ['-ffp-contract=off'], 'box_ops.hip': ['-ffp-contract=off'],
-         'image_pipeline.hip': ['-ffp-contract=off'], 'coco_eval.hip': ['-ffp-contract=off']}
+         'image_pipeline.hip': ['-ffp-contract=off'], 'coco_eval.hip': ['-ffp-contract=off'],
+         'voc_eval.hip': ['-ffp-contract=off']}
 
 
 def sources():

@@ -39,7 +39,7 @@ def parse_args(argv=None):
     p.add_argument('checkpoint', help='checkpoint file')
     p.add_argument('--out', help='write the results to this pickle file')
     p.add_argument('--format-only', action='store_true', help='write the result json files without evaluating')
-    p.add_argument('--eval', type=str, nargs='+', help='metrics: bbox, proposal, proposal_fast')
+    p.add_argument('--eval', type=str, nargs='+', help='metrics: bbox, proposal, proposal_fast (COCO); mAP, recall (VOC)')
     p.add_argument('--eval-options', nargs='+', action=_DictAction, help='key=value keyword arguments of '
                    'dataset.evaluate (or dataset.format_results with --format-only)')
     p.add_argument('--cfg-options', nargs='+', action=_DictAction, help='key=value overrides merged into the config, '

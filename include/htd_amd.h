@@ -32,7 +32,7 @@ extern "C" {
 const char *htd_last_error(void);
 /* ABI version, bumped on any signature change (added entry points do not bump it).  A binding compares
  * htd_abi_version() of the loaded library with the HTD_ABI_VERSION of the header it was written against. */
-#define HTD_ABI_VERSION 4
+#define HTD_ABI_VERSION 5
 int htd_abi_version(void);
 
 /* ------------------------------------------------------------------------------------
@@ -755,6 +755,32 @@ int64_t htd_eval_recalls_workspace_bytes(int64_t n_gt, int64_t n_prop, int n_num
 int htd_eval_recalls(const float *gts, const int64_t *gt_off, const float *props, const int64_t *prop_off, int n_img,
                      int64_t n_gt, int64_t n_prop, const int32_t *prop_nums, int n_nums, float *gt_ious,
                      void *workspace, void *stream);
+
+/* ------------------------------------------------------------------------------------
+ * Pascal VOC mean AP (csrc/voc_eval.hip): eval_map / tpfp_default / average_precision of
+ * core/evaluation/mean_ap.py; htd_amd/core/evaluation.py:eval_map groups and sorts, and sums the 'area' terms on
+ * the host.  float32 bbox_overlaps (eps 1e-6), float64 recall, float32 precision, as in the reference under NEP 50.
+ *   tpfp        one wavefront per (class, image) pair p = class * I + image.  dets [n_det][5] (x1 y1 x2 y2 score)
+ *               grouped by pair in row order, det_off [P+1]; gts [n_gt][4] grouped by pair, each pair's non-ignored
+ *               ground truths first, then its ignored ones, gt_off [P+1], n_keep [P] non-ignored per pair;
+ *               area_rng [S][2] float32 [lo, hi) or NULL (then S = 1); iou_thr compared in float32.
+ *               flags [n_det][S]: bit 0 = TP, bit 1 = FP; num_gts [P][S] non-ignored ground truths in range.
+ *               workspace: htd_voc_tpfp_workspace_bytes(n_det).
+ *   accumulate  one workgroup per (class, scale).  order [n_det]: the pair-grouped rows of class k at
+ *               cls_off[k]..cls_off[k+1], by score descending (ties in row order); thr11 [11] the 11-point recall
+ *               thresholds (float64).  recall [S][n_det] float64 and precision [S][n_det] float32 in that order;
+ *               terms [S][n_det + K]: class k's 'area' terms from cls_off[k] + k, n_terms [K][S] of them;
+ *               gts_out [K][S] num_gts; ap11 [K][S] the '11points' AP with the reference's division by 11 per scale
+ *               loop iteration.  workspace: htd_voc_accumulate_workspace_bytes(n_det, S).  n_det < 2^24.
+ * ---------------------------------------------------------------------------------- */
+int64_t htd_voc_tpfp_workspace_bytes(int64_t n_det);
+int htd_voc_tpfp(const float *dets, const int64_t *det_off, const float *gts, const int64_t *gt_off,
+                 const int32_t *n_keep, int P, const float *area_rng, int S, float iou_thr, uint8_t *flags,
+                 int32_t *num_gts, void *workspace, void *stream);
+int64_t htd_voc_accumulate_workspace_bytes(int64_t n_det, int S);
+int htd_voc_accumulate(const uint8_t *flags, const int64_t *order, const int64_t *cls_off, const int32_t *num_gts,
+                       int K, int I, int S, int64_t n_det, const double *thr11, double *recall, float *precision,
+                       double *terms, int32_t *n_terms, int32_t *gts_out, float *ap11, void *workspace, void *stream);
 
 #ifdef __cplusplus
 }
