@@ -150,10 +150,12 @@ __device__ __forceinline__ void softmax4(const float *att, int L, int64_t n, int
     for (int l = 0; l < L; ++l) w[l] *= inv;
 }
 
+// complement of the reference's zeroed slice [edge:-edge, edge:-edge] (adaptative_roi_extractor.py:88): at edge = 0 the slice
+// [0:-0] is empty, so the whole tile is ring (as it is once edge reaches half the tile)
 __device__ __forceinline__ bool on_ring(int p, int ph, int pw, int edge)
 {
     const int y = p / pw, x = p % pw;
-    return y < edge || y >= ph - edge || x < edge || x >= pw - edge;
+    return edge == 0 || y < edge || y >= ph - edge || x < edge || x >= pw - edge;
 }
 
 __global__ __launch_bounds__(256) void ba_fuse_fwd_kernel(Ptr4 lvl, int L, const float *__restrict__ border,

@@ -785,6 +785,9 @@ class GlobalAvgPoolFunction(Function):
         if g is None:
             return galias, None
         g = g.reshape(n, C).contiguous()
+        if C % 4:         # the forward kernel takes any C, the backward kernels move float4 of channels: plain tensor arithmetic
+            gx = (g / float(h * w)).view(n, C, 1, 1).expand(n, C, h, w)
+            return (gx.contiguous(memory_format=CL) if galias is None else gx + galias), None
         if galias is not None and galias.dtype == g.dtype and tuple(galias.shape) == (n, C, h, w) and \
                 galias.is_contiguous(memory_format=CL):
             _drop_amax(galias)

@@ -192,7 +192,9 @@ int htd_fuse_global_bwd_global(const float *grad, const float *rois, float *grad
  * per-level RoIAlign outputs lvl[l] [n][P][C], the P2 border RoIAlign `border` (may alias
  * lvl[0]) and the per-level attention logits att [L][n]:
  *   w = softmax_l(att);  out = sum_l w[l][i]*lvl[l][i] + border[i] * ring(p)
- * ring(p) = 1 on the outermost `edge` rows/cols of the ph x pw window, else 0.
+ * ring(p) = 1 on the outermost `edge` rows/cols of the ph x pw window, else 0.  The reference
+ * builds the ring by zeroing the slice [edge:-edge, edge:-edge] of a copy (:88), and that slice
+ * is EMPTY at edge = 0 (and at edge >= half the window): ring(p) = 1 on the whole window there.
  * bwd: grad_lvl[l] = w[l]*g (+ ring*g added into grad_lvl[0] when border aliases lvl[0]),
  *      grad_att[l][i] = w[l][i] * (d[l][i] - sum_m w[m][i] d[m][i]),  d[l][i] = <g[i], lvl[l][i]>.
  * ---------------------------------------------------------------------------------- */
