@@ -22,7 +22,7 @@ def _ctype(decl):
         return ctypes.c_void_p
     base = decl.rsplit(' ', 1)[0].strip() if ' ' in decl else decl
     base = base.replace('const', '').strip()
-    return {'int': ctypes.c_int, 'int64_t': ctypes.c_int64, 'float': ctypes.c_float,
+    return {'int': ctypes.c_int, 'int64_t': ctypes.c_int64, 'float': ctypes.c_float, 'double': ctypes.c_double,
             'uint8_t': ctypes.c_uint8}[base]
 
 

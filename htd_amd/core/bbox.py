@@ -20,7 +20,7 @@ from .misc import arange_cached, const_tensor
 
 # ------------------------------------------------------------------ IoU
 def bbox_overlaps(bboxes1, bboxes2, mode='iou', is_aligned=False, eps=1e-6):
-    assert mode in ('iou', 'iof'), f'Unsupported mode {mode}'
+    assert mode in ('iou', 'iof', 'giou'), f'Unsupported mode {mode}'
     assert bboxes1.size(-1) == 4 or bboxes1.size(0) == 0
     assert bboxes2.size(-1) == 4 or bboxes2.size(0) == 0
     rows, cols = bboxes1.size(0), bboxes2.size(0)
@@ -31,16 +31,21 @@ def bbox_overlaps(bboxes1, bboxes2, mode='iou', is_aligned=False, eps=1e-6):
     area1 = (bboxes1[:, 2] - bboxes1[:, 0]) * (bboxes1[:, 3] - bboxes1[:, 1])
     area2 = (bboxes2[:, 2] - bboxes2[:, 0]) * (bboxes2[:, 3] - bboxes2[:, 1])
     if is_aligned:
-        wh = (torch.min(bboxes1[:, 2:], bboxes2[:, 2:]) - torch.max(bboxes1[:, :2], bboxes2[:, :2])).clamp(min=0)
-        overlap = wh[:, 0] * wh[:, 1]
-        union = area1 + area2 - overlap if mode == 'iou' else area1
+        b1, b2 = bboxes1, bboxes2
     else:
-        wh = (torch.min(bboxes1[:, None, 2:], bboxes2[None, :, 2:]) -
-              torch.max(bboxes1[:, None, :2], bboxes2[None, :, :2])).clamp(min=0)
-        overlap = wh[..., 0] * wh[..., 1]
-        union = area1[:, None] + area2[None, :] - overlap if mode == 'iou' else area1[:, None]
-    union = torch.max(union, const_tensor([eps], union.device, union.dtype))
-    return overlap / union
+        b1, b2, area1, area2 = bboxes1[:, None, :], bboxes2[None, :, :], area1[:, None], area2[None, :]
+    wh = (torch.min(b1[..., 2:], b2[..., 2:]) - torch.max(b1[..., :2], b2[..., :2])).clamp(min=0)
+    overlap = wh[..., 0] * wh[..., 1]
+    union = area1 if mode == 'iof' else area1 + area2 - overlap
+    eps = const_tensor([eps], union.device, union.dtype)
+    union = torch.max(union, eps)
+    ious = overlap / union
+    if mode != 'giou':
+        return ious
+    # generalised IoU (iou2d_calculator.py:126-158): minus the share of the enclosing box that the union leaves empty
+    enclose_wh = (torch.max(b1[..., 2:], b2[..., 2:]) - torch.min(b1[..., :2], b2[..., :2])).clamp(min=0)
+    enclose_area = torch.max(enclose_wh[..., 0] * enclose_wh[..., 1], eps)
+    return ious - (enclose_area - union) / enclose_area
 
 
 @IOU_CALCULATORS.register_module()
@@ -258,6 +263,11 @@ def delta2bbox(rois, deltas, means=(0., 0., 0., 0.), stds=(1., 1., 1., 1.), max_
 def _f4(vals):
     import ctypes
     return (ctypes.c_float * 4)(*[float(v) for v in vals])
+
+
+def _d4(vals):
+    import ctypes
+    return (ctypes.c_double * 4)(*[float(v) for v in vals])
 
 
 def delta2bbox_clip_device(rois, deltas, means, stds, lim_wh=None, keep=None, rows_per_img=None,

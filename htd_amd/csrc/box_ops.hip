@@ -360,6 +360,49 @@ constexpr int ROI_LOSS_BLOCKS = 64;
 //   acc:  #(argmax x_i == label_i and w_i > 0) (first maximum, like torch.argmax)                  -> partial[3]
 // and d(sum)/dx, d(sum)/dpred in the same pass (the backward only scales them by loss weight / avg_factor).  One wavefront
 // per row, rows strided over a fixed grid; per-block partials, added in block order by the caller (bitwise reproducible).
+// Classification half of one row on one wavefront, shared by roi_head_loss_kernel and roi_head_loss_decoded_kernel (the same
+// device code, so their loss_cls / acc / grad_cls agree bit for bit): lane 0 adds the row to its running sums, every lane
+// writes its two columns of grad_cls.  -> the row's label.
+__device__ __forceinline__ int64_t roi_cls_row(const float *__restrict__ cls, const int64_t *__restrict__ labels,
+                                               const float *__restrict__ lw, int64_t i, int NC, int lane,
+                                               float *__restrict__ gcls, float &s_ce, float &s_w, float &s_hit)
+{
+    const int64_t lab = labels[i];
+    const float w = lw[i];
+    const float *x = cls + i * NC;
+    // NC <= 128: two logits per lane
+    const int c0 = lane, c1 = lane + 64;
+    const float x0 = c0 < NC ? x[c0] : -INFINITY, x1 = c1 < NC ? x[c1] : -INFINITY;
+    const float m = htd::wave_max(fmaxf(x0, x1));
+    const float e0 = c0 < NC ? expf(x0 - m) : 0.f, e1 = c1 < NC ? expf(x1 - m) : 0.f;
+    const float lse = m + logf(htd::wave_sum(e0 + e1));
+    // first index of the maximum
+    int am = x0 == m ? c0 : (x1 == m ? c1 : 1 << 30);
+    for (int o = 32; o > 0; o >>= 1) am = min(am, __shfl_xor(am, o, 64));
+    const float xl = (lab >= 0 && lab < NC) ? x[lab] : 0.f;
+    if (lane == 0) {
+        s_ce += w * (lse - xl);
+        s_w += w > 0.f ? 1.f : 0.f;
+        s_hit += (w > 0.f && (int64_t)am == lab) ? 1.f : 0.f;
+    }
+    if (c0 < NC) gcls[i * NC + c0] = w * (expf(x0 - lse) - (c0 == lab ? 1.f : 0.f));
+    if (c1 < NC) gcls[i * NC + c1] = w * (expf(x1 - lse) - (c1 == lab ? 1.f : 0.f));
+    return lab;
+}
+
+// the four running sums of a block's waves -> partial[blockIdx][4]
+// (box_elsewhere: column 2 is written by the caller)
+__device__ __forceinline__ void roi_loss_store_partial(float (*red)[4], int lane, int wave, float s_ce, float s_w, float s_box,
+                                                       float s_hit, float *__restrict__ partial, bool box_elsewhere = false)
+{
+    if (lane == 0) { red[0][wave] = s_ce; red[1][wave] = s_w; red[2][wave] = s_box; red[3][wave] = s_hit; }
+    __syncthreads();
+    if (threadIdx.x < 4 && !(box_elsewhere && threadIdx.x == 2)) {
+        const float *r = red[threadIdx.x];
+        partial[4 * blockIdx.x + threadIdx.x] = (r[0] + r[1]) + (r[2] + r[3]);
+    }
+}
+
 __global__ __launch_bounds__(256) void roi_head_loss_kernel(const float *__restrict__ cls, const int64_t *__restrict__ labels,
                                                             const float *__restrict__ lw, const float *__restrict__ pred,
                                                             const float *__restrict__ tgt, const float *__restrict__ bw,
@@ -371,26 +414,7 @@ __global__ __launch_bounds__(256) void roi_head_loss_kernel(const float *__restr
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     float s_ce = 0.f, s_w = 0.f, s_box = 0.f, s_hit = 0.f;               // lane 0 of the wave keeps the running sums
     for (int64_t i = (int64_t)blockIdx.x * 4 + wave; i < n; i += (int64_t)gridDim.x * 4) {
-        const int64_t lab = labels[i];
-        const float w = lw[i];
-        const float *x = cls + i * NC;
-        // NC <= 128: two logits per lane
-        const int c0 = lane, c1 = lane + 64;
-        const float x0 = c0 < NC ? x[c0] : -INFINITY, x1 = c1 < NC ? x[c1] : -INFINITY;
-        const float m = htd::wave_max(fmaxf(x0, x1));
-        const float e0 = c0 < NC ? expf(x0 - m) : 0.f, e1 = c1 < NC ? expf(x1 - m) : 0.f;
-        const float lse = m + logf(htd::wave_sum(e0 + e1));
-        // first index of the maximum
-        int am = x0 == m ? c0 : (x1 == m ? c1 : 1 << 30);
-        for (int o = 32; o > 0; o >>= 1) am = min(am, __shfl_xor(am, o, 64));
-        const float xl = (lab >= 0 && lab < NC) ? x[lab] : 0.f;
-        if (lane == 0) {
-            s_ce += w * (lse - xl);
-            s_w += w > 0.f ? 1.f : 0.f;
-            s_hit += (w > 0.f && (int64_t)am == lab) ? 1.f : 0.f;
-        }
-        if (c0 < NC) gcls[i * NC + c0] = w * (expf(x0 - lse) - (c0 == lab ? 1.f : 0.f));
-        if (c1 < NC) gcls[i * NC + c1] = w * (expf(x1 - lse) - (c1 == lab ? 1.f : 0.f));
+        const int64_t lab = roi_cls_row(cls, labels, lw, i, NC, lane, gcls, s_ce, s_w, s_hit);
         if (pred) {
             const bool fg = lab >= 0 && lab < num_fg;
             float l = 0.f, g = 0.f;
@@ -406,11 +430,195 @@ __global__ __launch_bounds__(256) void roi_head_loss_kernel(const float *__restr
             if (lane == 0) s_box += l;
         }
     }
-    if (lane == 0) { red[0][wave] = s_ce; red[1][wave] = s_w; red[2][wave] = s_box; red[3][wave] = s_hit; }
-    __syncthreads();
-    if (threadIdx.x < 4) {
-        const float *r = red[threadIdx.x];
-        partial[4 * blockIdx.x + threadIdx.x] = (r[0] + r[1]) + (r[2] + r[3]);
+    roi_loss_store_partial(red, lane, wave, s_ce, s_w, s_box, s_hit, partial);
+}
+
+// ---- IoU-family regression losses on decoded boxes (losses/iou_loss.py:11-209) with their derivatives ---------------------
+// Autograd's conventions at the non-differentiable points are kept (tests/golden/iou_loss.npz, tie set): a two-operand
+// max / min splits the gradient evenly at a tie, clamp passes it at its bound, |x| has slope 0 at 0.
+enum { BOX_IOU = 0, BOX_BOUNDED = 1, BOX_GIOU = 2, BOX_DIOU = 3, BOX_CIOU = 4 };
+
+struct Box { double x1, y1, x2, y2; };
+
+struct DecodedLossArgs { double means[4], stds[4], max_ratio, eps, beta; int kind; };
+
+__device__ __forceinline__ double max_tie(double a, double b, double &da)       // max(a, b), da = d/da
+{
+    da = a > b ? 1. : (a == b ? 0.5 : 0.);
+    return fmax(a, b);
+}
+
+__device__ __forceinline__ double min_tie(double a, double b, double &da)
+{
+    da = a < b ? 1. : (a == b ? 0.5 : 0.);
+    return fmin(a, b);
+}
+
+// loss of kinds iou / giou / diou / ciou for prediction p against target t, G = d loss / d p
+__device__ __forceinline__ double iou_family_loss(int kind, Box p, Box t, double eps, Box &G)
+{
+    // intersection, areas
+    double dltx, dlty, drbx, drby;
+    const double ltx = max_tie(p.x1, t.x1, dltx), lty = max_tie(p.y1, t.y1, dlty);
+    const double rbx = min_tie(p.x2, t.x2, drbx), rby = min_tie(p.y2, t.y2, drby);
+    const double iw0 = rbx - ltx, ih0 = rby - lty;
+    const double iw = fmax(iw0, 0.), ih = fmax(ih0, 0.);
+    const double giw = iw0 >= 0. ? 1. : 0., gih = ih0 >= 0. ? 1. : 0.;
+    const double ov = iw * ih;
+    const Box dov = {-ih * giw * dltx, -iw * gih * dlty, ih * giw * drbx, iw * gih * drby};
+    const double pw = p.x2 - p.x1, ph = p.y2 - p.y1;
+    const double ap = pw * ph, ag = (t.x2 - t.x1) * (t.y2 - t.y1);
+    const double un0 = ap + ag - ov;
+    double un, gu;
+    if (kind == BOX_IOU || kind == BOX_GIOU) { un = max_tie(un0, eps, gu); }        // bbox_overlaps: max(union, eps)
+    else { un = un0 + eps; gu = 1.; }                                              // diou / ciou: union + eps
+    const Box dun = {gu * (-ph - dov.x1), gu * (-pw - dov.y1), gu * (ph - dov.x2), gu * (pw - dov.y2)};
+    const double iou = ov / un;
+    const Box diou = {(dov.x1 - iou * dun.x1) / un, (dov.y1 - iou * dun.y1) / un, (dov.x2 - iou * dun.x2) / un,
+                      (dov.y2 - iou * dun.y2) / un};
+    if (kind == BOX_IOU) {      // the reference's edit: clamp(min=eps), IoUs of at most 0.1 lifted by 0.1, -log
+        const double c = fmax(iou, eps);
+        const double v = c > 0.1 ? c : 0.1 + c;
+        const double s = iou >= eps ? -1. / v : 0.;
+        G = {s * diou.x1, s * diou.y1, s * diou.x2, s * diou.y2};
+        return -log(v);
+    }
+    // enclosing box
+    double dex1, dey1, dex2, dey2;
+    const double ex1 = min_tie(p.x1, t.x1, dex1), ey1 = min_tie(p.y1, t.y1, dey1);
+    const double ex2 = max_tie(p.x2, t.x2, dex2), ey2 = max_tie(p.y2, t.y2, dey2);
+    const double ew0 = ex2 - ex1, eh0 = ey2 - ey1;
+    const double ew = fmax(ew0, 0.), eh = fmax(eh0, 0.);
+    const double gew = ew0 >= 0. ? 1. : 0., geh = eh0 >= 0. ? 1. : 0.;
+    if (kind == BOX_GIOU) {
+        double gea;
+        const double ea = max_tie(ew * eh, eps, gea);
+        const Box dea = {-gea * eh * gew * dex1, -gea * ew * geh * dey1, gea * eh * gew * dex2, gea * ew * geh * dey2};
+        const double hole = (ea - un) / ea;                       // d hole = (dea - dun) / ea - hole * dea / ea
+        G = {-(diou.x1 - ((dea.x1 - dun.x1) - hole * dea.x1) / ea), -(diou.y1 - ((dea.y1 - dun.y1) - hole * dea.y1) / ea),
+             -(diou.x2 - ((dea.x2 - dun.x2) - hole * dea.x2) / ea), -(diou.y2 - ((dea.y2 - dun.y2) - hole * dea.y2) / ea)};
+        return 1. - (iou - hole);
+    }
+    // squared centre distance over the squared diagonal of the enclosing box
+    const double c2 = ew * ew + eh * eh + eps;
+    const Box dc2 = {-2. * ew * gew * dex1, -2. * eh * geh * dey1, 2. * ew * gew * dex2, 2. * eh * geh * dey2};
+    const double sx = (t.x1 + t.x2) - (p.x1 + p.x2), sy = (t.y1 + t.y2) - (p.y1 + p.y2);
+    const double rho2 = sx * sx / 4. + sy * sy / 4.;
+    const double q = rho2 / c2;
+    const Box dq = {(-0.5 * sx - q * dc2.x1) / c2, (-0.5 * sy - q * dc2.y1) / c2, (-0.5 * sx - q * dc2.x2) / c2,
+                    (-0.5 * sy - q * dc2.y2) / c2};
+    if (kind == BOX_DIOU) {
+        G = {dq.x1 - diou.x1, dq.y1 - diou.y1, dq.x2 - diou.x2, dq.y2 - diou.y2};
+        return 1. - (iou - q);
+    }
+    // ciou: aspect-ratio term v^2 / (1 - iou + v), eps on the heights only
+    const double h1 = ph + eps, h2 = (t.y2 - t.y1) + eps;
+    const double r1 = pw / h1;
+    const double a = atan((t.x2 - t.x1) / h2) - atan(r1);
+    const double factor = 0.40528473456935109;                    // 4 / pi^2
+    const double v = factor * (a * a);
+    const double dvdr = -2. * factor * a / (1. + r1 * r1);      // d v / d r1
+    const Box dv = {dvdr * (-1. / h1), dvdr * (r1 / h1), dvdr * (1. / h1), dvdr * (-r1 / h1)};
+    // v == 0 makes the term 0 with zero slope, also where 1 - iou + v is 0 (pred == target with a union that swallows eps: the
+    // reference's fp32 form yields 0 / 0 there): the limit, as in the tensor formulation (losses.py:ciou_loss)
+    double term = 0.;
+    Box dterm = {0., 0., 0., 0.};
+    if (v != 0.) {
+        const double den = 1. - iou + v;
+        term = v * v / den;
+        const double k1 = 2. * v / den, k2 = term / den;
+        dterm = {k1 * dv.x1 - k2 * (dv.x1 - diou.x1), k1 * dv.y1 - k2 * (dv.y1 - diou.y1), k1 * dv.x2 - k2 * (dv.x2 - diou.x2),
+                 k1 * dv.y2 - k2 * (dv.y2 - diou.y2)};
+    }
+    G = {dq.x1 + dterm.x1 - diou.x1, dq.y1 + dterm.y1 - diou.y1, dq.x2 + dterm.x2 - diou.x2, dq.y2 + dterm.y2 - diou.y2};
+    return 1. - (iou - (q + term));
+}
+
+// one axis of bounded_iou_loss (iou_loss.py:47-75): centre and extent components with weights wc / we
+// -> weighted loss of the two components; g1 / g2 = its derivative wrt the low / high coordinate of the prediction
+__device__ __forceinline__ double bounded_axis(double p1, double p2, double t1, double t2, double wc, double we, double beta, double eps,
+                                              double &g1, double &g2)
+{
+    const double pc = (p1 + p2) * 0.5, pe = p2 - p1, tc = (t1 + t2) * 0.5, te = t2 - t1;
+    const double d = tc - pc, ad = fabs(d);
+    const double sgn = d > 0. ? 1. : (d < 0. ? -1. : 0.);
+    const double num = te - 2. * ad, den = te + 2. * ad + eps;
+    double gm;
+    const double lc = 1. - max_tie(num / den, 0., gm);
+    const double dlc_dpc = gm * (-2. * (den + num) / (den * den)) * sgn;          // d lc / d pc
+    double ga;
+    const double a1 = te / (pe + eps), a2 = pe / (te + eps);
+    const double le = 1. - min_tie(a1, a2, ga);
+    const double dle_dpe = -(ga * (-a1 / (pe + eps)) + (1. - ga) * (1. / (te + eps)));
+    const double sc = lc < beta ? 0.5 * lc * lc / beta : lc - 0.5 * beta, dsc = lc < beta ? lc / beta : 1.;
+    const double se = le < beta ? 0.5 * le * le / beta : le - 0.5 * beta, dse = le < beta ? le / beta : 1.;
+    const double gc = wc * dsc * dlc_dpc * 0.5, ge = we * dse * dle_dpe;
+    g1 = gc - ge;
+    g2 = gc + ge;
+    return wc * sc + we * se;
+}
+
+// BBoxHead.loss with reg_decoded_bbox (bbox_head.py:148-186): like roi_head_loss_kernel, with the regression loss taken on
+// the decoded box delta2bbox(roi, pred) (delta_xywh_bbox_coder.py:123-204 with max_shape=None) against the ground-truth box
+// tgt by one of the IoU-family losses, and gbox = d(sum)/d(pred) through the decode (a clamped dw / dh gets 0).  Rows with a
+// background label or all-zero weights -- the unused slots of the static path, whose boxes are all zero -- compute nothing
+// on the box side and get exact zeros.  The box arithmetic is the same in every lane (wave-uniform operands); lane 0 keeps it,
+// summed in fp64; a block's sum leaves as the float pair partial[b][2] + box_lo[b].
+__global__ __launch_bounds__(256) void roi_head_loss_decoded_kernel(
+    const float *__restrict__ cls, const int64_t *__restrict__ labels, const float *__restrict__ lw, const float *__restrict__ rois,
+    const float *__restrict__ pred, const float *__restrict__ tgt, const float *__restrict__ bw, int64_t n, int NC, int num_fg,
+    DecodedLossArgs q, float *__restrict__ partial, float *__restrict__ box_lo, float *__restrict__ gcls, float *__restrict__ gbox)
+{
+    __shared__ float red[4][4];
+    __shared__ double red_box[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    float s_ce = 0.f, s_w = 0.f, s_hit = 0.f;               // lane 0 of the wave keeps the running sums
+    double s_box = 0.;
+    for (int64_t i = (int64_t)blockIdx.x * 4 + wave; i < n; i += (int64_t)gridDim.x * 4) {
+        const int64_t lab = roi_cls_row(cls, labels, lw, i, NC, lane, gcls, s_ce, s_w, s_hit);
+        const float4 w4 = *reinterpret_cast<const float4 *>(bw + i * 4);
+        float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (lab >= 0 && lab < num_fg && (w4.x != 0.f || w4.y != 0.f || w4.z != 0.f || w4.w != 0.f)) {       // wave-uniform
+            const float4 r = *reinterpret_cast<const float4 *>(rois + i * 4);
+            const float4 d0 = *reinterpret_cast<const float4 *>(pred + i * 4);
+            const float4 t4 = *reinterpret_cast<const float4 *>(tgt + i * 4);
+            // delta2bbox, no border clip
+            const double dx = d0.x * q.stds[0] + q.means[0], dy = d0.y * q.stds[1] + q.means[1];
+            const double dw0 = d0.z * q.stds[2] + q.means[2], dh0 = d0.w * q.stds[3] + q.means[3];
+            const double dw = fmin(fmax(dw0, -q.max_ratio), q.max_ratio), dh = fmin(fmax(dh0, -q.max_ratio), q.max_ratio);
+            const double cw = (dw0 >= -q.max_ratio && dw0 <= q.max_ratio) ? 1. : 0.;      // clamp passes the gradient at its bounds
+            const double ch = (dh0 >= -q.max_ratio && dh0 <= q.max_ratio) ? 1. : 0.;
+            const double px = ((double)r.x + r.z) * 0.5, py = ((double)r.y + r.w) * 0.5, pw = (double)r.z - r.x, ph = (double)r.w - r.y;
+            const double gw = pw * exp(dw), gh = ph * exp(dh);
+            const double gx = px + pw * dx, gy = py + ph * dy;
+            const Box p = {gx - gw * 0.5, gy - gh * 0.5, gx + gw * 0.5, gy + gh * 0.5};
+            const Box t = {t4.x, t4.y, t4.z, t4.w};
+            Box G;
+            double l;
+            if (q.kind == BOX_BOUNDED) {
+                l = bounded_axis(p.x1, p.x2, t.x1, t.x2, w4.x, w4.z, q.beta, q.eps, G.x1, G.x2);
+                l += bounded_axis(p.y1, p.y2, t.y1, t.y2, w4.y, w4.w, q.beta, q.eps, G.y1, G.y2);
+            } else {
+                const double wr = ((double)w4.x + w4.y + w4.z + w4.w) / 4.;      // an (n, 4) weight counts with its row mean
+                l = wr * iou_family_loss(q.kind, p, t, q.eps, G);
+                G = {wr * G.x1, wr * G.y1, wr * G.x2, wr * G.y2};
+            }
+            // chain rule through the decode: x1, x2 = gx -+ gw / 2
+            g.x = (float)((G.x1 + G.x2) * (pw * q.stds[0]));
+            g.y = (float)((G.y1 + G.y2) * (ph * q.stds[1]));
+            g.z = (float)((G.x2 - G.x1) * (0.5 * gw * q.stds[2] * cw));
+            g.w = (float)((G.y2 - G.y1) * (0.5 * gh * q.stds[3] * ch));
+            if (lane == 0) s_box += l;
+        }
+        if (lane == 0) *reinterpret_cast<float4 *>(gbox + i * 4) = g;
+    }
+    if (lane == 0) red_box[wave] = s_box;
+    roi_loss_store_partial(red, lane, wave, s_ce, s_w, 0.f, s_hit, partial, true);    // (its barrier covers red_box)
+    if (threadIdx.x == 0) {         // the block's box sum as a float pair: hi in the partial's column 2, the rest in box_lo
+        const double s = (red_box[0] + red_box[1]) + (red_box[2] + red_box[3]);
+        const float hi = (float)s;
+        partial[4 * blockIdx.x + 2] = hi;
+        box_lo[blockIdx.x] = (float)(s - (double)hi);
     }
 }
 
@@ -433,6 +641,30 @@ extern "C" int htd_roi_head_loss(const float *cls_score, const int64_t *labels, 
     hipLaunchKernelGGL(roi_head_loss_kernel, dim3(ROI_LOSS_BLOCKS), dim3(256), 0, (hipStream_t)stream, cls_score, labels,
                        label_weights, bbox_pred, bbox_targets, bbox_weights, n, NC, num_fg, beta, partial, grad_cls, grad_box);
     return htd::check_launch("roi_head_loss");
+}
+
+// As htd_roi_head_loss for a head with reg_decoded_bbox: rois [n][4], bbox_pred [n][4] deltas, bbox_targets [n][4] ground-truth
+// boxes, kind 0 iou / 1 bounded / 2 giou / 3 diou / 4 ciou (eps of the loss module; beta of the bounded form).
+// -> partial [...][4] = per-block {sum w*CE, #(w > 0), sum weighted box loss (high part), #correct}, box_lo [...] the low part of
+//    the box sum (block sum = (double)partial[b][2] + box_lo[b]), grad_box = d(sum)/d(bbox_pred).
+extern "C" int htd_roi_head_loss_decoded(const float *cls_score, const int64_t *labels, const float *label_weights,
+                                         const float *rois, const float *bbox_pred, const float *bbox_targets,
+                                         const float *bbox_weights, int64_t n, int NC, int num_fg, const double *means4,
+                                         const double *stds4, double wh_ratio_clip, int kind, double eps, double beta,
+                                         float *partial, float *box_lo, float *grad_cls, float *grad_box, void *stream)
+{
+    HTD_REQUIRE(n > 0 && NC > 0 && NC <= 128 && num_fg >= 0, "roi_head_loss_decoded: bad sizes n=%lld NC=%d", (long long)n, NC);
+    HTD_REQUIRE(kind >= BOX_IOU && kind <= BOX_CIOU && eps > 0. && wh_ratio_clip > 0. && (kind != BOX_BOUNDED || beta > 0.),
+                "roi_head_loss_decoded: bad loss kind=%d eps=%g beta=%g", kind, eps, beta);
+    HTD_REQUIRE(cls_score && labels && label_weights && rois && bbox_pred && bbox_targets && bbox_weights && means4 && stds4 &&
+                    partial && box_lo && grad_cls && grad_box, "roi_head_loss_decoded: null pointer");
+    DecodedLossArgs q;
+    for (int k = 0; k < 4; ++k) { q.means[k] = means4[k]; q.stds[k] = stds4[k]; }
+    q.max_ratio = fabs(log(wh_ratio_clip)); q.eps = eps; q.beta = beta; q.kind = kind;
+    hipLaunchKernelGGL(roi_head_loss_decoded_kernel, dim3(ROI_LOSS_BLOCKS), dim3(256), 0, (hipStream_t)stream, cls_score, labels,
+                       label_weights, rois, bbox_pred, bbox_targets, bbox_weights, n, NC, num_fg, q, partial, box_lo, grad_cls,
+                       grad_box);
+    return htd::check_launch("roi_head_loss_decoded");
 }
 
 extern "C" int htd_rpn_loss_partial_rows(void) { return RPN_LOSS_BLOCKS; }

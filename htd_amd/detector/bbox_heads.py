@@ -151,9 +151,16 @@ class BBoxHead(nn.Module):
         """num_samples (device scalar, optional): number of real rows when the batch carries unused sample slots
         (static-shape training path); rows with label_weight 0 are then excluded from `acc` as well."""
         if self._fused_loss_ok(cls_score, bbox_pred, reduction_override, num_samples):
-            loss_cls, acc, loss_bbox = _RoIHeadLoss.apply(cls_score, bbox_pred, labels, label_weights, bbox_targets, bbox_weights,
-                                                          num_samples, self.num_classes, float(self.loss_bbox.beta),
-                                                          float(self.loss_cls.loss_weight), float(self.loss_bbox.loss_weight))
+            lb = self.loss_bbox
+            if self.reg_decoded_bbox:
+                loss_cls, acc, loss_bbox = _RoIHeadLossDecoded.apply(
+                    cls_score, bbox_pred, rois[:, 1:], labels, label_weights, bbox_targets, bbox_weights, num_samples,
+                    self.num_classes, self.bbox_coder.means, self.bbox_coder.stds, int(lb.kind), float(lb.eps),
+                    float(getattr(lb, 'beta', 0.)), float(self.loss_cls.loss_weight), float(lb.loss_weight))
+            else:
+                loss_cls, acc, loss_bbox = _RoIHeadLoss.apply(cls_score, bbox_pred, labels, label_weights, bbox_targets, bbox_weights,
+                                                              num_samples, self.num_classes, float(lb.beta),
+                                                              float(self.loss_cls.loss_weight), float(lb.loss_weight))
             return dict(loss_cls=loss_cls, acc=acc, loss_bbox=loss_bbox)
         losses = dict()
         if cls_score is not None:
@@ -184,19 +191,24 @@ class BBoxHead(nn.Module):
                                                  num_samples.to(pred.dtype).clamp(min=1))
         return losses
 
-    fused_loss = True        # one kernel for cross-entropy + smooth-L1 + accuracy on the static-shape training path
+    fused_loss = True        # one kernel for cross-entropy + regression loss + accuracy on the static-shape training path
+
+    def fused_loss_config_ok(self):
+        """The part of _fused_loss_ok that the configuration alone decides: softmax cross-entropy without class weights and a
+        class-agnostic regressor with either smooth-L1 on encoded deltas or an IoU-family loss on decoded boxes, mean reductions."""
+        from .losses import DECODED_BOX_LOSSES, CrossEntropyLoss, SmoothL1Loss
+        lc, lb = self.loss_cls, self.loss_bbox
+        box_ok = type(lb) in DECODED_BOX_LOSSES if self.reg_decoded_bbox else type(lb) is SmoothL1Loss
+        return (self.reg_class_agnostic and box_ok and lb.reduction == 'mean' and type(lc) is CrossEntropyLoss and
+                not lc.use_sigmoid and lc.class_weight is None and lc.reduction == 'mean')
 
     def _fused_loss_ok(self, cls_score, bbox_pred, reduction_override, num_samples):
-        """The configuration of the HTD heads (softmax cross-entropy without class weights, class-agnostic smooth-L1 on
-        encoded deltas, mean reduction, static-shape batch): everything else keeps the tensor formulation below."""
-        from .losses import CrossEntropyLoss, SmoothL1Loss
-        lc, lb = self.loss_cls, self.loss_bbox
+        """The configurations of fused_loss_config_ok on a static-shape batch of fp32 device tensors: everything else keeps the
+        tensor formulation below."""
         return (self.fused_loss and cls_score is not None and bbox_pred is not None and num_samples is not None and
                 reduction_override is None and cls_score.is_cuda and cls_score.dtype == torch.float32 and cls_score.dim() == 2 and
                 0 < cls_score.size(0) and cls_score.size(1) <= 128 and bbox_pred.dtype == torch.float32 and
-                self.reg_class_agnostic and not self.reg_decoded_bbox and tuple(bbox_pred.shape) == (cls_score.size(0), 4) and
-                type(lc) is CrossEntropyLoss and not lc.use_sigmoid and lc.class_weight is None and lc.reduction == 'mean' and
-                type(lb) is SmoothL1Loss and lb.reduction == 'mean')
+                tuple(bbox_pred.shape) == (cls_score.size(0), 4) and self.fused_loss_config_ok())
 
     # ---------------------------------------------------------------- inference / refinement
     def get_bboxes(self, rois, cls_score, bbox_pred, img_shape, scale_factor, rescale=False, cfg=None):
@@ -245,6 +257,23 @@ class BBoxHead(nn.Module):
         return torch.cat((rois[:, [0]], bboxes), dim=1)
 
 
+def _finish_roi_head_loss(ctx, partial, gcls, gbox, num_samples, lw_cls, lw_box, box_lo=None):
+    """The scalar tail of both fused head losses: per-block partials -> loss_cls, acc, loss_bbox; the backward's scales saved.
+    box_lo (htd_roi_head_loss_decoded): low parts of the blocks' fp64 box sums; loss_bbox is then summed and scaled in fp64 and
+    rounded to fp32 once."""
+    sums = partial.sum(0)                                     # {sum w*CE, #(w > 0), sum weighted box loss, #correct}
+    avg = torch.stack([sums[1], num_samples.to(torch.float32).reshape(())]).clamp(min=1.)       # avg_factor of cls, of box / acc
+    scale = torch.stack([lw_cls / avg[0], lw_box / avg[1], 100.0 / avg[1]])
+    vals = torch.stack([sums[0], sums[2], sums[3]]) * scale   # loss_cls, loss_bbox, acc (no index upload: that copy waits)
+    loss_cls, loss_bbox, acc = vals[0], vals[1], vals[2:3]
+    if box_lo is not None:
+        total = (partial[:, 2].double() + box_lo.double()).sum()
+        loss_bbox = (total * (lw_box / num_samples.to(torch.float64).reshape(()).clamp(min=1.))).float()
+    ctx.save_for_backward(gcls, gbox, scale)
+    ctx.mark_non_differentiable(acc)
+    return loss_cls, acc, loss_bbox
+
+
 class _RoIHeadLoss(torch.autograd.Function):
     """BBoxHead.loss of the static-shape training path as one kernel (htd_roi_head_loss) plus a handful of scalar operations:
     -> dict(loss_cls, acc, loss_bbox) with the values of the tensor formulation (sums in another fixed order)."""
@@ -262,14 +291,7 @@ class _RoIHeadLoss(torch.autograd.Function):
         capi.call('htd_roi_head_loss', capi.ptr(cls), capi.ptr(labels.contiguous()), capi.ptr(label_weights.float().contiguous()),
                   capi.ptr(pred), capi.ptr(bbox_targets.float().contiguous()), capi.ptr(bbox_weights.float().contiguous()), n, NC,
                   int(num_fg), float(beta), capi.ptr(partial), capi.ptr(gcls), capi.ptr(gbox), capi.current_stream_ptr())
-        sums = partial.sum(0)                                     # {sum w*CE, #(w > 0), sum bw*SmoothL1, #correct}
-        avg = torch.stack([sums[1], num_samples.to(torch.float32).reshape(())]).clamp(min=1.)       # avg_factor of cls, of box / acc
-        scale = torch.stack([lw_cls / avg[0], lw_box / avg[1], 100.0 / avg[1]])
-        vals = torch.stack([sums[0], sums[2], sums[3]]) * scale   # loss_cls, loss_bbox, acc (no index upload: that copy waits)
-        loss_cls, loss_bbox, acc = vals[0], vals[1], vals[2:3]
-        ctx.save_for_backward(gcls, gbox, scale)
-        ctx.mark_non_differentiable(acc)
-        return loss_cls, acc, loss_bbox
+        return _finish_roi_head_loss(ctx, partial, gcls, gbox, num_samples, lw_cls, lw_box)
 
     @staticmethod
     def backward(ctx, g_cls, g_acc, g_box):
@@ -277,6 +299,38 @@ class _RoIHeadLoss(torch.autograd.Function):
         gc = gcls * (g_cls * scale[0]) if g_cls is not None else None
         gb = gbox * (g_box * scale[1]) if g_box is not None else None
         return gc, gb, None, None, None, None, None, None, None, None, None
+
+
+class _RoIHeadLossDecoded(torch.autograd.Function):
+    """_RoIHeadLoss for a head with reg_decoded_bbox: decode, IoU-family loss and the gradient with respect to the deltas in the
+    same single kernel (htd_roi_head_loss_decoded); bbox_targets are ground-truth boxes, rois (n, 4)."""
+
+    @staticmethod
+    def forward(ctx, cls_score, bbox_pred, rois, labels, label_weights, bbox_targets, bbox_weights, num_samples, num_fg, means,
+                stds, kind, eps, beta, lw_cls, lw_box):
+        from .. import capi
+        from ..core.bbox import _d4
+        n, NC = cls_score.shape
+        cls = cls_score.contiguous()
+        pred = bbox_pred.contiguous()
+        blocks = capi.lib().htd_roi_head_loss_partial_rows()
+        partial = torch.empty(blocks, 4, device=cls.device, dtype=torch.float32)
+        box_lo = torch.empty(blocks, device=cls.device, dtype=torch.float32)
+        gcls, gbox = torch.empty_like(cls), torch.empty_like(pred)
+        # converted operands stay referenced until the launch is queued
+        rois4, lab, lw = rois.float().contiguous(), labels.contiguous(), label_weights.float().contiguous()
+        tgt, bw = bbox_targets.float().contiguous(), bbox_weights.float().contiguous()
+        capi.call('htd_roi_head_loss_decoded', capi.ptr(cls), capi.ptr(lab), capi.ptr(lw), capi.ptr(rois4), capi.ptr(pred),
+                  capi.ptr(tgt), capi.ptr(bw), n, NC, int(num_fg), _d4(means), _d4(stds), float(16 / 1000), int(kind), float(eps),
+                  float(beta), capi.ptr(partial), capi.ptr(box_lo), capi.ptr(gcls), capi.ptr(gbox), capi.current_stream_ptr())
+        return _finish_roi_head_loss(ctx, partial, gcls, gbox, num_samples, lw_cls, lw_box, box_lo)
+
+    @staticmethod
+    def backward(ctx, g_cls, g_acc, g_box):
+        gcls, gbox, scale = ctx.saved_tensors
+        gc = gcls * (g_cls * scale[0]) if g_cls is not None else None
+        gb = gbox * (g_box * scale[1]) if g_box is not None else None
+        return (gc, gb) + (None, ) * 14
 
 
 @HEADS.register_module()

@@ -127,10 +127,11 @@ class HTDRoIHead(nn.Module):
 
     def _targets(self, stage, sampling_results, cfg):
         """BBoxHead.get_targets (bbox_head.py:85-139) for the whole batch in a handful of launches: rows are
-        [pos_i ; neg_i] per image, positives carry their gt label and encoded deltas, everything has weight 1
+        [pos_i ; neg_i] per image, positives carry their gt label and encoded deltas (their gt box for a head with
+        reg_decoded_bbox), everything has weight 1
         (pos_weight <= 0), negatives the background label."""
         head = self.bbox_head[stage]
-        if cfg.pos_weight > 0 or head.reg_decoded_bbox:
+        if cfg.pos_weight > 0:
             return head.get_targets(sampling_results, None, None, cfg)
         npos = [r.pos_bboxes.size(0) for r in sampling_results]
         nneg = [r.neg_bboxes.size(0) for r in sampling_results]
@@ -147,7 +148,9 @@ class HTDRoIHead(nn.Module):
         bbox_weights = pos_b.new_zeros(N, 4)
         if pos_rows.numel():
             labels[pos_rows] = torch.cat([r.pos_gt_labels for r in sampling_results])
-            bbox_targets[pos_rows] = head.bbox_coder.encode(pos_b, torch.cat([r.pos_gt_bboxes for r in sampling_results]))
+            pos_gt = torch.cat([r.pos_gt_bboxes for r in sampling_results])
+            # a head in decoded mode regresses against the gt box itself (bbox_head.py:118-124)
+            bbox_targets[pos_rows] = pos_gt if head.reg_decoded_bbox else head.bbox_coder.encode(pos_b, pos_gt)
             bbox_weights.index_fill_(0, pos_rows, 1.0)
         return labels, pos_b.new_ones(N), bbox_targets, bbox_weights
 
@@ -237,16 +240,23 @@ class HTDRoIHead(nn.Module):
             if a.ignore_iof_thr > 0 or not isinstance(a.neg_iou_thr, float) or type(smp).__name__ != 'RandomSampler':
                 return False
         h = self.bbox_head[0]
-        return h.reg_class_agnostic and h.bbox_coder.clip_border and not h.reg_decoded_bbox and \
-            all(c.pos_weight <= 0 for c in self.train_cfg)
+        # a head that regresses decoded boxes stays on this path when its loss is one the fused kernel takes (BBoxHead.loss);
+        # each stage decides for itself
+        if any(hd.reg_decoded_bbox and not hd.fused_loss_config_ok() for hd in self.bbox_head):
+            return False
+        return h.reg_class_agnostic and h.bbox_coder.clip_border and all(c.pos_weight <= 0 for c in self.train_cfg)
 
     def _static_targets(self, stage, S):
-        """bbox_head.get_targets (bbox_head.py:85-146) on fixed slots: unused slots carry weight 0."""
+        """bbox_head.get_targets (bbox_head.py:85-146) on fixed slots: unused slots carry weight 0.  A head with
+        reg_decoded_bbox gets the gt boxes of its positives instead of encoded deltas, zeros everywhere else."""
         head = self.bbox_head[stage]
         from ..core.bbox import roi_targets_device
-        return roi_targets_device(S.boxes.view(-1, 4), S.pos_gt_bboxes.view(-1, 4), S.pos_gt_labels.view(-1),
-                                  S.is_pos.view(-1), S.valid.view(-1), head.num_classes, head.bbox_coder.means,
-                                  head.bbox_coder.stds)
+        labels, lw, bt, bw = roi_targets_device(S.boxes.view(-1, 4), S.pos_gt_bboxes.view(-1, 4), S.pos_gt_labels.view(-1),
+                                                S.is_pos.view(-1), S.valid.view(-1), head.num_classes, head.bbox_coder.means,
+                                                head.bbox_coder.stds)
+        if head.reg_decoded_bbox:
+            bt = S.pos_gt_bboxes.view(-1, 4).float() * bw            # bw: 1 on the positives, 0 elsewhere
+        return labels, lw, bt, bw
 
     def forward_train_static(self, x, img_metas, proposals, n_keep, gt_bboxes, gt_labels):
         """forward_train (htd_roi_head.py:240-349) on fixed-size tensors: proposals (B,P,5) zero-padded past

@@ -1,7 +1,10 @@
-"""Losses of the HTD path: CrossEntropyLoss (softmax / sigmoid), SmoothL1Loss, accuracy.
-Reference: mmdet/models/losses/{cross_entropy_loss.py:9-202, smooth_l1_loss.py:8-94, utils.py:26-52,
-accuracy.py:4-48}.  Same constructor kwargs and forward signature (weight, avg_factor,
+"""Losses of the HTD path: CrossEntropyLoss (softmax / sigmoid), SmoothL1Loss, the IoU family on decoded boxes
+(IoULoss, BoundedIoULoss, GIoULoss, DIoULoss, CIoULoss), accuracy.
+Reference: mmdet/models/losses/{cross_entropy_loss.py:9-202, smooth_l1_loss.py:8-94, iou_loss.py:11-418,
+utils.py:26-52, accuracy.py:4-48}.  Same constructor kwargs and forward signature (weight, avg_factor,
 reduction_override)."""
+import math
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -76,6 +79,137 @@ class SmoothL1Loss(nn.Module):
         reduction = reduction_override if reduction_override else self.reduction
         return self.loss_weight * smooth_l1_loss(pred, target, weight, beta=self.beta, reduction=reduction,
                                                  avg_factor=avg_factor, **kwargs)
+
+
+# ---------------------------------------------------------------- IoU family (iou_loss.py), per-row losses on (n, 4) boxes
+def iou_loss(pred, target, eps=1e-6):
+    """-log(IoU) in the reference's own edit (iou_loss.py:27-29): IoUs of at most 0.1 are lifted by 0.1 before the log."""
+    from ..core.bbox import bbox_overlaps
+    ious = bbox_overlaps(pred, target, is_aligned=True).clamp(min=eps)
+    ious = torch.where(ious > 0.1, ious, 0.1 + ious)
+    return -ious.log()
+
+
+def bounded_iou_loss(pred, target, beta=0.2, eps=1e-3):
+    """iou_loss.py:34-75 -> (n, 4): smooth-L1 of the bounded IoU of centre x / y and width / height."""
+    pred_ctrx, pred_ctry = (pred[:, 0] + pred[:, 2]) * 0.5, (pred[:, 1] + pred[:, 3]) * 0.5
+    pred_w, pred_h = pred[:, 2] - pred[:, 0], pred[:, 3] - pred[:, 1]
+    with torch.no_grad():
+        target_ctrx, target_ctry = (target[:, 0] + target[:, 2]) * 0.5, (target[:, 1] + target[:, 3]) * 0.5
+        target_w, target_h = target[:, 2] - target[:, 0], target[:, 3] - target[:, 1]
+    dx, dy = target_ctrx - pred_ctrx, target_ctry - pred_ctry
+    loss_dx = 1 - torch.max((target_w - 2 * dx.abs()) / (target_w + 2 * dx.abs() + eps), torch.zeros_like(dx))
+    loss_dy = 1 - torch.max((target_h - 2 * dy.abs()) / (target_h + 2 * dy.abs() + eps), torch.zeros_like(dy))
+    loss_dw = 1 - torch.min(target_w / (pred_w + eps), pred_w / (target_w + eps))
+    loss_dh = 1 - torch.min(target_h / (pred_h + eps), pred_h / (target_h + eps))
+    loss_comb = torch.stack([loss_dx, loss_dy, loss_dw, loss_dh], dim=-1).view(loss_dx.size(0), -1)
+    return torch.where(loss_comb < beta, 0.5 * loss_comb * loss_comb / beta, loss_comb - 0.5 * beta)
+
+
+def giou_loss(pred, target, eps=1e-7):
+    from ..core.bbox import bbox_overlaps
+    return 1 - bbox_overlaps(pred, target, mode='giou', is_aligned=True, eps=eps)
+
+
+def _iou_and_centre_term(pred, target, eps):
+    """The part diou_loss and ciou_loss share (iou_loss.py:112-143, 167-201): IoU with eps added to the union, and the squared
+    centre distance over the squared diagonal of the enclosing box (eps added)."""
+    wh = (torch.min(pred[:, 2:], target[:, 2:]) - torch.max(pred[:, :2], target[:, :2])).clamp(min=0)
+    overlap = wh[:, 0] * wh[:, 1]
+    ap = (pred[:, 2] - pred[:, 0]) * (pred[:, 3] - pred[:, 1])
+    ag = (target[:, 2] - target[:, 0]) * (target[:, 3] - target[:, 1])
+    ious = overlap / (ap + ag - overlap + eps)
+    enclose_wh = (torch.max(pred[:, 2:], target[:, 2:]) - torch.min(pred[:, :2], target[:, :2])).clamp(min=0)
+    c2 = enclose_wh[:, 0]**2 + enclose_wh[:, 1]**2 + eps
+    left = ((target[:, 0] + target[:, 2]) - (pred[:, 0] + pred[:, 2]))**2 / 4
+    right = ((target[:, 1] + target[:, 3]) - (pred[:, 1] + pred[:, 3]))**2 / 4
+    return ious, (left + right) / c2
+
+
+def diou_loss(pred, target, eps=1e-7):
+    ious, centre = _iou_and_centre_term(pred, target, eps)
+    return 1 - (ious - centre)
+
+
+def ciou_loss(pred, target, eps=1e-7):
+    ious, centre = _iou_and_centre_term(pred, target, eps)
+    w1, h1 = pred[:, 2] - pred[:, 0], pred[:, 3] - pred[:, 1] + eps          # eps on the heights only (iou_loss.py:196-197)
+    w2, h2 = target[:, 2] - target[:, 0], target[:, 3] - target[:, 1] + eps
+    v = (4 / math.pi**2) * torch.pow(torch.atan(w2 / h2) - torch.atan(w1 / h1), 2)
+    # v == 0 makes the aspect term 0 with zero slope.  With pred == target (a gt-born positive with zero deltas) the fp32 IoU
+    # rounds to 1 and the reference divides 0 by 0 there; the limit is taken instead (what its fp64 run gives), so every per-row
+    # loss of finite boxes is finite and a zero weight really removes the row.  Everywhere else this is the same arithmetic.
+    den = torch.where(v > 0, 1 - ious + v, torch.ones_like(v))
+    return 1 - (ious - (centre + v**2 / den))
+
+
+class _BoxLoss(nn.Module):
+    """Common forward of the five modules (iou_loss.py:212-418).  The reference leaves early with (pred * weight).sum() when no
+    weight is positive, which costs a host sync (`torch.any`); the weighted sum below gives the same exact 0 with zero
+    gradients because every per-row loss of finite boxes is finite, so it is not reproduced."""
+    per_row = True          # loss of shape (n,): an (n, 4) weight is reduced to its row mean
+
+    def __init__(self, eps=1e-6, reduction='mean', loss_weight=1.0):
+        super().__init__()
+        self.eps, self.reduction, self.loss_weight = eps, reduction, loss_weight
+
+    def _loss(self, pred, target):
+        raise NotImplementedError
+
+    def forward(self, pred, target, weight=None, avg_factor=None, reduction_override=None, **kwargs):
+        assert reduction_override in (None, 'none', 'mean', 'sum')
+        reduction = reduction_override if reduction_override else self.reduction
+        if self.per_row and weight is not None and weight.dim() > 1:
+            assert weight.shape == pred.shape
+            weight = weight.mean(-1)
+        return self.loss_weight * weight_reduce_loss(self._loss(pred, target), weight, reduction, avg_factor)
+
+
+@LOSSES.register_module()
+class IoULoss(_BoxLoss):
+    kind = 0
+
+    def _loss(self, pred, target):
+        return iou_loss(pred, target, eps=self.eps)
+
+
+@LOSSES.register_module()
+class BoundedIoULoss(_BoxLoss):
+    kind, per_row = 1, False
+
+    def __init__(self, beta=0.2, eps=1e-3, reduction='mean', loss_weight=1.0):
+        super().__init__(eps, reduction, loss_weight)
+        self.beta = beta
+
+    def _loss(self, pred, target):
+        return bounded_iou_loss(pred, target, beta=self.beta, eps=self.eps)
+
+
+@LOSSES.register_module()
+class GIoULoss(_BoxLoss):
+    kind = 2
+
+    def _loss(self, pred, target):
+        return giou_loss(pred, target, eps=self.eps)
+
+
+@LOSSES.register_module()
+class DIoULoss(_BoxLoss):
+    kind = 3
+
+    def _loss(self, pred, target):
+        return diou_loss(pred, target, eps=self.eps)
+
+
+@LOSSES.register_module()
+class CIoULoss(_BoxLoss):
+    kind = 4
+
+    def _loss(self, pred, target):
+        return ciou_loss(pred, target, eps=self.eps)
+
+
+DECODED_BOX_LOSSES = (IoULoss, BoundedIoULoss, GIoULoss, DIoULoss, CIoULoss)       # index = `kind` of htd_roi_head_loss_decoded
 
 
 def accuracy(pred, target, topk=1, thresh=None):

@@ -129,6 +129,15 @@ def _merge(base, child):
     for k, v in child.items():
         if isinstance(v, dict) and isinstance(out.get(k), dict) and not v.get('_delete_', False):
             out[k] = _merge(out[k], v)
+        elif isinstance(v, dict) and v and isinstance(out.get(k), (list, tuple)) and all(str(i).isdigit() for i in v):
+            # mmcv's allow_list_keys: `--cfg-options model.roi_head.bbox_head.1.reg_decoded_bbox=True` reaches into a list
+            items = list(out[k])
+            for i, sub in v.items():
+                i = int(i)
+                if i >= len(items):
+                    raise KeyError(f'Index {i} exceeds the length of list {k} ({len(items)})')
+                items[i] = _merge({'_': items[i]}, {'_': sub})['_']
+            out[k] = type(out[k])(items)
         else:
             if isinstance(v, dict):
                 v = {a: b for a, b in v.items() if a != '_delete_'}

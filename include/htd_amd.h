@@ -32,7 +32,7 @@ extern "C" {
 const char *htd_last_error(void);
 /* ABI version, bumped on any signature change (added entry points do not bump it).  A binding compares
  * htd_abi_version() of the loaded library with the HTD_ABI_VERSION of the header it was written against. */
-#define HTD_ABI_VERSION 5
+#define HTD_ABI_VERSION 6
 int htd_abi_version(void);
 
 /* ------------------------------------------------------------------------------------
@@ -558,6 +558,22 @@ int htd_roi_head_loss_partial_rows(void);
 int htd_roi_head_loss(const float *cls_score, const int64_t *labels, const float *label_weights, const float *bbox_pred,
                       const float *bbox_targets, const float *bbox_weights, int64_t n, int NC, int num_fg, float beta,
                       float *partial, float *grad_cls, float *grad_box, void *stream);
+/* BBoxHead.loss of a head with reg_decoded_bbox=True (bbox_heads/bbox_head.py:148-186) in one pass: the classification half
+ * of htd_roi_head_loss (the same device code: loss_cls, acc and grad_cls are bitwise those), and the regression loss taken on
+ * the decoded box delta2bbox(rois, bbox_pred) (core/bbox/coder/delta_xywh_bbox_coder.py:123-204 with max_shape=None: dw / dh
+ * clamped to +-|log(wh_ratio_clip)|, no border clip) against the ground-truth box bbox_targets [n][4] by one of
+ * losses/iou_loss.py: kind 0 iou_loss (the reference's edited form), 1 bounded_iou_loss (beta; per-component weights),
+ * 2 giou_loss, 3 diou_loss, 4 ciou_loss, with the module's eps; an [n][4] weight counts with its row mean for kinds 0, 2, 3, 4.
+ * rois [n][4] (no batch column).  The box side is evaluated in fp64 from the fp32 operands (means4 / stds4 / eps / beta are
+ * doubles: the module's values unrounded).  partial as htd_roi_head_loss, with the high part of the block's weighted box-loss sum
+ * in column 2 and its low part in box_lo [htd_roi_head_loss_partial_rows()]: block sum = (double)partial[b][2] + box_lo[b], so
+ * the caller can round the summed loss once.  grad_box [n][4] = d(sum)/d(bbox_pred), through the decode (0 for a clamped
+ * dw / dh).  Rows with a background label or all-zero weights are not evaluated on the box side and get exact zeros.  Same
+ * fixed grid, no atomics: reproducible. */
+int htd_roi_head_loss_decoded(const float *cls_score, const int64_t *labels, const float *label_weights, const float *rois,
+                              const float *bbox_pred, const float *bbox_targets, const float *bbox_weights, int64_t n, int NC,
+                              int num_fg, const double *means4, const double *stds4, double wh_ratio_clip, int kind, double eps,
+                              double beta, float *partial, float *box_lo, float *grad_cls, float *grad_box, void *stream);
 int htd_rpn_loss_partial_rows(void);
 int htd_rpn_loss(const float *cls, const float *reg, const float *anchors, const float *gts, const int64_t *assigned,
                  const uint8_t *pos, const uint8_t *neg, int B, int A, int K, const float *means4, const float *stds4,
