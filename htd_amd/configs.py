@@ -2,6 +2,10 @@
 R101 / R101-DCN siblings htd_resnet101_2x.py, htd_resnet101_dcn_2x_mstrain.py:139-150), produced
 programmatically so the package carries no config files of its own.  The reference's config *files*
 load unchanged through `htd_amd.Config.fromfile` (same `type=` names and kwargs).
+
+The two baselines HTD is measured against come the same way: faster_rcnn_config (configs/faster_rcnn/
+faster_rcnn_r50_fpn_1x_coco.py) and cascade_rcnn_config (configs/cascade_rcnn/cascade_rcnn_r50_fpn_1x_coco.py), with
+their `_base_` chains merged.
 """
 import copy
 
@@ -72,6 +76,62 @@ def htd_test_cfg(soft_nms=False):
     return dict(rpn=dict(nms_across_levels=False, nms_pre=1000, nms_post=1000, max_num=1000, nms_thr=0.7,
                          min_bbox_size=0),
                 rcnn=dict(score_thr=0.05, nms=nms, max_per_img=100))
+
+
+def _baseline_model(kind, depth, roi_head, rpn_loss_bbox):
+    model = htd_model(depth)
+    model.update(type=kind, pretrained=f'torchvision://resnet{depth}', roi_head=roi_head)
+    model['rpn_head']['loss_bbox'] = rpn_loss_bbox
+    return model
+
+
+def _single_extractor():
+    return dict(type='SingleRoIExtractor', roi_layer=dict(type='RoIAlign', output_size=7, sampling_ratio=0), out_channels=256,
+                featmap_strides=[4, 8, 16, 32])
+
+
+def faster_rcnn_model(depth=50):
+    """configs/_base_/models/faster_rcnn_r50_fpn.py: L1 regression in the RPN and in a class-specific Shared2FCBBoxHead."""
+    l1 = dict(type='L1Loss', loss_weight=1.0)
+    head = _bbox_head('Shared2FCBBoxHead', [0.1, 0.1, 0.2, 0.2], reg_class_agnostic=False, loss_bbox=dict(l1))
+    return _baseline_model('FasterRCNN', depth, dict(type='StandardRoIHead', bbox_roi_extractor=_single_extractor(),
+                                                     bbox_head=head), dict(l1))
+
+
+def cascade_rcnn_model(depth=50):
+    """configs/_base_/models/cascade_rcnn_r50_fpn.py: three class-agnostic stages with tightening target_stds."""
+    heads = [_bbox_head('Shared2FCBBoxHead', stds) for stds in ([0.1, 0.1, 0.2, 0.2], [0.05, 0.05, 0.1, 0.1],
+                                                                [0.033, 0.033, 0.067, 0.067])]
+    return _baseline_model('CascadeRCNN', depth,
+                           dict(type='CascadeRoIHead', num_stages=3, stage_loss_weights=[1, 0.5, 0.25],
+                                bbox_roi_extractor=_single_extractor(), bbox_head=heads),
+                           dict(type='SmoothL1Loss', beta=1.0 / 9.0, loss_weight=1.0))
+
+
+def _baseline_config(model, train_cfg, depth):
+    if depth not in (50, 101):
+        raise ValueError(f'baseline configs exist for ResNet-50 and ResNet-101, got depth={depth!r}')
+    return ConfigDict(
+        model=model, train_cfg=train_cfg, test_cfg=htd_test_cfg(False), data=htd_data(50),
+        evaluation=dict(interval=1, metric='bbox'),
+        optimizer=dict(type='SGD', lr=0.02, momentum=0.9, weight_decay=0.0001), optimizer_config=dict(grad_clip=None),
+        lr_config=dict(policy='step', warmup='linear', warmup_iters=500, warmup_ratio=0.001, step=[8, 11]), total_epochs=12)
+
+
+def faster_rcnn_config(depth=50):
+    """faster_rcnn_r{depth}_fpn_1x_coco: the RPN ignores no border anchors (allowed_border=-1) and hands on 1000 proposals."""
+    train_cfg = htd_train_cfg()
+    train_cfg['rpn']['allowed_border'] = -1
+    train_cfg['rpn_proposal'].update(nms_post=1000, max_num=1000)
+    train_cfg['rcnn'] = _rcnn(0.5)
+    return _baseline_config(faster_rcnn_model(depth), train_cfg, depth)
+
+
+def cascade_rcnn_config(depth=50):
+    """cascade_rcnn_r{depth}_fpn_1x_coco: IoU thresholds 0.5 / 0.6 / 0.7 over the three stages."""
+    train_cfg = htd_train_cfg()
+    train_cfg['rcnn'] = [_rcnn(0.5), _rcnn(0.6), _rcnn(0.7)]
+    return _baseline_config(cascade_rcnn_model(depth), train_cfg, depth)
 
 
 IMG_NORM_CFG = dict(mean=[123.675, 116.28, 103.53], std=[58.395, 57.12, 57.375], to_rgb=True)
@@ -176,8 +236,24 @@ def build_htd_detector(depth=50, dcn=False, cfg=None, bf16=False, resnext=False)
             # property of THIS model (runner.Trainer applies it around its steps), not of the process.
             model.overlap_wgrad = False
         model.backbone.compute_dtype = torch.bfloat16
-        for head in model.roi_head.bbox_head:          # the 12544->1024->1024 FC stacks of both stages
+        heads = model.roi_head.bbox_head
+        for head in (heads if isinstance(heads, torch.nn.ModuleList) else [heads]):      # the 12544->1024->1024 FC stacks of every stage
             head.compute_dtype = torch.bfloat16
             for m in getattr(head, 'convs', []):       # and the 3x3 stack of the regression branch (GroupNorm stays fp32)
                 m.compute_dtype = torch.bfloat16
     return model
+
+
+def build_baseline_detector(kind='faster_rcnn', depth=50, cfg=None, bf16=False):
+    """kind = 'faster_rcnn' | 'cascade_rcnn' -> the detector of faster_rcnn_config / cascade_rcnn_config (or of `cfg`), with
+    the `pretrained` URL of the reference's config dropped: weights come from a checkpoint or from init_weights.  bf16 as in
+    build_htd_detector."""
+    makers = dict(faster_rcnn=faster_rcnn_config, cascade_rcnn=cascade_rcnn_config)
+    if cfg is None:
+        if kind not in makers:
+            raise ValueError(f'build_baseline_detector: kind must be one of {sorted(makers)}, got {kind!r}')
+        cfg = makers[kind](depth)
+    cfg = copy.deepcopy(cfg)
+    if str(cfg.model.get('pretrained') or '').startswith('torchvision://'):
+        cfg.model.pretrained = None
+    return build_htd_detector(cfg=cfg, bf16=bf16)

@@ -283,12 +283,24 @@ namespace {
 
 constexpr int RPN_LOSS_BLOCKS = 1024;
 
+// One component of the regression loss, shared by the RPN and the RoI-head kernels: -> loss, g = d(loss)/d(pred).
+template <bool L1>
+__device__ __forceinline__ float box_elem_loss(float d, float beta, float &g)
+{
+    const float ad = fabsf(d);
+    if (!L1 && ad < beta) { g = d / beta; return 0.5f * ad * ad / beta; }
+    g = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
+    return L1 ? ad : ad - 0.5f * beta;
+}
+
 // RPN loss of the whole batch in one pass (anchor_head.py:373-418 loss_single summed over levels and images, with
 // the targets of _get_targets_single :172-269 formed on the fly): per anchor row
 //   cls:  w * BCEWithLogits(x, t),  t = 1 on sampled positives, w = 1 (pos_weight on positives) on sampled rows
 //   box:  SmoothL1_beta(reg - bbox2delta(anchor, gt[assigned-1])) summed over 4, on sampled positives
 // and, in the same pass, d(sum)/dx and d(sum)/dreg (the backward only scales them).  Sums are written as per-block
 // partials in a fixed grid and reduced in a fixed order afterwards (bitwise reproducible).
+// L1 (htd_rpn_loss_l1): |d| in place of SmoothL1_beta (smooth_l1_loss.py:29-44), slope sign(d) with 0 at d == 0; beta unused.
+template <bool L1>
 __global__ __launch_bounds__(256) void rpn_loss_kernel(const float *__restrict__ cls, const float *__restrict__ reg,
                                                        const float *__restrict__ anchors,
                                                        const float *__restrict__ gts,
@@ -326,11 +338,7 @@ __global__ __launch_bounds__(256) void rpn_loss_kernel(const float *__restrict__
             const float rr[4] = {r.x, r.y, r.z, r.w};
             float go[4];
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const float d = rr[k] - tgt[k], ad = fabsf(d);
-                if (ad < beta) { s_box += 0.5f * ad * ad / beta; go[k] = d / beta; }
-                else { s_box += ad - 0.5f * beta; go[k] = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f); }
-            }
+            for (int k = 0; k < 4; ++k) s_box += box_elem_loss<L1>(rr[k] - tgt[k], beta, go[k]);
             gr = make_float4(go[0], go[1], go[2], go[3]);
         }
         gcls[i] = gx;
@@ -428,6 +436,50 @@ __global__ __launch_bounds__(256) void roi_head_loss_kernel(const float *__restr
             l += __shfl_xor(l, 1, 64);
             l += __shfl_xor(l, 2, 64);
             if (lane == 0) s_box += l;
+        }
+    }
+    roi_loss_store_partial(red, lane, wave, s_ce, s_w, s_box, s_hit, partial);
+}
+
+// roi_head_loss_kernel for a class-specific regressor (bbox_head.py:165-183 with reg_class_agnostic=False) and for L1Loss:
+// pred / gbox are [n][4 * reg_classes]; a foreground row with label c is compared through its columns 4c..4c+3 (columns 0..3
+// when reg_classes == 1).  The row's wavefront writes the WHOLE gbox row -- zeros outside those four columns, zeros everywhere
+// on background rows -- so the caller clears nothing and no two waves touch the same element.  The four loss terms are formed
+// and added exactly as in roi_head_loss_kernel (lanes 0..3, two shuffles), so reg_classes == 1 with smooth-L1 is that kernel
+// bit for bit.
+template <bool L1>
+__global__ __launch_bounds__(256) void roi_head_loss_classes_kernel(const float *__restrict__ cls, const int64_t *__restrict__ labels,
+                                                                    const float *__restrict__ lw, const float *__restrict__ pred,
+                                                                    const float *__restrict__ tgt, const float *__restrict__ bw,
+                                                                    int64_t n, int NC, int num_fg, int reg_classes, float beta,
+                                                                    float *__restrict__ partial, float *__restrict__ gcls,
+                                                                    float *__restrict__ gbox)
+{
+    __shared__ float red[4][4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int cols = 4 * reg_classes;
+    float s_ce = 0.f, s_w = 0.f, s_box = 0.f, s_hit = 0.f;               // lane 0 of the wave keeps the running sums
+    for (int64_t i = (int64_t)blockIdx.x * 4 + wave; i < n; i += (int64_t)gridDim.x * 4) {
+        const int64_t lab = roi_cls_row(cls, labels, lw, i, NC, lane, gcls, s_ce, s_w, s_hit);
+        const bool fg = lab >= 0 && lab < num_fg;
+        const int c4 = (fg && reg_classes > 1) ? 4 * (int)lab : 0;       // fg => lab < num_fg == reg_classes: inside the row
+        float l = 0.f, g = 0.f;
+        if (lane < 4) {
+            const float wk = fg ? bw[i * 4 + lane] : 0.f;
+            const float e = box_elem_loss<L1>(pred[i * cols + c4 + lane] - tgt[i * 4 + lane], beta, g);
+            l = wk * e;
+            g = wk * g;
+        }
+        l += __shfl_xor(l, 1, 64);
+        l += __shfl_xor(l, 2, 64);
+        if (lane == 0) s_box += l;
+        // the row of gbox: lane k holds column c4 + k (k < 4); every other column is zero
+        float *grow = gbox + i * cols;
+        for (int c0 = 0; c0 < cols; c0 += 64) {                          // wave-uniform trip count: every lane takes the shuffle
+            const int c = c0 + lane, k = c - c4;
+            const bool mine = k >= 0 && k < 4;
+            const float v = __shfl(g, mine ? k : 0, 64);
+            if (c < cols) grow[c] = (fg && mine) ? v : 0.f;
         }
     }
     roi_loss_store_partial(red, lane, wave, s_ce, s_w, s_box, s_hit, partial);
@@ -667,6 +719,32 @@ extern "C" int htd_roi_head_loss_decoded(const float *cls_score, const int64_t *
     return htd::check_launch("roi_head_loss_decoded");
 }
 
+// htd_roi_head_loss with a regressor of reg_classes box columns per row (1: class-agnostic, num_fg: one box per foreground
+// class, bbox_pred / grad_box [n][4 * reg_classes]) and box_loss 0 = SmoothL1_beta (beta > 0), 1 = L1 (beta ignored).
+// grad_box is written in full, zeros included.
+extern "C" int htd_roi_head_loss_classes(const float *cls_score, const int64_t *labels, const float *label_weights,
+                                         const float *bbox_pred, const float *bbox_targets, const float *bbox_weights, int64_t n,
+                                         int NC, int num_fg, int reg_classes, int box_loss, float beta, float *partial,
+                                         float *grad_cls, float *grad_box, void *stream)
+{
+    HTD_REQUIRE(n > 0 && NC > 0 && NC <= 128 && num_fg >= 0 && num_fg <= NC, "roi_head_loss_classes: bad sizes n=%lld NC=%d num_fg=%d",
+                (long long)n, NC, num_fg);
+    HTD_REQUIRE(reg_classes == 1 || (reg_classes == num_fg && num_fg > 0), "roi_head_loss_classes: reg_classes=%d is neither 1 nor num_fg=%d",
+                reg_classes, num_fg);
+    HTD_REQUIRE(box_loss == 1 || (box_loss == 0 && beta > 0.f), "roi_head_loss_classes: bad loss box_loss=%d beta=%g", box_loss, (double)beta);
+    HTD_REQUIRE(cls_score && labels && label_weights && bbox_pred && bbox_targets && bbox_weights && partial && grad_cls && grad_box,
+                "roi_head_loss_classes: null pointer");
+    if (box_loss == 1)
+        hipLaunchKernelGGL(roi_head_loss_classes_kernel<true>, dim3(ROI_LOSS_BLOCKS), dim3(256), 0, (hipStream_t)stream, cls_score, labels,
+                           label_weights, bbox_pred, bbox_targets, bbox_weights, n, NC, num_fg, reg_classes, beta, partial, grad_cls,
+                           grad_box);
+    else
+        hipLaunchKernelGGL(roi_head_loss_classes_kernel<false>, dim3(ROI_LOSS_BLOCKS), dim3(256), 0, (hipStream_t)stream, cls_score, labels,
+                           label_weights, bbox_pred, bbox_targets, bbox_weights, n, NC, num_fg, reg_classes, beta, partial, grad_cls,
+                           grad_box);
+    return htd::check_launch("roi_head_loss_classes");
+}
+
 extern "C" int htd_rpn_loss_partial_rows(void) { return RPN_LOSS_BLOCKS; }
 
 extern "C" int htd_rpn_loss(const float *cls, const float *reg, const float *anchors, const float *gts,
@@ -679,10 +757,28 @@ extern "C" int htd_rpn_loss(const float *cls, const float *reg, const float *anc
                     grad_reg, "rpn_loss: null pointer");
     Vec4 m, sd;
     for (int k = 0; k < 4; ++k) { m.v[k] = means4[k]; sd.v[k] = stds4[k]; }
-    hipLaunchKernelGGL(rpn_loss_kernel, dim3(RPN_LOSS_BLOCKS), dim3(256), 0, (hipStream_t)stream, cls, reg, anchors,
+    hipLaunchKernelGGL(rpn_loss_kernel<false>, dim3(RPN_LOSS_BLOCKS), dim3(256), 0, (hipStream_t)stream, cls, reg, anchors,
                        gts, assigned, pos, neg, (int64_t)B * A, A, K, m, sd, beta, pos_weight, partial, grad_cls,
                        grad_reg);
     return htd::check_launch("rpn_loss");
+}
+
+// htd_rpn_loss with L1Loss on the encoded deltas (the RPN of the Faster R-CNN / Cascade R-CNN configurations): the same kernel,
+// |d| in place of SmoothL1.
+extern "C" int htd_rpn_loss_l1(const float *cls, const float *reg, const float *anchors, const float *gts,
+                               const int64_t *assigned, const uint8_t *pos, const uint8_t *neg, int B, int A, int K,
+                               const float *means4, const float *stds4, float pos_weight, float *partial,
+                               float *grad_cls, float *grad_reg, void *stream)
+{
+    HTD_REQUIRE(B > 0 && A > 0 && K > 0, "rpn_loss_l1: bad sizes");
+    HTD_REQUIRE(cls && reg && anchors && gts && assigned && pos && neg && means4 && stds4 && partial && grad_cls &&
+                    grad_reg, "rpn_loss_l1: null pointer");
+    Vec4 m, sd;
+    for (int k = 0; k < 4; ++k) { m.v[k] = means4[k]; sd.v[k] = stds4[k]; }
+    hipLaunchKernelGGL(rpn_loss_kernel<true>, dim3(RPN_LOSS_BLOCKS), dim3(256), 0, (hipStream_t)stream, cls, reg, anchors,
+                       gts, assigned, pos, neg, (int64_t)B * A, A, K, m, sd, 0.f, pos_weight, partial, grad_cls,
+                       grad_reg);
+    return htd::check_launch("rpn_loss_l1");
 }
 
 

@@ -151,16 +151,22 @@ class BBoxHead(nn.Module):
         """num_samples (device scalar, optional): number of real rows when the batch carries unused sample slots
         (static-shape training path); rows with label_weight 0 are then excluded from `acc` as well."""
         if self._fused_loss_ok(cls_score, bbox_pred, reduction_override, num_samples):
+            from .losses import L1Loss, SmoothL1Loss
             lb = self.loss_bbox
             if self.reg_decoded_bbox:
                 loss_cls, acc, loss_bbox = _RoIHeadLossDecoded.apply(
                     cls_score, bbox_pred, rois[:, 1:], labels, label_weights, bbox_targets, bbox_weights, num_samples,
                     self.num_classes, self.bbox_coder.means, self.bbox_coder.stds, int(lb.kind), float(lb.eps),
                     float(getattr(lb, 'beta', 0.)), float(self.loss_cls.loss_weight), float(lb.loss_weight))
-            else:
+            elif self.reg_class_agnostic and type(lb) is SmoothL1Loss:
                 loss_cls, acc, loss_bbox = _RoIHeadLoss.apply(cls_score, bbox_pred, labels, label_weights, bbox_targets, bbox_weights,
                                                               num_samples, self.num_classes, float(lb.beta),
                                                               float(self.loss_cls.loss_weight), float(lb.loss_weight))
+            else:       # one box per class and / or L1Loss
+                loss_cls, acc, loss_bbox = _RoIHeadLossClasses.apply(
+                    cls_score, bbox_pred, labels, label_weights, bbox_targets, bbox_weights, num_samples, self.num_classes,
+                    1 if self.reg_class_agnostic else self.num_classes, int(type(lb) is L1Loss), float(getattr(lb, 'beta', 0.)),
+                    float(self.loss_cls.loss_weight), float(lb.loss_weight))
             return dict(loss_cls=loss_cls, acc=acc, loss_bbox=loss_bbox)
         losses = dict()
         if cls_score is not None:
@@ -194,12 +200,16 @@ class BBoxHead(nn.Module):
     fused_loss = True        # one kernel for cross-entropy + regression loss + accuracy on the static-shape training path
 
     def fused_loss_config_ok(self):
-        """The part of _fused_loss_ok that the configuration alone decides: softmax cross-entropy without class weights and a
-        class-agnostic regressor with either smooth-L1 on encoded deltas or an IoU-family loss on decoded boxes, mean reductions."""
-        from .losses import DECODED_BOX_LOSSES, CrossEntropyLoss, SmoothL1Loss
+        """The part of _fused_loss_ok that the configuration alone decides: softmax cross-entropy without class weights and either
+        smooth-L1 / L1 on encoded deltas (class-agnostic or one box per class) or an IoU-family loss on the decoded boxes of a
+        class-agnostic regressor, mean reductions."""
+        from .losses import DECODED_BOX_LOSSES, CrossEntropyLoss, L1Loss, SmoothL1Loss
         lc, lb = self.loss_cls, self.loss_bbox
-        box_ok = type(lb) in DECODED_BOX_LOSSES if self.reg_decoded_bbox else type(lb) is SmoothL1Loss
-        return (self.reg_class_agnostic and box_ok and lb.reduction == 'mean' and type(lc) is CrossEntropyLoss and
+        if self.reg_decoded_bbox:
+            box_ok = self.reg_class_agnostic and type(lb) in DECODED_BOX_LOSSES
+        else:
+            box_ok = (type(lb) is SmoothL1Loss and lb.beta > 0) or type(lb) is L1Loss
+        return (box_ok and lb.reduction == 'mean' and type(lc) is CrossEntropyLoss and
                 not lc.use_sigmoid and lc.class_weight is None and lc.reduction == 'mean')
 
     def _fused_loss_ok(self, cls_score, bbox_pred, reduction_override, num_samples):
@@ -207,8 +217,10 @@ class BBoxHead(nn.Module):
         tensor formulation below."""
         return (self.fused_loss and cls_score is not None and bbox_pred is not None and num_samples is not None and
                 reduction_override is None and cls_score.is_cuda and cls_score.dtype == torch.float32 and cls_score.dim() == 2 and
-                0 < cls_score.size(0) and cls_score.size(1) <= 128 and bbox_pred.dtype == torch.float32 and
-                tuple(bbox_pred.shape) == (cls_score.size(0), 4) and self.fused_loss_config_ok())
+                0 < cls_score.size(0) and cls_score.size(1) <= 128 and cls_score.size(1) == self.num_classes + 1 and
+                bbox_pred.dtype == torch.float32 and
+                tuple(bbox_pred.shape) == (cls_score.size(0), 4 if self.reg_class_agnostic else 4 * self.num_classes) and
+                self.fused_loss_config_ok())
 
     # ---------------------------------------------------------------- inference / refinement
     def get_bboxes(self, rois, cls_score, bbox_pred, img_shape, scale_factor, rescale=False, cfg=None):
@@ -299,6 +311,36 @@ class _RoIHeadLoss(torch.autograd.Function):
         gc = gcls * (g_cls * scale[0]) if g_cls is not None else None
         gb = gbox * (g_box * scale[1]) if g_box is not None else None
         return gc, gb, None, None, None, None, None, None, None, None, None
+
+
+class _RoIHeadLossClasses(torch.autograd.Function):
+    """_RoIHeadLoss for a regressor with one box per foreground class (bbox_pred (n, 4 * num_fg)) and / or L1Loss
+    (htd_roi_head_loss_classes): the kernel writes every element of the (n, 4 * reg_classes) gradient itself."""
+
+    @staticmethod
+    def forward(ctx, cls_score, bbox_pred, labels, label_weights, bbox_targets, bbox_weights, num_samples, num_fg, reg_classes,
+                box_loss, beta, lw_cls, lw_box):
+        from .. import capi
+        n, NC = cls_score.shape
+        cls = cls_score.contiguous()
+        pred = bbox_pred.contiguous()
+        blocks = capi.lib().htd_roi_head_loss_partial_rows()
+        partial = torch.empty(blocks, 4, device=cls.device, dtype=torch.float32)
+        gcls, gbox = torch.empty_like(cls), torch.empty_like(pred)
+        # converted operands stay referenced until the launch is queued
+        lab, lw = labels.contiguous(), label_weights.float().contiguous()
+        tgt, bw = bbox_targets.float().contiguous(), bbox_weights.float().contiguous()
+        capi.call('htd_roi_head_loss_classes', capi.ptr(cls), capi.ptr(lab), capi.ptr(lw), capi.ptr(pred), capi.ptr(tgt), capi.ptr(bw),
+                  n, NC, int(num_fg), int(reg_classes), int(box_loss), float(beta), capi.ptr(partial), capi.ptr(gcls), capi.ptr(gbox),
+                  capi.current_stream_ptr())
+        return _finish_roi_head_loss(ctx, partial, gcls, gbox, num_samples, lw_cls, lw_box)
+
+    @staticmethod
+    def backward(ctx, g_cls, g_acc, g_box):
+        gcls, gbox, scale = ctx.saved_tensors
+        gc = gcls * (g_cls * scale[0]) if g_cls is not None else None
+        gb = gbox * (g_box * scale[1]) if g_box is not None else None
+        return (gc, gb) + (None, ) * 11
 
 
 class _RoIHeadLossDecoded(torch.autograd.Function):

@@ -1,6 +1,6 @@
-"""Losses of the HTD path: CrossEntropyLoss (softmax / sigmoid), SmoothL1Loss, the IoU family on decoded boxes
+"""Losses of the HTD path: CrossEntropyLoss (softmax / sigmoid), SmoothL1Loss, L1Loss, the IoU family on decoded boxes
 (IoULoss, BoundedIoULoss, GIoULoss, DIoULoss, CIoULoss), accuracy.
-Reference: mmdet/models/losses/{cross_entropy_loss.py:9-202, smooth_l1_loss.py:8-94, iou_loss.py:11-418,
+Reference: mmdet/models/losses/{cross_entropy_loss.py:9-202, smooth_l1_loss.py:8-136, iou_loss.py:11-418,
 utils.py:26-52, accuracy.py:4-48}.  Same constructor kwargs and forward signature (weight, avg_factor,
 reduction_override)."""
 import math
@@ -79,6 +79,25 @@ class SmoothL1Loss(nn.Module):
         reduction = reduction_override if reduction_override else self.reduction
         return self.loss_weight * smooth_l1_loss(pred, target, weight, beta=self.beta, reduction=reduction,
                                                  avg_factor=avg_factor, **kwargs)
+
+
+def l1_loss(pred, target, weight=None, reduction='mean', avg_factor=None):
+    assert pred.size() == target.size() and target.numel() > 0
+    return weight_reduce_loss(torch.abs(pred - target), weight, reduction, avg_factor)
+
+
+@LOSSES.register_module()
+class L1Loss(nn.Module):
+    """smooth_l1_loss.py:97-136: |pred - target|; zero with a zero gradient where pred == target (autograd's slope of |x| at 0)."""
+
+    def __init__(self, reduction='mean', loss_weight=1.0):
+        super().__init__()
+        self.reduction, self.loss_weight = reduction, loss_weight
+
+    def forward(self, pred, target, weight=None, avg_factor=None, reduction_override=None):
+        assert reduction_override in (None, 'none', 'mean', 'sum')
+        reduction = reduction_override if reduction_override else self.reduction
+        return self.loss_weight * l1_loss(pred, target, weight, reduction=reduction, avg_factor=avg_factor)
 
 
 # ---------------------------------------------------------------- IoU family (iou_loss.py), per-row losses on (n, 4) boxes

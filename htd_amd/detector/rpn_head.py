@@ -22,7 +22,7 @@ from .bricks import Conv2d, normal_init
 
 class _RPNLossFunction(torch.autograd.Function):
     """(sum of weighted BCE, sum of SmoothL1 on positives) over every anchor of the batch: one launch forward
-    (htd_rpn_loss, which also leaves the derivatives), two scalings backward."""
+    (htd_rpn_loss, which also leaves the derivatives), two scalings backward.  beta None: L1Loss (htd_rpn_loss_l1)."""
 
     @staticmethod
     def forward(ctx, cls, reg, anchors, gts, assigned, pos, neg, means, stds, beta, pos_weight):
@@ -36,9 +36,14 @@ class _RPNLossFunction(torch.autograd.Function):
         pos8, neg8 = pos.to(torch.uint8).contiguous(), neg.to(torch.uint8).contiguous()
         partial = torch.empty(capi.lib().htd_rpn_loss_partial_rows(), 2, device=cls.device, dtype=torch.float32)
         gcls, greg = torch.empty_like(cls), torch.empty_like(reg)
-        capi.call('htd_rpn_loss', capi.ptr(cls), capi.ptr(reg), capi.ptr(anchors), capi.ptr(gts), capi.ptr(assigned),
-                  capi.ptr(pos8), capi.ptr(neg8), B, A, K, _f4(means), _f4(stds), beta, pos_weight, capi.ptr(partial),
-                  capi.ptr(gcls), capi.ptr(greg), capi.current_stream_ptr())
+        if beta is None:                     # L1Loss
+            capi.call('htd_rpn_loss_l1', capi.ptr(cls), capi.ptr(reg), capi.ptr(anchors), capi.ptr(gts), capi.ptr(assigned),
+                      capi.ptr(pos8), capi.ptr(neg8), B, A, K, _f4(means), _f4(stds), pos_weight, capi.ptr(partial),
+                      capi.ptr(gcls), capi.ptr(greg), capi.current_stream_ptr())
+        else:
+            capi.call('htd_rpn_loss', capi.ptr(cls), capi.ptr(reg), capi.ptr(anchors), capi.ptr(gts), capi.ptr(assigned),
+                      capi.ptr(pos8), capi.ptr(neg8), B, A, K, _f4(means), _f4(stds), beta, pos_weight, capi.ptr(partial),
+                      capi.ptr(gcls), capi.ptr(greg), capi.current_stream_ptr())
         ctx.save_for_backward(gcls, greg)
         sums = partial.sum(0)
         return sums[0], sums[1]
@@ -357,7 +362,8 @@ class RPNHead(nn.Module):
         if self._fused_loss_ok():
             s_cls, s_box = _RPNLossFunction.apply(cls.reshape(-1), reg.reshape(-1, 4), flat_anchors, gts, assigned,
                                                   pos, neg, tuple(self.bbox_coder.means), tuple(self.bbox_coder.stds),
-                                                  float(self.loss_bbox.beta), float(self.train_cfg.pos_weight))
+                                                  float(self.loss_bbox.beta) if hasattr(self.loss_bbox, 'beta') else None,
+                                                  float(self.train_cfg.pos_weight))
             return dict(loss_rpn_cls=[self.loss_cls.loss_weight * s_cls / num_total],
                         loss_rpn_bbox=[self.loss_bbox.loss_weight * s_box / num_total])
         # targets (anchor_head.py:172-269): labels 0 = foreground, num_classes = background; weights 1 on samples
@@ -378,12 +384,12 @@ class RPNHead(nn.Module):
         return dict(loss_rpn_cls=[loss_cls], loss_rpn_bbox=[loss_bbox])
 
     def _fused_loss_ok(self):
-        """htd_rpn_loss covers the RPN of every HTD config: one sigmoid channel, BCE without class weights,
-        SmoothL1 on encoded deltas."""
+        """htd_rpn_loss / htd_rpn_loss_l1 cover the RPN of every HTD, Faster R-CNN and Cascade R-CNN config: one sigmoid channel,
+        BCE without class weights, SmoothL1 or L1 on encoded deltas."""
         lc, lb = self.loss_cls, self.loss_bbox
         return getattr(self, 'fused_loss', True) and self.cls_out_channels == 1 and \
             type(lc).__name__ == 'CrossEntropyLoss' and lc.use_sigmoid and lc.class_weight is None and \
-            lc.reduction == 'mean' and type(lb).__name__ == 'SmoothL1Loss' and lb.reduction == 'mean' and \
+            lc.reduction == 'mean' and type(lb).__name__ in ('SmoothL1Loss', 'L1Loss') and lb.reduction == 'mean' and \
             not getattr(self, 'reg_decoded_bbox', False)
 
     # -------------------------------------------------------------- reference-order path

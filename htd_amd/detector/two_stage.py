@@ -2,7 +2,7 @@
 
 Reference: detectors/base.py:15-372 (forward :168-182, _parse_losses :184-223, train_step :225-258),
 two_stage.py:10-222 (extract_feat :80-87, forward_train :107-170, simple_test :190-211),
-faster_rcnn.py:5-24.  `_parse_losses` packs all log scalars into ONE all-reduce and ONE device->host
+faster_rcnn.py:5-24, cascade_rcnn.py:5-46.  `_parse_losses` packs all log scalars into ONE all-reduce and ONE device->host
 copy (the reference does ~9 of each per step, base.py:216-221).
 """
 from collections import OrderedDict
@@ -253,5 +253,14 @@ class TwoStageDetector(BaseDetector):
 @DETECTORS.register_module()
 class FasterRCNN(TwoStageDetector):
     def __init__(self, backbone, rpn_head, roi_head, train_cfg, test_cfg, neck=None, pretrained=None):
+        super().__init__(backbone=backbone, neck=neck, rpn_head=rpn_head, roi_head=roi_head, train_cfg=train_cfg,
+                         test_cfg=test_cfg, pretrained=pretrained)
+
+
+@DETECTORS.register_module()
+class CascadeRCNN(TwoStageDetector):
+    """detectors/cascade_rcnn.py:5-24 (its show_result unwraps the 'ensemble' dict of a mask cascade: no mask branch here)."""
+
+    def __init__(self, backbone, neck=None, rpn_head=None, roi_head=None, train_cfg=None, test_cfg=None, pretrained=None):
         super().__init__(backbone=backbone, neck=neck, rpn_head=rpn_head, roi_head=roi_head, train_cfg=train_cfg,
                          test_cfg=test_cfg, pretrained=pretrained)

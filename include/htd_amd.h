@@ -32,7 +32,7 @@ extern "C" {
 const char *htd_last_error(void);
 /* ABI version, bumped on any signature change (added entry points do not bump it).  A binding compares
  * htd_abi_version() of the loaded library with the HTD_ABI_VERSION of the header it was written against. */
-#define HTD_ABI_VERSION 6
+#define HTD_ABI_VERSION 7
 int htd_abi_version(void);
 
 /* ------------------------------------------------------------------------------------
@@ -574,10 +574,24 @@ int htd_roi_head_loss_decoded(const float *cls_score, const int64_t *labels, con
                               const float *bbox_pred, const float *bbox_targets, const float *bbox_weights, int64_t n, int NC,
                               int num_fg, const double *means4, const double *stds4, double wh_ratio_clip, int kind, double eps,
                               double beta, float *partial, float *box_lo, float *grad_cls, float *grad_box, void *stream);
+/* htd_roi_head_loss for a class-specific regressor and for L1Loss (bbox_heads/bbox_head.py:165-183 with
+ * reg_class_agnostic=False; losses/smooth_l1_loss.py:29-44).  reg_classes = 1 (class-agnostic) or num_fg: bbox_pred and grad_box
+ * are [n][4 * reg_classes], and a foreground row with label c is compared with bbox_targets [n][4] through its columns
+ * 4c .. 4c+3.  box_loss 0 = SmoothL1 (beta > 0), 1 = L1 (|d|, slope 0 at d == 0; beta ignored).  grad_box is written in full by
+ * the kernel, zeros included (no memset before, no atomics); partial has the layout of htd_roi_head_loss, and the classification
+ * half is the same device code (loss_cls, acc, grad_cls bitwise those).  With reg_classes = 1 and box_loss = 0 every output is
+ * bitwise that of htd_roi_head_loss. */
+int htd_roi_head_loss_classes(const float *cls_score, const int64_t *labels, const float *label_weights, const float *bbox_pred,
+                              const float *bbox_targets, const float *bbox_weights, int64_t n, int NC, int num_fg, int reg_classes,
+                              int box_loss, float beta, float *partial, float *grad_cls, float *grad_box, void *stream);
 int htd_rpn_loss_partial_rows(void);
 int htd_rpn_loss(const float *cls, const float *reg, const float *anchors, const float *gts, const int64_t *assigned,
                  const uint8_t *pos, const uint8_t *neg, int B, int A, int K, const float *means4, const float *stds4,
                  float beta, float pos_weight, float *partial, float *grad_cls, float *grad_reg, void *stream);
+/* htd_rpn_loss with L1Loss in place of SmoothL1Loss on the encoded deltas (the same kernel code; partial column 1 = sum |d|). */
+int htd_rpn_loss_l1(const float *cls, const float *reg, const float *anchors, const float *gts, const int64_t *assigned,
+                    const uint8_t *pos, const uint8_t *neg, int B, int A, int K, const float *means4, const float *stds4,
+                    float pos_weight, float *partial, float *grad_cls, float *grad_reg, void *stream);
 
 /* nn.MaxPool2d(kernel, stride, padding) of the ResNet stem (backbones/resnet.py:509,629) on NHWC maps
  * x [B][H][W][C] -> y [B][Ho][Wo][C], C % 4 == 0, padding = -inf, floor mode.  idx (may be NULL for inference; int32
