@@ -24,6 +24,8 @@ def _model_device(model):
 
 
 def _num_classes(model):
+    if getattr(model, 'roi_head', None) is None:        # single-stage detectors
+        return model.bbox_head.num_classes
     heads = model.roi_head.bbox_head
     return (heads[-1] if isinstance(heads, (list, tuple, torch.nn.ModuleList)) else heads).num_classes
 

@@ -5,7 +5,8 @@ load unchanged through `htd_amd.Config.fromfile` (same `type=` names and kwargs)
 
 The two baselines HTD is measured against come the same way: faster_rcnn_config (configs/faster_rcnn/
 faster_rcnn_r50_fpn_1x_coco.py) and cascade_rcnn_config (configs/cascade_rcnn/cascade_rcnn_r50_fpn_1x_coco.py), with
-their `_base_` chains merged.
+their `_base_` chains merged, and so does the single-stage baseline retinanet_config (configs/retinanet/
+retinanet_r50_fpn_1x_coco.py).
 """
 import copy
 
@@ -134,6 +135,35 @@ def cascade_rcnn_config(depth=50):
     return _baseline_config(cascade_rcnn_model(depth), train_cfg, depth)
 
 
+def retinanet_model(depth=50):
+    """configs/_base_/models/retinanet_r50_fpn.py: P3-P7 (P6, P7 by stride-2 convolutions from C5), nine anchors per position,
+    focal loss on 80 sigmoid classes and L1 on the deltas."""
+    model = htd_model(depth)
+    return dict(
+        type='RetinaNet', pretrained=f'torchvision://resnet{depth}', backbone=model['backbone'],
+        neck=dict(type='FPN', in_channels=[256, 512, 1024, 2048], out_channels=256, start_level=1, add_extra_convs='on_input',
+                  num_outs=5),
+        bbox_head=dict(type='RetinaHead', num_classes=80, in_channels=256, stacked_convs=4, feat_channels=256,
+                       anchor_generator=dict(type='AnchorGenerator', octave_base_scale=4, scales_per_octave=3,
+                                             ratios=[0.5, 1.0, 2.0], strides=[8, 16, 32, 64, 128]),
+                       bbox_coder=dict(type='DeltaXYWHBBoxCoder', target_means=[.0, .0, .0, .0],
+                                       target_stds=[1.0, 1.0, 1.0, 1.0]),
+                       loss_cls=dict(type='FocalLoss', use_sigmoid=True, gamma=2.0, alpha=0.25, loss_weight=1.0),
+                       loss_bbox=dict(type='L1Loss', loss_weight=1.0)))
+
+
+def retinanet_config(depth=50):
+    """retinanet_r{depth}_fpn_1x_coco: every anchor is a sample (no sampler), lr 0.01."""
+    cfg = _baseline_config(
+        retinanet_model(depth),
+        dict(assigner=dict(type='MaxIoUAssigner', pos_iou_thr=0.5, neg_iou_thr=0.4, min_pos_iou=0, ignore_iof_thr=-1),
+             allowed_border=-1, pos_weight=-1, debug=False), depth)
+    cfg.test_cfg = ConfigDict(nms_pre=1000, min_bbox_size=0, score_thr=0.05, nms=dict(type='nms', iou_threshold=0.5),
+                              max_per_img=100)
+    cfg.optimizer.lr = 0.01
+    return cfg
+
+
 IMG_NORM_CFG = dict(mean=[123.675, 116.28, 103.53], std=[58.395, 57.12, 57.375], to_rgb=True)
 
 
@@ -236,8 +266,8 @@ def build_htd_detector(depth=50, dcn=False, cfg=None, bf16=False, resnext=False)
             # property of THIS model (runner.Trainer applies it around its steps), not of the process.
             model.overlap_wgrad = False
         model.backbone.compute_dtype = torch.bfloat16
-        heads = model.roi_head.bbox_head
-        for head in (heads if isinstance(heads, torch.nn.ModuleList) else [heads]):      # the 12544->1024->1024 FC stacks of every stage
+        heads = model.roi_head.bbox_head if getattr(model, 'roi_head', None) is not None else []
+        for head in (heads if isinstance(heads, (list, torch.nn.ModuleList)) else [heads]):      # the 12544->1024->1024 FC stacks of every stage
             head.compute_dtype = torch.bfloat16
             for m in getattr(head, 'convs', []):       # and the 3x3 stack of the regression branch (GroupNorm stays fp32)
                 m.compute_dtype = torch.bfloat16
@@ -257,3 +287,10 @@ def build_baseline_detector(kind='faster_rcnn', depth=50, cfg=None, bf16=False):
     if str(cfg.model.get('pretrained') or '').startswith('torchvision://'):
         cfg.model.pretrained = None
     return build_htd_detector(cfg=cfg, bf16=bf16)
+
+
+def build_retinanet_detector(depth=50, cfg=None, bf16=False):
+    """The detector of retinanet_config(depth) (or of `cfg`), built like the two-stage baselines: the `pretrained` URL of the
+    reference's config dropped.  The single-stage baseline has a builder of its own: the kinds of build_baseline_detector are
+    the two-stage ones."""
+    return build_baseline_detector(cfg=retinanet_config(depth) if cfg is None else cfg, bf16=bf16)

@@ -19,6 +19,10 @@ EXTRA = {'nms.hip': ['-ffp-contract=off'], 'box_ops.hip': ['-ffp-contract=off'],
          'voc_eval.hip': ['-ffp-contract=off']}
 
 
+# Every *.hip / *.cpp of this directory is a translation unit of the library; what each one replaces (include/htd_amd.h cites
+# the reference interface per entry point):
+#   focal_loss.hip   mmcv.ops.sigmoid_focal_loss (mmdet/models/losses/focal_loss.py:10-87) and AnchorHead.loss of a head without
+#                    sampling over all pyramid levels (dense_heads/anchor_head.py:172-269,288-291,373-488, retina_head.py)
 def sources():
     return sorted(f for f in os.listdir(HERE) if f.endswith('.hip') or f.endswith('.cpp'))
 

@@ -1,0 +1,412 @@
+"""Anchor-based dense heads of single-stage detectors: AnchorHead and RetinaHead.
+
+Reference: dense_heads/anchor_head.py:14-682 (AnchorHead: forward, get_anchors, get_targets, loss, get_bboxes),
+base_dense_head.py:22-59 (forward_train), retina_head.py:8-114 (RetinaHead).  Same registry names, constructor kwargs,
+state_dict keys (cls_convs / reg_convs / retina_cls / retina_reg) and return structures.
+
+`loss` has two forms, like RPNHead.loss.  The tensor form follows the reference's order of operations (per image targets, per
+level losses) and works with any loss modules, `reg_decoded_bbox`, ignore boxes and on the CPU.  The fused form -- FocalLoss with
+L1Loss / SmoothL1Loss on delta targets, no ignore boxes, fp32 GPU tensors -- assigns the whole batch against the shared anchors
+(htd_max_iou_assign), counts the positives on the device (htd_retina_avg_factor) and takes both losses and both gradients of all
+levels in one launch (htd_retina_loss) that reads the convolution outputs where they are: no labels / label_weights /
+bbox_targets / bbox_weights tensors, no permute or concatenation of the logits, no host read.
+
+`get_bboxes` handles the whole batch: one key launch (htd_retina_keys) and one segmented top-k give every (image, level) cut
+to nms_pre, one gather of the kept logits and deltas, one multiclass NMS over all images.  The decode and the rescale stay the
+coder's own tensor operations applied image by image (a handful of element-wise launches on nms_pre x levels rows each), so the
+result is bit-identical to the per-image loop, which is the rule the two-stage post-processing follows.
+"""
+import os
+
+import torch
+import torch.nn as nn
+
+from ..core import anchor_inside_flags, images_to_levels, multi_apply, unmap
+from ..core.misc import const_tensor
+from .. import mmcv_ops as M
+from ..registry import HEADS, build_anchor_generator, build_assigner, build_bbox_coder, build_loss, build_sampler
+from .bricks import Conv2d, ConvModule, normal_init
+
+RETINA_FUSED = os.environ.get('HTD_RETINA_FUSED', '1') != '0'       # 0: the tensor-path loss (A/B runs)
+
+
+def bias_init_with_prob(prior_prob):
+    """mmcv.cnn.bias_init_with_prob: the bias that makes sigmoid(bias) = prior_prob."""
+    import math
+    return float(-math.log((1 - prior_prob) / prior_prob))
+
+
+@HEADS.register_module()
+class AnchorHead(nn.Module):
+    def __init__(self, num_classes, in_channels, feat_channels=256,
+                 anchor_generator=dict(type='AnchorGenerator', scales=[8, 16, 32], ratios=[0.5, 1.0, 2.0],
+                                       strides=[4, 8, 16, 32, 64]),
+                 bbox_coder=dict(type='DeltaXYWHBBoxCoder', clip_border=True, target_means=(.0, .0, .0, .0),
+                                 target_stds=(1.0, 1.0, 1.0, 1.0)),
+                 reg_decoded_bbox=False,
+                 loss_cls=dict(type='CrossEntropyLoss', use_sigmoid=True, loss_weight=1.0),
+                 loss_bbox=dict(type='SmoothL1Loss', beta=1.0 / 9.0, loss_weight=1.0), train_cfg=None, test_cfg=None):
+        super().__init__()
+        self.in_channels, self.num_classes, self.feat_channels = in_channels, num_classes, feat_channels
+        self.use_sigmoid_cls = loss_cls.get('use_sigmoid', False)
+        self.sampling = loss_cls['type'] not in ['FocalLoss', 'GHMC', 'QualityFocalLoss']       # anchor_head.py:60-66
+        self.cls_out_channels = num_classes if self.use_sigmoid_cls else num_classes + 1
+        if self.cls_out_channels <= 0:
+            raise ValueError(f'num_classes={num_classes} is too small')
+        self.reg_decoded_bbox = reg_decoded_bbox
+        self.bbox_coder = build_bbox_coder(bbox_coder)
+        self.loss_cls = build_loss(loss_cls)
+        self.loss_bbox = build_loss(loss_bbox)
+        self.train_cfg, self.test_cfg = train_cfg, test_cfg
+        if self.train_cfg:
+            self.assigner = build_assigner(self.train_cfg.assigner)
+            if self.sampling and hasattr(self.train_cfg, 'sampler'):
+                sampler_cfg = self.train_cfg.sampler
+            else:
+                sampler_cfg = dict(type='PseudoSampler')
+            self.sampler = build_sampler(sampler_cfg, context=self)
+        self.fp16_enabled = False
+        self.anchor_generator = build_anchor_generator(anchor_generator)
+        self.num_anchors = self.anchor_generator.num_base_anchors[0]
+        self._init_layers()
+
+    def _init_layers(self):
+        self.conv_cls = Conv2d(self.in_channels, self.num_anchors * self.cls_out_channels, 1)
+        self.conv_reg = Conv2d(self.in_channels, self.num_anchors * 4, 1)
+
+    def init_weights(self):
+        normal_init(self.conv_cls, std=0.01)
+        normal_init(self.conv_reg, std=0.01)
+
+    # ------------------------------------------------------------------ forward
+    def forward_single(self, x):
+        return self.conv_cls(x), self.conv_reg(x)
+
+    def forward(self, feats):
+        return multi_apply(self.forward_single, feats)
+
+    def forward_train(self, x, img_metas, gt_bboxes, gt_labels=None, gt_bboxes_ignore=None, proposal_cfg=None, **kwargs):
+        """base_dense_head.py:22-59."""
+        outs = self(x)
+        if gt_labels is None:
+            losses = self.loss(*outs, gt_bboxes, img_metas, gt_bboxes_ignore=gt_bboxes_ignore)
+        else:
+            losses = self.loss(*outs, gt_bboxes, gt_labels, img_metas, gt_bboxes_ignore=gt_bboxes_ignore)
+        if proposal_cfg is None:
+            return losses
+        return losses, self.get_bboxes(*outs, img_metas, cfg=proposal_cfg)
+
+    def simple_test(self, feats, img_metas, rescale=False):
+        return self.get_bboxes(*self(feats), img_metas, rescale=rescale)
+
+    # ------------------------------------------------------------------ targets
+    def get_anchors(self, featmap_sizes, img_metas, device='cuda'):
+        mlvl = self.anchor_generator.grid_anchors(featmap_sizes, device)
+        anchor_list = [mlvl for _ in img_metas]
+        valid_flag_list = [self.anchor_generator.valid_flags(featmap_sizes, m['pad_shape'], device) for m in img_metas]
+        return anchor_list, valid_flag_list
+
+    def _get_targets_single(self, flat_anchors, valid_flags, gt_bboxes, gt_bboxes_ignore, gt_labels, img_meta,
+                            label_channels=1, unmap_outputs=True):
+        """anchor_head.py:172-269."""
+        inside = anchor_inside_flags(flat_anchors, valid_flags, img_meta['img_shape'][:2], self.train_cfg.allowed_border)
+        if not inside.any():
+            return (None, ) * 7
+        anchors = flat_anchors[inside, :]
+        assign_result = self.assigner.assign(anchors, gt_bboxes, gt_bboxes_ignore, None if self.sampling else gt_labels)
+        sr = self.sampler.sample(assign_result, anchors, gt_bboxes)
+        n = anchors.shape[0]
+        bbox_targets = torch.zeros_like(anchors)
+        bbox_weights = torch.zeros_like(anchors)
+        labels = anchors.new_full((n, ), self.num_classes, dtype=torch.long)
+        label_weights = anchors.new_zeros(n, dtype=torch.float)
+        pos_inds, neg_inds = sr.pos_inds, sr.neg_inds
+        if len(pos_inds) > 0:
+            if not self.reg_decoded_bbox:
+                pos_bbox_targets = self.bbox_coder.encode(sr.pos_bboxes, sr.pos_gt_bboxes)
+            else:
+                pos_bbox_targets = sr.pos_gt_bboxes
+            bbox_targets[pos_inds, :] = pos_bbox_targets
+            bbox_weights[pos_inds, :] = 1.0
+            if gt_labels is None:
+                labels[pos_inds] = 0        # only the RPN gives gt_labels as None: foreground is class 0
+            else:
+                labels[pos_inds] = gt_labels[sr.pos_assigned_gt_inds]
+            label_weights[pos_inds] = 1.0 if self.train_cfg.pos_weight <= 0 else self.train_cfg.pos_weight
+        if len(neg_inds) > 0:
+            label_weights[neg_inds] = 1.0
+        if unmap_outputs:
+            total = flat_anchors.size(0)
+            labels = unmap(labels, total, inside, fill=self.num_classes)
+            label_weights = unmap(label_weights, total, inside)
+            bbox_targets = unmap(bbox_targets, total, inside)
+            bbox_weights = unmap(bbox_weights, total, inside)
+        return labels, label_weights, bbox_targets, bbox_weights, pos_inds, neg_inds, sr
+
+    def get_targets(self, anchor_list, valid_flag_list, gt_bboxes_list, img_metas, gt_bboxes_ignore_list=None,
+                    gt_labels_list=None, label_channels=1, unmap_outputs=True):
+        """anchor_head.py:271-371 -> (labels, label_weights, bbox_targets, bbox_weights per level, num_total_pos,
+        num_total_neg)."""
+        num_imgs = len(img_metas)
+        assert len(anchor_list) == len(valid_flag_list) == num_imgs
+        num_level_anchors = [a.size(0) for a in anchor_list[0]]
+        concat_anchors = [torch.cat(a) for a in anchor_list]
+        concat_valid = [torch.cat(v) for v in valid_flag_list]
+        if gt_bboxes_ignore_list is None:
+            gt_bboxes_ignore_list = [None] * num_imgs
+        if gt_labels_list is None:
+            gt_labels_list = [None] * num_imgs
+        res = [self._get_targets_single(concat_anchors[i], concat_valid[i], gt_bboxes_list[i], gt_bboxes_ignore_list[i],
+                                        gt_labels_list[i], img_metas[i], label_channels, unmap_outputs) for i in range(num_imgs)]
+        if any(r[0] is None for r in res):
+            return None
+        num_total_pos = sum(max(r[4].numel(), 1) for r in res)
+        num_total_neg = sum(max(r[5].numel(), 1) for r in res)
+        lv = [images_to_levels([r[k] for r in res], num_level_anchors) for k in range(4)]
+        return lv[0], lv[1], lv[2], lv[3], num_total_pos, num_total_neg
+
+    # ------------------------------------------------------------------ loss
+    def loss_single(self, cls_score, bbox_pred, anchors, labels, label_weights, bbox_targets, bbox_weights, num_total_samples):
+        """anchor_head.py:373-418."""
+        labels = labels.reshape(-1)
+        label_weights = label_weights.reshape(-1)
+        cls_score = cls_score.permute(0, 2, 3, 1).reshape(-1, self.cls_out_channels)
+        loss_cls = self.loss_cls(cls_score, labels, label_weights, avg_factor=num_total_samples)
+        bbox_targets = bbox_targets.reshape(-1, 4)
+        bbox_weights = bbox_weights.reshape(-1, 4)
+        bbox_pred = bbox_pred.permute(0, 2, 3, 1).reshape(-1, 4)
+        if self.reg_decoded_bbox:
+            bbox_pred = self.bbox_coder.decode(anchors.reshape(-1, 4), bbox_pred)
+        loss_bbox = self.loss_bbox(bbox_pred, bbox_targets, bbox_weights, avg_factor=num_total_samples)
+        return loss_cls, loss_bbox
+
+    def loss(self, cls_scores, bbox_preds, gt_bboxes, gt_labels, img_metas, gt_bboxes_ignore=None):
+        if self._fused_loss_ok(cls_scores, bbox_preds, gt_bboxes, gt_labels, gt_bboxes_ignore):
+            return self.loss_fused(cls_scores, bbox_preds, gt_bboxes, gt_labels, img_metas)
+        return self.loss_tensor(cls_scores, bbox_preds, gt_bboxes, gt_labels, img_metas, gt_bboxes_ignore)
+
+    def loss_tensor(self, cls_scores, bbox_preds, gt_bboxes, gt_labels, img_metas, gt_bboxes_ignore=None):
+        """anchor_head.py:420-488, in the reference's order of operations."""
+        featmap_sizes = [f.size()[-2:] for f in cls_scores]
+        assert len(featmap_sizes) == self.anchor_generator.num_levels
+        device = cls_scores[0].device
+        anchor_list, valid_flag_list = self.get_anchors(featmap_sizes, img_metas, device=device)
+        label_channels = self.cls_out_channels if self.use_sigmoid_cls else 1
+        targets = self.get_targets(anchor_list, valid_flag_list, gt_bboxes, img_metas, gt_bboxes_ignore_list=gt_bboxes_ignore,
+                                   gt_labels_list=gt_labels, label_channels=label_channels)
+        if targets is None:
+            return None
+        labels, label_weights, bbox_targets, bbox_weights, num_total_pos, num_total_neg = targets
+        num_total_samples = num_total_pos + num_total_neg if self.sampling else num_total_pos
+        num_level_anchors = [a.size(0) for a in anchor_list[0]]
+        all_anchors = images_to_levels([torch.cat(a) for a in anchor_list], num_level_anchors)
+        losses_cls, losses_bbox = multi_apply(self.loss_single, cls_scores, bbox_preds, all_anchors, labels, label_weights,
+                                              bbox_targets, bbox_weights, num_total_samples=num_total_samples)
+        return dict(loss_cls=losses_cls, loss_bbox=losses_bbox)
+
+    def _fused_loss_ok(self, cls_scores, bbox_preds, gt_bboxes, gt_labels, gt_bboxes_ignore):
+        """htd_retina_loss covers FocalLoss + L1Loss / SmoothL1Loss on delta targets without ignore boxes, fp32 on the GPU."""
+        lc, lb = self.loss_cls, self.loss_bbox
+        a = getattr(self, 'assigner', None)
+        return getattr(self, 'fused_loss', RETINA_FUSED) and gt_labels is not None and gt_bboxes_ignore is None and \
+            type(lc).__name__ == 'FocalLoss' and lc.reduction == 'mean' and \
+            type(lb).__name__ in ('SmoothL1Loss', 'L1Loss') and lb.reduction == 'mean' and not self.reg_decoded_bbox and \
+            type(a).__name__ == 'MaxIoUAssigner' and a.ignore_iof_thr <= 0 and isinstance(a.neg_iou_thr, float) and \
+            (a.gt_max_assign_all or not a.match_low_quality) and len(cls_scores) <= 8 and \
+            all(t.is_cuda and t.dtype == torch.float32 and M.nhwc_channel_stride(t) is not None
+                for t in list(cls_scores) + list(bbox_preds))       # (other layouts, e.g. NCHW-contiguous maps: the tensor path)
+
+    def _anchors_inside(self, featmap_sizes, img_metas, dev):
+        """(A, 4) level-concatenated anchors and the (B, A) mask of anchors that are valid and inside their image
+        (anchor_head.py:200-207): constants of (feature-map sizes, image shapes), cached under exactly those."""
+        border = self.train_cfg.allowed_border
+        key = (tuple(tuple(int(v) for v in f) for f in featmap_sizes),
+               tuple((tuple(m['img_shape'][:2]), tuple(m['pad_shape'][:2])) for m in img_metas), str(dev), border)
+        cache = self.__dict__.setdefault('_inside_cache', {})
+        if key not in cache:
+            if len(cache) > 64:
+                cache.clear()
+            anchor_list, valid_flag_list = self.get_anchors(featmap_sizes, img_metas, device=dev)
+            flat_anchors = torch.cat(anchor_list[0])
+            valid = torch.stack([torch.cat(v) for v in valid_flag_list])
+            if border >= 0:
+                lim = const_tensor([[m['img_shape'][1], m['img_shape'][0]] for m in img_metas], dev, flat_anchors.dtype)
+                valid = valid & (flat_anchors[None, :, 0] >= -border) & (flat_anchors[None, :, 1] >= -border) & \
+                    (flat_anchors[None, :, 2] < lim[:, 0:1] + border) & (flat_anchors[None, :, 3] < lim[:, 1:2] + border)
+            cache[key] = (flat_anchors.contiguous(), valid.contiguous())
+        return cache[key]
+
+    def loss_fused(self, cls_scores, bbox_preds, gt_bboxes, gt_labels, img_metas):
+        from ..core.bbox import batched_max_iou_assign, pad_gt_batch
+        dev = cls_scores[0].device
+        featmap_sizes = [f.size()[-2:] for f in cls_scores]
+        assert len(featmap_sizes) == self.anchor_generator.num_levels
+        flat_anchors, inside = self._anchors_inside(featmap_sizes, img_metas, dev)
+        gts, gt_valid, labels = pad_gt_batch(gt_bboxes, gt_labels)
+        assigned, _ = batched_max_iou_assign(self.assigner, flat_anchors, inside, gts, gt_valid)
+        num_pos, avg = M.retina_avg_factor(assigned)
+        self._last_assigned = (assigned, num_pos, avg)          # exposed for tests
+        lb = self.loss_bbox
+        l1 = type(lb).__name__ == 'L1Loss'
+        loss_cls, loss_bbox = M.retina_loss(
+            cls_scores, bbox_preds, self.num_anchors, self.cls_out_channels, flat_anchors, gts, labels, assigned, avg,
+            tuple(self.bbox_coder.means), tuple(self.bbox_coder.stds), self.loss_cls.gamma, self.loss_cls.alpha,
+            self.train_cfg.pos_weight, 1 if l1 else 0, 0.0 if l1 else lb.beta, self.loss_cls.loss_weight, lb.loss_weight)
+        return dict(loss_cls=[loss_cls], loss_bbox=[loss_bbox])
+
+    # ------------------------------------------------------------------ boxes
+    @torch.no_grad()
+    def get_bboxes(self, cls_scores, bbox_preds, img_metas, cfg=None, rescale=False, with_nms=True):
+        """anchor_head.py:490-664 -> list (per image) of (dets (k, 5), labels (k,)).  GPU fp32 sigmoid heads with hard NMS take
+        the batched form; everything else the per-image loop."""
+        cfg = self.test_cfg if cfg is None else cfg
+        assert len(cls_scores) == len(bbox_preds)
+        nms_pre = cfg.get('nms_pre', -1)
+        Ns = [int(c.shape[2] * c.shape[3]) * self.num_anchors for c in cls_scores]
+        batched = with_nms and self.use_sigmoid_cls and cls_scores[0].is_cuda and len(cls_scores) <= 8 and \
+            all(t.dtype == torch.float32 for t in list(cls_scores) + list(bbox_preds)) and \
+            cfg.nms.get('type', 'nms') == 'nms' and (nms_pre <= 0 or nms_pre <= M.TOPK_KMAX) and \
+            getattr(self, 'batched_get_bboxes', True) and (nms_pre > 0 or max(Ns) <= M.TOPK_KMAX)
+        if batched:
+            return self._get_bboxes_batched(cls_scores, bbox_preds, img_metas, cfg, rescale)
+        dev = cls_scores[0].device
+        featmap_sizes = [c.shape[-2:] for c in cls_scores]
+        mlvl_anchors = self.anchor_generator.grid_anchors(featmap_sizes, device=dev)
+        out = []
+        for b, meta in enumerate(img_metas):
+            out.append(self._get_bboxes_single([c[b].detach() for c in cls_scores], [r[b].detach() for r in bbox_preds],
+                                               mlvl_anchors, meta['img_shape'], meta['scale_factor'], cfg, rescale, with_nms))
+        return out
+
+    def _level_keys(self, cls_score_list):
+        """per level (n_l,) max_c sigmoid(score): htd_retina_keys on the GPU (the same launch form as the batched path, so
+        the two rank identically), tensor operations elsewhere."""
+        if cls_score_list[0].is_cuda and cls_score_list[0].dtype == torch.float32 and self.use_sigmoid_cls and \
+                len(cls_score_list) <= 8:
+            keys = M.retina_keys([c[None] for c in cls_score_list], self.num_anchors, self.cls_out_channels)[0]
+            sizes = [int(c.shape[1] * c.shape[2]) * self.num_anchors for c in cls_score_list]
+            return list(keys.split(sizes))
+        out = []
+        for c in cls_score_list:
+            s = c.permute(1, 2, 0).reshape(-1, self.cls_out_channels)
+            out.append(s.sigmoid().max(dim=1)[0] if self.use_sigmoid_cls else s.softmax(-1)[:, :-1].max(dim=1)[0])
+        return out
+
+    def _get_bboxes_single(self, cls_score_list, bbox_pred_list, mlvl_anchors, img_shape, scale_factor, cfg, rescale=False,
+                           with_nms=True):
+        """anchor_head.py:581-664 for one image."""
+        from ..core.post_processing import multiclass_nms
+        cfg = self.test_cfg if cfg is None else cfg
+        assert len(cls_score_list) == len(bbox_pred_list) == len(mlvl_anchors)
+        nms_pre = cfg.get('nms_pre', -1)
+        keys = self._level_keys(cls_score_list) if nms_pre > 0 and any(a.size(0) > nms_pre for a in mlvl_anchors) else None
+        mlvl_bboxes, mlvl_scores = [], []
+        for lvl, (cls_score, bbox_pred, anchors) in enumerate(zip(cls_score_list, bbox_pred_list, mlvl_anchors)):
+            assert cls_score.size()[-2:] == bbox_pred.size()[-2:]
+            cls_score = cls_score.permute(1, 2, 0).reshape(-1, self.cls_out_channels)
+            bbox_pred = bbox_pred.permute(1, 2, 0).reshape(-1, 4)
+            if nms_pre > 0 and cls_score.shape[0] > nms_pre:
+                # the first nms_pre of the stable descending order (equal keys: lower anchor index first)
+                topk_inds = keys[lvl].sort(descending=True, stable=True)[1][:nms_pre]
+                anchors, bbox_pred, cls_score = anchors[topk_inds, :], bbox_pred[topk_inds, :], cls_score[topk_inds, :]
+            scores = cls_score.sigmoid() if self.use_sigmoid_cls else cls_score.softmax(-1)
+            mlvl_bboxes.append(self.bbox_coder.decode(anchors, bbox_pred, max_shape=img_shape))
+            mlvl_scores.append(scores)
+        mlvl_bboxes = torch.cat(mlvl_bboxes)
+        if rescale:
+            mlvl_bboxes = mlvl_bboxes / mlvl_bboxes.new_tensor(scale_factor)
+        mlvl_scores = torch.cat(mlvl_scores)
+        if self.use_sigmoid_cls:
+            mlvl_scores = torch.cat([mlvl_scores, mlvl_scores.new_zeros(mlvl_scores.shape[0], 1)], dim=1)
+        if with_nms:
+            return multiclass_nms(mlvl_bboxes, mlvl_scores, cfg.score_thr, cfg.nms, cfg.max_per_img)
+        return mlvl_bboxes, mlvl_scores
+
+    def _get_bboxes_batched(self, cls_scores, bbox_preds, img_metas, cfg, rescale):
+        from ..core.post_processing import multiclass_nms_images
+        B, L = cls_scores[0].size(0), len(cls_scores)
+        dev = cls_scores[0].device
+        C, na = self.cls_out_channels, self.num_anchors
+        featmap_sizes = [c.shape[-2:] for c in cls_scores]
+        Ns = [int(c.shape[2] * c.shape[3]) * na for c in cls_scores]
+        nms_pre = cfg.get('nms_pre', -1)
+        ks = [n if nms_pre <= 0 or n <= nms_pre else nms_pre for n in Ns]
+        total, offs = sum(Ns), [sum(Ns[:l]) for l in range(L)]
+        cls_scores = [c.detach() for c in cls_scores]
+        # keyed on the map sizes themselves: transposed (portrait / landscape) batches have equal products
+        ck = (tuple(tuple(int(v) for v in f) for f in featmap_sizes), tuple(ks), str(dev))
+        cache = self.__dict__.setdefault('_bbox_cache', {})
+        if ck not in cache:
+            if len(cache) > 32:
+                cache.clear()
+            cache[ck] = torch.cat(self.anchor_generator.grid_anchors(featmap_sizes, device=dev))
+        anchors = cache[ck]
+        cut = [l for l in range(L) if ks[l] < Ns[l]]
+        pieces = [torch.arange(offs[l], offs[l] + Ns[l], device=dev)[None].expand(B, Ns[l]) for l in range(L)]
+        if cut:
+            # every (image, level) cut of the call in one key launch and one segmented top-k; a level that is not cut keeps its
+            # anchors in their own order, as the per-image form does
+            keys = M.retina_keys(cls_scores, na, C)                                   # (B, total)
+            top_idx, _ = M.segmented_topk(keys, [(b * total + offs[l], Ns[l], ks[l]) for b in range(B) for l in cut])
+            top_idx, at = top_idx.view(B, -1), 0
+            for l in cut:
+                pieces[l] = top_idx[:, at:at + ks[l]] + offs[l]
+                at += ks[l]
+        gidx = torch.cat(pieces, 1)
+        K = gidx.size(1)
+        logits = torch.cat([c.permute(0, 2, 3, 1).reshape(B, -1, C) for c in cls_scores], 1)
+        deltas = torch.cat([r.detach().permute(0, 2, 3, 1).reshape(B, -1, 4) for r in bbox_preds], 1)
+        scores = torch.gather(logits, 1, gidx[..., None].expand(B, K, C)).sigmoid()
+        deltas = torch.gather(deltas, 1, gidx[..., None].expand(B, K, 4))
+        boxes = torch.stack([self.bbox_coder.decode(anchors[gidx[b]], deltas[b], max_shape=img_metas[b]['img_shape'])
+                             for b in range(B)])
+        if rescale:
+            boxes = torch.stack([boxes[b] / boxes.new_tensor(img_metas[b]['scale_factor']) for b in range(B)])
+        scores = torch.cat([scores, scores.new_zeros(B, K, 1)], dim=2)
+        img_of = torch.arange(B, device=dev).repeat_interleave(K)
+        dets, labels = multiclass_nms_images(boxes.reshape(B * K, 4), scores.reshape(B * K, C + 1), img_of, B, cfg.score_thr,
+                                             cfg.nms, cfg.max_per_img)
+        return list(zip(dets, labels))
+
+    def aug_test(self, feats, img_metas, rescale=False):
+        raise NotImplementedError('test-time augmentation of dense heads is not part of this package')
+
+
+@HEADS.register_module()
+class RetinaHead(AnchorHead):
+    def __init__(self, num_classes, in_channels, stacked_convs=4, conv_cfg=None, norm_cfg=None,
+                 anchor_generator=dict(type='AnchorGenerator', octave_base_scale=4, scales_per_octave=3, ratios=[0.5, 1.0, 2.0],
+                                       strides=[8, 16, 32, 64, 128]), **kwargs):
+        self.stacked_convs, self.conv_cfg, self.norm_cfg = stacked_convs, conv_cfg, norm_cfg
+        super().__init__(num_classes, in_channels, anchor_generator=anchor_generator, **kwargs)
+
+    def _init_layers(self):
+        self.relu = nn.ReLU(inplace=True)
+        self.cls_convs = nn.ModuleList()
+        self.reg_convs = nn.ModuleList()
+        for i in range(self.stacked_convs):
+            chn = self.in_channels if i == 0 else self.feat_channels
+            self.cls_convs.append(ConvModule(chn, self.feat_channels, 3, stride=1, padding=1, conv_cfg=self.conv_cfg,
+                                             norm_cfg=self.norm_cfg))
+            self.reg_convs.append(ConvModule(chn, self.feat_channels, 3, stride=1, padding=1, conv_cfg=self.conv_cfg,
+                                             norm_cfg=self.norm_cfg))
+        self.retina_cls = Conv2d(self.feat_channels, self.num_anchors * self.cls_out_channels, 3, padding=1)
+        self.retina_reg = Conv2d(self.feat_channels, self.num_anchors * 4, 3, padding=1)
+
+    def init_weights(self):
+        for m in self.cls_convs:
+            normal_init(m.conv, std=0.01)
+        for m in self.reg_convs:
+            normal_init(m.conv, std=0.01)
+        normal_init(self.retina_cls, std=0.01, bias=bias_init_with_prob(0.01))
+        normal_init(self.retina_reg, std=0.01)
+
+    def forward_single(self, x):
+        if x.dtype != torch.float32:             # a bf16 pyramid: the towers and all box / loss arithmetic stay fp32
+            x = x.float()
+        cls_feat = reg_feat = x
+        for cls_conv in self.cls_convs:
+            cls_feat = cls_conv(cls_feat)
+        for reg_conv in self.reg_convs:
+            reg_feat = reg_conv(reg_feat)
+        return self.retina_cls(cls_feat), self.retina_reg(reg_feat)

@@ -1,5 +1,6 @@
-"""FPN neck (mmdet/models/necks/fpn.py:9-216): 1x1 laterals, nearest top-down add, 3x3 output convs,
-P6 = stride-2 subsample of P5.  The HTD configs use the plain variant (no extra convs, no norm)."""
+"""FPN neck (mmdet/models/necks/fpn.py:9-216): 1x1 laterals, nearest top-down add, 3x3 output convs; the levels past the
+backbone's are stride-2 subsamples of the last output (the HTD configs: P6 of P5) or, with add_extra_convs, stride-2 3x3
+convolutions on the last input, lateral or output (RetinaNet: P6, P7 from C5 with start_level=1)."""
 import os
 
 import torch
@@ -20,7 +21,6 @@ class FPN(nn.Module):
                  norm_cfg=None, act_cfg=None, upsample_cfg=dict(mode='nearest')):
         super().__init__()
         assert isinstance(in_channels, list)
-        assert not add_extra_convs, 'extra FPN convs are outside the HTD path (P6 is a subsample of P5)'
         self.in_channels, self.out_channels = in_channels, out_channels
         self.num_ins, self.num_outs = len(in_channels), num_outs
         self.upsample_cfg = dict(upsample_cfg)
@@ -30,7 +30,14 @@ class FPN(nn.Module):
         else:
             self.backbone_end_level = end_level
             assert end_level <= len(in_channels) and num_outs == end_level - start_level
-        self.start_level, self.end_level, self.add_extra_convs = start_level, end_level, add_extra_convs
+        self.start_level, self.end_level = start_level, end_level
+        self.relu_before_extra_convs, self.no_norm_on_lateral = relu_before_extra_convs, no_norm_on_lateral
+        assert isinstance(add_extra_convs, (str, bool))
+        if isinstance(add_extra_convs, str):
+            assert add_extra_convs in ('on_input', 'on_lateral', 'on_output')
+        elif add_extra_convs:                    # True: the older switch decides the source (fpn.py:104-110)
+            add_extra_convs = 'on_input' if extra_convs_on_inputs else 'on_output'
+        self.add_extra_convs = add_extra_convs
         self.lateral_convs = nn.ModuleList()
         self.fpn_convs = nn.ModuleList()
         for i in range(self.start_level, self.backbone_end_level):
@@ -39,6 +46,27 @@ class FPN(nn.Module):
                                                  act_cfg=act_cfg, inplace=False))
             self.fpn_convs.append(ConvModule(out_channels, out_channels, 3, padding=1, conv_cfg=conv_cfg,
                                              norm_cfg=norm_cfg, act_cfg=act_cfg, inplace=False))
+        extra_levels = num_outs - self.backbone_end_level + self.start_level
+        if self.add_extra_convs and extra_levels >= 1:
+            for i in range(extra_levels):
+                cin = in_channels[self.backbone_end_level - 1] if i == 0 and self.add_extra_convs == 'on_input' else out_channels
+                self.fpn_convs.append(ConvModule(cin, out_channels, 3, stride=2, padding=1, conv_cfg=conv_cfg, norm_cfg=norm_cfg,
+                                                 act_cfg=act_cfg, inplace=False))
+
+    def _extra_levels(self, inputs, laterals, outs):
+        """fpn.py:193-215: the levels past the backbone's, appended to outs."""
+        n = len(self.lateral_convs)
+        if self.num_outs <= n:
+            return outs
+        if not self.add_extra_convs:
+            for _ in range(self.num_outs - n):
+                outs.append(outs[-1][:, :, ::2, ::2])      # == F.max_pool2d(x, 1, stride=2), fpn.py:197-199
+            return outs
+        source = dict(on_input=inputs[self.backbone_end_level - 1], on_lateral=laterals[-1], on_output=outs[-1])
+        outs.append(self.fpn_convs[n](source[self.add_extra_convs]))
+        for i in range(n + 1, self.num_outs):
+            outs.append(self.fpn_convs[i](F.relu(outs[-1]) if self.relu_before_extra_convs else outs[-1]))
+        return outs
 
     def init_weights(self):
         for m in self.modules():
@@ -70,6 +98,7 @@ class FPN(nn.Module):
             # alias, so in backward the summed-down gradient joins in the output convolution's data-gradient epilogue.
             laterals, outs_chain = [None] * n, [None] * n
             chain = inputs[0].is_cuda and inputs[0].dtype == torch.float32 and torch.is_grad_enabled() and \
+                self.add_extra_convs != 'on_lateral' and \
                 all(not c.with_norm and not c.with_activation and getattr(c, 'compute_dtype', None) is None
                     for c in self.fpn_convs[:n])
             for i in range(n - 1, -1, -1):
@@ -80,9 +109,7 @@ class FPN(nn.Module):
                     outs_chain[i], laterals[i] = self.fpn_convs[i].conv(laterals[i], chain=True)
             if chain:
                 outs = [outs_chain[i] if i > 0 else self.fpn_convs[0](laterals[0]) for i in range(n)]
-                for _ in range(self.num_outs - n):
-                    outs.append(outs[-1][:, :, ::2, ::2])
-                return tuple(outs)
+                return tuple(self._extra_levels(inputs, laterals, outs))
         else:
             laterals = [conv(inputs[i + self.start_level]) for i, conv in enumerate(self.lateral_convs)]
             for i in range(n - 1, 0, -1):
@@ -92,6 +119,4 @@ class FPN(nn.Module):
                     up = F.interpolate(laterals[i], size=laterals[i - 1].shape[2:], **self.upsample_cfg)
                 laterals[i - 1] = laterals[i - 1] + up
         outs = [self.fpn_convs[i](laterals[i]) for i in range(n)]
-        for _ in range(self.num_outs - n):
-            outs.append(outs[-1][:, :, ::2, ::2])      # == F.max_pool2d(x, 1, stride=2), fpn.py:197-199
-        return tuple(outs)
+        return tuple(self._extra_levels(inputs, laterals, outs))

@@ -1,7 +1,7 @@
 """Losses of the HTD path: CrossEntropyLoss (softmax / sigmoid), SmoothL1Loss, L1Loss, the IoU family on decoded boxes
-(IoULoss, BoundedIoULoss, GIoULoss, DIoULoss, CIoULoss), accuracy.
+(IoULoss, BoundedIoULoss, GIoULoss, DIoULoss, CIoULoss), FocalLoss, accuracy.
 Reference: mmdet/models/losses/{cross_entropy_loss.py:9-202, smooth_l1_loss.py:8-136, iou_loss.py:11-418,
-utils.py:26-52, accuracy.py:4-48}.  Same constructor kwargs and forward signature (weight, avg_factor,
+utils.py:26-52, focal_loss.py:10-157, accuracy.py:4-48}.  Same constructor kwargs and forward signature (weight, avg_factor,
 reduction_override)."""
 import math
 
@@ -226,6 +226,62 @@ class CIoULoss(_BoxLoss):
 
     def _loss(self, pred, target):
         return ciou_loss(pred, target, eps=self.eps)
+
+
+# ---------------------------------------------------------------- focal loss (focal_loss.py:10-157)
+def py_sigmoid_focal_loss(pred, target, weight=None, gamma=2.0, alpha=0.25, reduction='mean', avg_factor=None):
+    """focal_loss.py:10-41, the reference's own arithmetic: pred (N, C) logits, target (N, C) one-hot."""
+    pred_sigmoid = pred.sigmoid()
+    target = target.type_as(pred)
+    pt = (1 - pred_sigmoid) * target + pred_sigmoid * (1 - target)
+    focal_weight = (alpha * target + (1 - alpha) * (1 - target)) * pt.pow(gamma)
+    loss = F.binary_cross_entropy_with_logits(pred, target, reduction='none') * focal_weight
+    return weight_reduce_loss(loss, weight, reduction, avg_factor)
+
+
+def sigmoid_focal_loss(pred, target, weight=None, gamma=2.0, alpha=0.25, reduction='mean', avg_factor=None):
+    """focal_loss.py:44-87: pred (N, C) logits, target (N,) class indices with C = background, weight (N,), (N, C) or (N * C,).
+    fp32 GPU tensors go through htd_sigmoid_focal_loss (a per-row weight and the sum inside the launch); everything else
+    through the tensor formula on the one-hot target."""
+    from .. import mmcv_ops as M
+    N, C = pred.shape
+    device_op = pred.is_cuda and pred.dtype == torch.float32
+    if device_op and reduction != 'none' and (weight is None or weight.shape == (N, )):
+        total = M.sigmoid_focal_loss(pred, target, gamma, alpha, None if weight is None else weight.float(), 'sum')
+        if avg_factor is None:
+            return total / max(N * C, 1) if reduction == 'mean' else total
+        if reduction == 'mean':
+            return total / avg_factor
+        raise ValueError('avg_factor can not be used with reduction="sum"')
+    if device_op:
+        loss = M.sigmoid_focal_loss(pred, target, gamma, alpha, None, 'none')
+    else:
+        onehot = target.view(-1, 1) == torch.arange(C, device=target.device).view(1, -1)
+        loss = py_sigmoid_focal_loss(pred, onehot, None, gamma, alpha, 'none')
+    if weight is not None:
+        if weight.shape != loss.shape:
+            if weight.size(0) == loss.size(0):
+                weight = weight.view(-1, 1)          # one weight per prior
+            else:
+                assert weight.numel() == loss.numel()
+                weight = weight.view(loss.size(0), -1)
+        assert weight.ndim == loss.ndim
+    return weight_reduce_loss(loss, weight, reduction, avg_factor)
+
+
+@LOSSES.register_module()
+class FocalLoss(nn.Module):
+    def __init__(self, use_sigmoid=True, gamma=2.0, alpha=0.25, reduction='mean', loss_weight=1.0):
+        super().__init__()
+        assert use_sigmoid is True, 'Only sigmoid focal loss supported now.'
+        self.use_sigmoid, self.gamma, self.alpha = use_sigmoid, gamma, alpha
+        self.reduction, self.loss_weight = reduction, loss_weight
+
+    def forward(self, pred, target, weight=None, avg_factor=None, reduction_override=None):
+        assert reduction_override in (None, 'none', 'mean', 'sum')
+        reduction = reduction_override if reduction_override else self.reduction
+        return self.loss_weight * sigmoid_focal_loss(pred, target, weight, gamma=self.gamma, alpha=self.alpha,
+                                                     reduction=reduction, avg_factor=avg_factor)
 
 
 DECODED_BOX_LOSSES = (IoULoss, BoundedIoULoss, GIoULoss, DIoULoss, CIoULoss)       # index = `kind` of htd_roi_head_loss_decoded

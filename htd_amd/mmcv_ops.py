@@ -930,3 +930,200 @@ def segmented_topk(keys, segments):
     capi.call('htd_segmented_topk', _P(keys), _P(segs), _P(tab) if tab is not None else None, S, nchunks, _P(idx), _P(val),
               _P(ws), _S())
     return idx, val
+
+
+# ====================================================================== sigmoid focal loss (mmcv.ops.sigmoid_focal_loss)
+def sigmoid_focal_loss_tensor(input, target, gamma=2.0, alpha=0.25):
+    """The element losses (N, C) of py_sigmoid_focal_loss (mmdet/models/losses/focal_loss.py:10-41) in tensor operations, with
+    softplus in place of sigmoid + log so that any finite logit gives a finite loss.  target (N,) int64, C = background."""
+    C = input.size(1)
+    t = target.view(-1, 1) == torch.arange(C, device=input.device).view(1, -1)
+    z = torch.where(t, -input, input)
+    sp = torch.nn.functional.softplus(z, beta=1, threshold=1e4)          # = BCEWithLogits(input, t)
+    at = torch.where(t, input.new_full((), alpha), input.new_full((), 1 - alpha))
+    return at * torch.exp(-gamma * torch.nn.functional.softplus(-z, beta=1, threshold=1e4)) * sp
+
+
+def _table(ptrs):
+    return (ctypes.c_void_p * len(ptrs))(*ptrs)
+
+
+def _i64s(vals):
+    return (ctypes.c_int64 * len(vals))(*[int(v) for v in vals])
+
+
+class SigmoidFocalLossFunction(Function):
+    """htd_sigmoid_focal_loss: one launch leaves the element losses (reduction 'none' only), their fixed-grid partial sums and the
+    derivative; backward scales the derivative.  weight: (N,) per row or None."""
+
+    @staticmethod
+    def forward(ctx, input, target, gamma=2.0, alpha=0.25, weight=None, reduction='mean'):
+        assert reduction in ('none', 'mean', 'sum')
+        if input.dim() != 2 or target.dim() != 1 or target.size(0) != input.size(0) or target.dtype != torch.int64:
+            raise ValueError('sigmoid_focal_loss: input (N, C) float32 and target (N,) int64 expected')
+        if weight is not None and (weight.dim() != 1 or weight.size(0) != input.size(0)):
+            raise ValueError('sigmoid_focal_loss: weight must have one entry per row')
+        if not input.is_cuda:
+            with torch.enable_grad():
+                x = input.detach().requires_grad_()
+                loss = sigmoid_focal_loss_tensor(x, target, gamma, alpha)
+                if weight is not None:
+                    loss = loss * weight.view(-1, 1)
+                grad, = torch.autograd.grad(loss.sum(), x)
+            loss = loss.detach()
+            out = loss if reduction == 'none' else (loss.sum() if reduction == 'sum' else loss.sum() / max(loss.numel(), 1))
+        else:
+            x = _f32(input, 'sigmoid_focal_loss').contiguous()
+            N, C = x.shape
+            w = None if weight is None else _f32(weight, 'sigmoid_focal_loss').contiguous()
+            grad = torch.empty_like(x)
+            loss = torch.empty_like(x) if reduction == 'none' else None
+            partial = torch.empty(capi.lib().htd_focal_loss_partial_rows(), device=x.device, dtype=torch.float32)
+            capi.call('htd_sigmoid_focal_loss', _P(x), _P(target.contiguous()), _P(w), N, C, float(gamma), float(alpha), _P(loss),
+                      _P(partial), _P(grad), _S())
+            out = loss if reduction == 'none' else (partial.sum() if reduction == 'sum' else partial.sum() / max(N * C, 1))
+        ctx.save_for_backward(grad)
+        ctx.scale = 1.0 / max(input.numel(), 1) if reduction == 'mean' else 1.0
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        grad, = ctx.saved_tensors
+        return grad * (g * ctx.scale), None, None, None, None, None
+
+
+def sigmoid_focal_loss(input, target, gamma=2.0, alpha=0.25, weight=None, reduction='mean'):
+    """mmcv.ops.sigmoid_focal_loss: input (N, C) logits, target (N,) int64 class indices with C = background."""
+    return SigmoidFocalLossFunction.apply(input, target, gamma, alpha, weight, reduction)
+
+
+class SigmoidFocalLoss(nn.Module):
+    def __init__(self, gamma, alpha, weight=None, reduction='mean'):
+        super().__init__()
+        self.gamma, self.alpha, self.reduction = gamma, alpha, reduction
+        self.register_buffer('weight', weight)
+
+    def forward(self, input, target):
+        return sigmoid_focal_loss(input, target, self.gamma, self.alpha, self.weight, self.reduction)
+
+    def __repr__(self):
+        return f'{self.__class__.__name__}(gamma={self.gamma}, alpha={self.alpha}, reduction={self.reduction})'
+
+
+def nhwc_channel_stride(m):
+    """Per-pixel channel stride of a (B, C, h, w) tensor whose memory is [B][h][w][stride] -- a channels_last map or a channel
+    slice of one -- or None for any other layout.  The stride of a size-1 dimension says nothing and is not looked at."""
+    B, C, h, w = m.shape
+    sb, sc, sh, sw = m.stride()
+    sw = (sb if B > 1 else C) if h * w == 1 else (sh if w == 1 else sw)
+    if sc != 1 or sw < C or (h > 1 and w > 1 and sh != w * sw) or (B > 1 and sb != h * w * sw):
+        return None
+    return sw
+
+
+def _level_tables(maps):
+    """channels_last (B, C, h, w) maps (possibly channel slices of wider maps) -> pointer table, channel strides, pixel counts."""
+    ptrs, strides, pix = [], [], []
+    for m in maps:
+        sw = nhwc_channel_stride(m)
+        if sw is None:
+            raise ValueError('retina ops: maps must be channels_last (or channel slices of channels_last maps)')
+        ptrs.append(m.data_ptr())
+        strides.append(sw)
+        pix.append(m.size(2) * m.size(3))
+    return _table(ptrs), _i64s(strides), _i64s(pix)
+
+
+def retina_avg_factor(assigned):
+    """(num_pos (B,) int32, avg (1,) float32 = sum_b max(num_pos_b, 1)) on the device (anchor_head.py:288-291)."""
+    _need_gpu(assigned, 'retina_avg_factor')
+    B, A = assigned.shape
+    ws = torch.empty(capi.lib().htd_retina_avg_factor_workspace_bytes(B) // 4, dtype=torch.int32, device=assigned.device)
+    num_pos = torch.empty(B, dtype=torch.int32, device=assigned.device)
+    avg = torch.empty(1, dtype=torch.float32, device=assigned.device)
+    capi.call('htd_retina_avg_factor', _P(assigned.contiguous()), B, A, _P(ws), _P(num_pos), _P(avg), _S())
+    return num_pos, avg
+
+
+class RetinaLossFunction(Function):
+    """htd_retina_loss: (sum focal, sum box loss) / avg * loss weights over every level and image in one launch, which also
+    writes the finished gradient maps (scaled by loss weight / avg); backward hands them over, after htd_retina_grad_scale
+    applies incoming gradients other than 1 on the device, in place.  Single use: a second backward through the same forward
+    raises."""
+
+    @staticmethod
+    def forward(ctx, na, C, anchors, gts, gt_labels, assigned, avg, means, stds, gamma, alpha, pos_weight, box_loss, beta,
+                cls_weight, box_weight, *maps):
+        from .core.bbox import _f4
+        L = len(maps) // 2
+        cls, reg = maps[:L], maps[L:]
+        B, A = assigned.shape
+        K = gts.size(1)
+        ct, cs, pix = _level_tables(cls)
+        rt, rs, _ = _level_tables(reg)
+        dev = assigned.device
+        gcls = [torch.empty(m.shape, device=dev, dtype=torch.float32, memory_format=CL) for m in cls]
+        greg = [torch.empty(m.shape, device=dev, dtype=torch.float32, memory_format=CL) for m in reg]
+        gct, gcs, _ = _level_tables(gcls)
+        grt, grs, _ = _level_tables(greg)
+        if list(gcs) != list(cs) or list(grs) != list(rs):
+            # maps that are slices of wider ones: the gradient maps take the same padded layout, padding written as zeros
+            gcls = [torch.empty(m.size(0), s, m.size(2), m.size(3), device=dev, dtype=torch.float32, memory_format=CL)[:, :m.size(1)]
+                    for m, s in zip(cls, cs)]
+            greg = [torch.empty(m.size(0), s, m.size(2), m.size(3), device=dev, dtype=torch.float32, memory_format=CL)[:, :m.size(1)]
+                    for m, s in zip(reg, rs)]
+            gct, gcs, _ = _level_tables(gcls)
+            grt, grs, _ = _level_tables(greg)
+        partial = torch.empty(capi.lib().htd_focal_loss_partial_rows(), 2, device=dev, dtype=torch.float32)
+        capi.call('htd_retina_loss', ct, cs, rt, rs, pix, L, B, int(na), int(C), _P(anchors), _P(gts), _P(gt_labels), _P(assigned),
+                  A, K, _f4(means), _f4(stds), float(gamma), float(alpha), float(pos_weight), int(box_loss), float(beta),
+                  _P(avg), float(cls_weight), float(box_weight), _P(partial), gct, grt, _S())
+        ctx.meta = (int(na), int(C), B, L)
+        ctx.save_for_backward(*gcls, *greg)
+        sums = partial.sum(0) / avg
+        return sums[0] * cls_weight, sums[1] * box_weight
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_cls, g_box):
+        na, C, B, L = ctx.meta
+        grads = ctx.saved_tensors
+        gcls, greg = grads[:L], grads[L:]
+        gct, gcs, pix = _level_tables(gcls)
+        grt, grs, _ = _level_tables(greg)
+        if all(s % 4 == 0 for s in gcs):
+            # the saved maps are scaled where they are (no second 258 MB pass): one backward per forward
+            if getattr(ctx, 'scaled', False):
+                raise RuntimeError('retina_loss: a second backward through the same forward (retain_graph=True) is not supported: '
+                                   'the gradient maps were handed over and scaled in place by the first')
+            ctx.scaled = True
+            capi.call('htd_retina_grad_scale', gct, gcs, grt, grs, pix, L, B, na, C, _P(g_cls.float().contiguous()),
+                      _P(g_box.float().contiguous()), _S())
+        else:
+            gcls, greg = [g * g_cls for g in gcls], [g * g_box for g in greg]
+        return (None, ) * 16 + tuple(gcls) + tuple(greg)
+
+
+def retina_loss(cls_maps, reg_maps, na, C, anchors, gts, gt_labels, assigned, avg, means, stds, gamma, alpha, pos_weight,
+                box_loss, beta, cls_weight=1.0, box_weight=1.0):
+    """-> (loss_cls, loss_bbox) of a RetinaNet-style head from its per-level (B, na * C, h, w) / (B, na * 4, h, w) maps."""
+    _need_gpu(assigned, 'retina_loss')
+    for m in list(cls_maps) + list(reg_maps):
+        _f32(m, 'retina_loss')
+    return RetinaLossFunction.apply(na, C, anchors.float().contiguous(), gts.float().contiguous(), gt_labels.contiguous(),
+                                    assigned.contiguous(), avg, means, stds, gamma, alpha, pos_weight, box_loss, beta, cls_weight,
+                                    box_weight, *cls_maps, *reg_maps)
+
+
+def retina_keys(cls_maps, na, C):
+    """(B, A) max_c sigmoid(score) of every anchor of every level (level-major), one launch (htd_retina_keys)."""
+    _need_gpu(cls_maps[0], 'retina_keys')
+    for m in cls_maps:
+        _f32(m, 'retina_keys')
+    ct, cs, pix = _level_tables(cls_maps)
+    B = cls_maps[0].size(0)
+    A = na * sum(pix)
+    keys = torch.empty(B, A, device=cls_maps[0].device, dtype=torch.float32)
+    capi.call('htd_retina_keys', ct, cs, pix, len(cls_maps), B, int(na), int(C), _P(keys), _S())
+    return keys

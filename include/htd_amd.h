@@ -593,6 +593,51 @@ int htd_rpn_loss_l1(const float *cls, const float *reg, const float *anchors, co
                     const uint8_t *pos, const uint8_t *neg, int B, int A, int K, const float *means4, const float *stds4,
                     float pos_weight, float *partial, float *grad_cls, float *grad_reg, void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * Sigmoid focal loss (replaces mmcv.ops.sigmoid_focal_loss as mmdet/models/losses/focal_loss.py:44-87 calls it; the
+ * arithmetic is py_sigmoid_focal_loss, focal_loss.py:10-41, with the stable softplus form: finite for any finite logit).
+ *   loss = BCEWithLogits(x, t) * (alpha t + (1 - alpha)(1 - t)) * pt^gamma,  pt = (1 - sigmoid x) t + sigmoid x (1 - t),
+ *   t = one-hot of labels [N] int64, label == C = background (no column); weight [N] per row or NULL.
+ * loss_out [N][C] (NULL unless reduction='none' is wanted) = weighted element losses; partial
+ * [htd_focal_loss_partial_rows()] = per-block sums of them in a fixed grid (add in row order: reproducible);
+ * grad [N][C] = derivative of the plain weighted sum.  gamma == 2 takes a path without pow.
+ * ---------------------------------------------------------------------------------- */
+int htd_focal_loss_partial_rows(void);
+int htd_sigmoid_focal_loss(const float *logits, const int64_t *labels, const float *weight, int64_t N, int C, float gamma,
+                           float alpha, float *loss_out, float *partial, float *grad, void *stream);
+/* The averaging factor of a dense head without sampling (dense_heads/anchor_head.py:288-291,466-467): num_pos [B] = anchors
+ * with assigned > 0 per image, *avg_factor = sum_b max(num_pos_b, 1), both left on the device.  workspace:
+ * htd_retina_avg_factor_workspace_bytes(B) bytes. */
+int64_t htd_retina_avg_factor_workspace_bytes(int B);
+int htd_retina_avg_factor(const int64_t *assigned, int B, int A, void *workspace, int *num_pos, float *avg_factor,
+                          void *stream);
+/* RetinaHead loss of the whole batch over all L <= 8 pyramid levels in one launch (AnchorHead.loss / loss_single,
+ * dense_heads/anchor_head.py:373-488 with FocalLoss and SmoothL1Loss / L1Loss, the targets of _get_targets_single :172-269 with
+ * PseudoSampler and bbox2delta formed on the fly).  cls / reg / grad_cls / grad_reg are HOST tables of L device pointers:
+ * level l's classification map [B][pix[l]][cls_stride[l]] (channel a * C + c = class c of anchor a < na, the rest padding) and
+ * regression map [B][pix[l]][reg_stride[l]] (channel 4 a + j), read in place; the gradient maps have the same layout.
+ * anchors [A][4] level-major (A = na * sum pix), gts [B][K][4], gt_labels [B][K], assigned [B][A] as htd_max_iou_assign leaves
+ * it (-1: the anchor takes no part in this image, 0: background, k + 1: gt k); means4 / stds4 HOST arrays; rows of a positive
+ * weigh pos_weight when it is > 0; box_loss 0 = SmoothL1 (beta > 0), 1 = L1.  avg_factor is a DEVICE scalar
+ * (htd_retina_avg_factor): no host read.  partial [htd_focal_loss_partial_rows()][2] = per-block {sum focal, sum box loss},
+ * unscaled; the gradient maps receive d(cls_weight * sum focal / avg) and d(box_weight * sum box / avg), every element
+ * written exactly once, zeros (padding channels, anchors with assigned < 0) included: no memset, no atomics. */
+int htd_retina_loss(const float *const *cls, const int64_t *cls_stride, const float *const *reg, const int64_t *reg_stride,
+                    const int64_t *pix, int L, int B, int na, int C, const float *anchors, const float *gts,
+                    const int64_t *gt_labels, const int64_t *assigned, int A, int K, const float *means4,
+                    const float *stds4, float gamma, float alpha, float pos_weight, int box_loss, float beta,
+                    const float *avg_factor, float cls_weight, float box_weight, float *partial, float *const *grad_cls,
+                    float *const *grad_reg, void *stream);
+/* The gradient maps of htd_retina_loss times the incoming gradients *g_cls / *g_box (device scalars), in place; a factor
+ * of exactly 1 leaves its maps untouched, decided on the device.  Channel strides must be multiples of 4. */
+int htd_retina_grad_scale(float *const *grad_cls, const int64_t *cls_stride, float *const *grad_reg,
+                          const int64_t *reg_stride, const int64_t *pix, int L, int B, int na, int C, const float *g_cls,
+                          const float *g_box, void *stream);
+/* keys [B][A] = max_c sigmoid(cls score) of every anchor of every level in one launch: what AnchorHead._get_bboxes_single
+ * (dense_heads/anchor_head.py:633-641) ranks the nms_pre cut by.  Tables as in htd_retina_loss. */
+int htd_retina_keys(const float *const *cls, const int64_t *cls_stride, const int64_t *pix, int L, int B, int na, int C,
+                    float *keys, void *stream);
+
 /* nn.MaxPool2d(kernel, stride, padding) of the ResNet stem (backbones/resnet.py:509,629) on NHWC maps
  * x [B][H][W][C] -> y [B][Ho][Wo][C], C % 4 == 0, padding = -inf, floor mode.  idx (may be NULL for inference; int32
  * [B][Ho][Wo][C]) records the input pixel hi*W+wi of the first maximum of each window; bwd sends the gradient there
