@@ -982,8 +982,9 @@ extern "C" int htd_bgemm_nt(const float *a, const float *b, float *c, int G, int
 }
 
 // The same over zero-padded groups: counts[g] (device, int64) entries of group g are real.  limit bits: 1 = rows of a / c,
-// 2 = rows of b = columns of c, 4 = the reduction index; what lies beyond the count must be zero in the operands (it is
-// not read) and is written as zeros in c.  PGraph's three contractions (htd_bbox_head.py:210,213-216) at B = 64 x 512
+// 2 = rows of b = columns of c, 4 = the reduction index; what lies beyond the count must be zero in the operands (only whole
+// tiles of padding are skipped: a live tile multiplies all its rows, and with bit 4 the last K slice is read up to the next
+// multiple of the slice length) and is written as zeros in c.  PGraph's three contractions (htd_bbox_head.py:210,213-216) at B = 64 x 512
 // proposals pad 256 groups to the largest image: 584 GFLOP issued for 123 GFLOP of real groups without this.
 extern "C" int htd_bgemm_nt_counts(const float *a, const float *b, float *c, int G, int M, int N, int K,
                                    const int64_t *counts, int limit, void *stream)

@@ -138,16 +138,19 @@ __global__ void zero_words(unsigned long long *p, int64_t n)
         p[i] = 0ull;
 }
 
+constexpr int64_t SEG_CAP = 64ll * 64 * KMAX;      // boxes per segment
+
 int64_t ncb_for(int64_t max_seg) { return (max_seg + 63) / 64; }
+
+// column tiles of the worst case of n_total boxes: one segment holding everything, capped by the per-segment limit.  The one
+// place the single-problem form's workspace layout comes from (htd_nms_workspace_bytes and htd_nms_sorted).
+int64_t ncb_capped(int64_t n_total) { return ncb_for(n_total < SEG_CAP ? n_total : SEG_CAP); }
 
 }  // namespace
 
 extern "C" int64_t htd_nms_workspace_bytes(int64_t n_total)
 {
-    // worst case: one segment holding everything, capped by the per-segment limit
-    const int64_t cap = 64ll * 64 * KMAX;
-    const int64_t ms = n_total < cap ? n_total : cap;
-    return n_total * ncb_for(ms) * 8 + 64;
+    return n_total * ncb_capped(n_total) * 8 + 64;
 }
 
 extern "C" int htd_nms_sorted_batched(const float *boxes, const int64_t *seg_offsets, int segments,
@@ -155,8 +158,7 @@ extern "C" int htd_nms_sorted_batched(const float *boxes, const int64_t *seg_off
                                       int offset, void *workspace, void *stream)
 {
     HTD_REQUIRE(segments >= 0 && n_total >= 0 && max_seg >= 0, "nms: negative size");
-    HTD_REQUIRE(max_seg <= 64ll * 64 * KMAX, "nms: segment of %lld boxes exceeds the %d-box limit",
-                (long long)max_seg, 64 * 64 * KMAX);
+    HTD_REQUIRE(max_seg <= SEG_CAP, "nms: segment of %lld boxes exceeds the %d-box limit", (long long)max_seg, (int)SEG_CAP);
     HTD_REQUIRE(offset == 0 || offset == 1, "nms: offset must be 0 or 1");
     if (segments == 0 || n_total == 0 || max_seg == 0) return HTD_OK;
     HTD_REQUIRE(boxes && seg_offsets && keep_mask && workspace, "nms: null pointer");
@@ -180,10 +182,16 @@ __global__ void write_two(int64_t *p, int64_t n) { p[0] = 0; p[1] = n; }
 extern "C" int htd_nms_sorted(const float *boxes, uint8_t *keep_mask, int64_t n, float iou_thr, int offset,
                               void *workspace, void *stream)
 {
+    // everything is checked before the first launch: the segment table below is written inside the workspace only if n is
+    // within the limit htd_nms_workspace_bytes sized it for
+    HTD_REQUIRE(n >= 0, "nms: negative size");
+    HTD_REQUIRE(n <= SEG_CAP, "nms: segment of %lld boxes exceeds the %d-box limit", (long long)n, (int)SEG_CAP);
+    HTD_REQUIRE(offset == 0 || offset == 1, "nms: offset must be 0 or 1");
     if (n == 0) return HTD_OK;
-    HTD_REQUIRE(workspace, "nms: null workspace");
+    HTD_REQUIRE(boxes && keep_mask && workspace, "nms: null pointer");
+    HTD_REQUIRE(((uintptr_t)boxes & 15) == 0, "nms: boxes must be 16-byte aligned");
     // the segment table of the single-problem form lives in the last 64 bytes of the workspace
-    const int64_t ncb = ncb_for(n);
+    const int64_t ncb = ncb_capped(n);
     int64_t *seg = (int64_t *)((char *)workspace + n * ncb * 8);
     seg = (int64_t *)(((uintptr_t)seg + 15) & ~(uintptr_t)15);
     hipLaunchKernelGGL(write_two, dim3(1), dim3(1), 0, (hipStream_t)stream, seg, n);

@@ -1648,8 +1648,8 @@ class BatchedGemmNT(Function):
 def bgemm_nt(a, b, counts=None, limit=0):
     """Batched a @ b^T; every dimension that becomes a row count must be a multiple of 128 when G > 1 and every
     reduction length a multiple of 8 (PGraph pads its groups accordingly).  counts (G,) int64 device tensor + limit bits
-    (1 rows of a, 2 rows of b, 4 reduction): group g has counts[g] real entries along those axes, zeros beyond -- the padding
-    is then neither read nor multiplied (htd_bgemm_nt_counts)."""
+    (1 rows of a, 2 rows of b, 4 reduction): group g has counts[g] real entries along those axes and MUST hold zeros beyond --
+    whole tiles and K slices of padding are then skipped on the device (htd_bgemm_nt_counts)."""
     return BatchedGemmNT.apply(a, b, counts, int(limit))
 
 

@@ -115,7 +115,8 @@ int htd_roi_align_bwd_gather(const float *grad_out, const float *rois, const int
  * core/post_processing/bbox_nms.py:65.  Suppression rule: inter / union > iou_thr with an
  * IEEE fp32 division (the CPU path's arithmetic), offset in {0,1}.
  *   boxes [n][4] sorted;  keep_mask [n] uint8 out (1 = survivor);
- *   workspace: htd_nms_workspace_bytes(n) bytes.
+ *   workspace: htd_nms_workspace_bytes(n) bytes.  One problem (segment) holds at most 16 384 boxes; a larger n or max_seg is
+ *   rejected before anything is launched.
  * Batched form: `segments` problems stored back to back; seg_offsets[segments+1] (device,
  * int64) gives each problem's [begin,end) row range; one launch handles them all, no host
  * synchronisation (per-image RPN NMS, rpn_head.py:78-168).
@@ -250,9 +251,10 @@ int htd_conv2d_fwd(const float *x, const float *w, const float *bias, const floa
  * (torch.mm calls of htd_bbox_head.py:210,213,214,216 batched over all (image, level) groups). */
 int htd_bgemm_nt(const float *a, const float *b, float *c, int G, int M, int N, int K, void *stream);
 /* The same over zero-padded groups: counts [G] (DEVICE, int64) says how many leading entries of group g are real; limit
- * bits: 1 = rows of a / c, 2 = rows of b (= columns of c), 4 = the reduction index.  Operands must be zero beyond the count
- * (not read); c is written as zeros there.  No host read of the group sizes (the reference's per-group loop reads them,
- * htd_bbox_head.py:198-219). */
+ * bits: 1 = rows of a / c, 2 = rows of b (= columns of c), 4 = the reduction index.  Operands MUST be zero beyond the count:
+ * whole tiles of padding are skipped, but rows and columns inside a live tile are multiplied, and with bit 4 the last K slice
+ * is read up to the next multiple of the slice length (32, 16 or 8).  c is written as zeros there.  No host read of the group
+ * sizes (the reference's per-group loop reads them, htd_bbox_head.py:198-219). */
 int htd_bgemm_nt_counts(const float *a, const float *b, float *c, int G, int M, int N, int K, const int64_t *counts, int limit,
                         void *stream);
 int htd_conv2d_flip_weights(const float *w, float *wT, int Co, int kh, int kw, int Ci, void *stream);

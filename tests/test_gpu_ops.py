@@ -178,9 +178,12 @@ def clustered_boxes(gen, n, span=300.):
     return torch.cat([c - wh / 2, c + wh / 2], 1)
 
 
-@pytest.mark.parametrize('n', [1, 63, 64, 65, 500, 3000])
+@pytest.mark.parametrize('n', [1, 63, 64, 65, 500, 3000, 4096, 4097, 8256, 16384])
 @pytest.mark.parametrize('thr', [0.5, 0.7])
 def test_nms_bit_exact(dev, n, thr):
+    """n > 4096: nms_reduce_kernel's column-tile slots 1..3 and the `(q >> 6) == k` broadcast (a lane owns tiles lane, lane + 64,
+    ...); 16384 = 64 * 64 * KMAX is the limit.  The slots are exercised only if later 4096-row blocks hold rows that earlier
+    rows suppress and rows that survive, which the oracle's keep set must show."""
     from htd_amd import mmcv_ops as M
     from oracle import ops as O
     gen = torch.Generator().manual_seed(n)
@@ -190,11 +193,47 @@ def test_nms_bit_exact(dev, n, thr):
         scores[5] = scores[3]          # exact score tie: lower index first
         boxes[7] = boxes[2]            # duplicate box
     dets_r, keep_r = O.nms(boxes, scores, thr)
+    if n > 4096:
+        kept = torch.zeros(n, dtype=torch.bool)
+        kept[keep_r] = True
+        kept = kept[torch.sort(scores, descending=True, stable=True)[1]]           # in the sorted order the kernel walks
+        for blk in kept.split(4096):
+            if blk.numel() > 1:                                                      # n = 4097: the last block is one row
+                assert 0 < int(blk.sum()) < blk.numel(), 'a block of 4096 sorted rows without both kept and suppressed rows'
     dets, keep = M.nms(boxes.to(dev), scores.to(dev), thr)
     assert torch.equal(keep.cpu(), keep_r)
     assert torch.equal(dets.cpu(), dets_r)
     _, keep1 = M.nms(boxes.to(dev), scores.to(dev), thr, offset=1)
     assert torch.equal(keep1.cpu(), O.nms(boxes, scores, thr, 1)[1])
+
+
+def test_nms_segments_of_mixed_size_share_one_mask(dev):
+    """Six segments of 0, 1, 64, 5000, 130 and 0 boxes in one launch: the mask's row length (79 words) comes from the 5000-box
+    segment, whose chunks past 4096 use slot 1, while the short and the empty segments use a corner of the same mask."""
+    from htd_amd import mmcv_ops as M
+    from oracle import ops as O
+    sizes = [0, 1, 64, 5000, 130, 0]
+    gen = torch.Generator().manual_seed(6)
+    boxes = torch.cat([clustered_boxes(gen, s) for s in sizes])
+    seg = torch.tensor([0] + sizes).cumsum(0)
+    keep = M.nms_sorted_mask(boxes.to(dev), 0.5, 0, seg.to(dev), max(sizes)).cpu()
+    assert keep.shape == (sum(sizes), )
+    for s, b in zip(sizes, seg.tolist()):
+        ref = torch.zeros(s, dtype=torch.uint8)
+        ref[O.nms(boxes[b:b + s], -torch.arange(s, dtype=torch.float32), 0.5)[1]] = 1        # already in descending-score order
+        assert torch.equal(keep[b:b + s], ref), s
+
+
+def test_nms_rejects_a_segment_beyond_the_limit_before_any_launch(dev):
+    """n = 16385 > 64 * 64 * KMAX: htd_nms_sorted used to write its segment table past the workspace (sized for the capped row
+    length) and only then reject the size.  It now validates first and launches nothing."""
+    from htd_amd import mmcv_ops as M
+    n = 16385
+    gen = torch.Generator().manual_seed(n)
+    boxes, scores = clustered_boxes(gen, n).to(dev), torch.rand(n, generator=gen).to(dev)
+    with pytest.raises(ValueError, match='exceeds'):
+        M.nms(boxes, scores, 0.5)
+    torch.cuda.synchronize()
 
 
 def test_nms_empty(dev):
