@@ -2,7 +2,11 @@
 
 Reference: dense_heads/anchor_head.py:14-682 (AnchorHead: forward, get_anchors, get_targets, loss, get_bboxes),
 base_dense_head.py:22-59 (forward_train), retina_head.py:8-114 (RetinaHead).  Same registry names, constructor kwargs,
-state_dict keys (cls_convs / reg_convs / retina_cls / retina_reg) and return structures.
+state_dict keys (cls_convs / reg_convs / retina_cls / retina_reg) and return structures.  AnchorHead is also the base of RPNHead
+(detector/rpn_head.py), as in the reference: anchors, per-image targets (gt_labels None: foreground is class 0), the
+reference-order loss and forward_train are written once, here.  So are the constants of the pyramid's map shapes: `_shape_key`
+makes their cache key, `_cached` fetches them, and `_anchors_inside`, the RPN's proposal constants and the level-concatenated
+anchors of `_get_bboxes_batched` all go through the two.
 
 `loss` has two forms, like RPNHead.loss.  The tensor form follows the reference's order of operations (per image targets, per
 level losses) and works with any loss modules, `reg_decoded_bbox`, ignore boxes and on the CPU.  The fused form -- FocalLoss with
@@ -94,7 +98,7 @@ class AnchorHead(nn.Module):
             losses = self.loss(*outs, gt_bboxes, gt_labels, img_metas, gt_bboxes_ignore=gt_bboxes_ignore)
         if proposal_cfg is None:
             return losses
-        return losses, self.get_bboxes(*outs, img_metas, cfg=proposal_cfg)
+        return losses, self.get_bboxes(*outs, img_metas, cfg=proposal_cfg, **kwargs)
 
     def simple_test(self, feats, img_metas, rescale=False):
         return self.get_bboxes(*self(feats), img_metas, rescale=rescale)
@@ -216,16 +220,29 @@ class AnchorHead(nn.Module):
             all(t.is_cuda and t.dtype == torch.float32 and M.nhwc_channel_stride(t) is not None
                 for t in list(cls_scores) + list(bbox_preds))       # (other layouts, e.g. NCHW-contiguous maps: the tensor path)
 
+    # ------------------------------------------------------------------ constants of the map shapes
+    @staticmethod
+    def _shape_key(featmap_sizes):
+        """Cache key of whatever is computed from the pyramid's map sizes: the (h, w) pairs themselves, never their products --
+        a portrait and a landscape batch have the same number of anchors on every level and different anchors."""
+        return tuple(tuple(int(v) for v in f) for f in featmap_sizes)
+
+    def _cached(self, name, cap, key, make):
+        """self.<name>[key], made by make() on a miss; a cache that has grown past `cap` entries is emptied first."""
+        cache = self.__dict__.setdefault(name, {})
+        if key not in cache:
+            if len(cache) > cap:
+                cache.clear()
+            cache[key] = make()
+        return cache[key]
+
     def _anchors_inside(self, featmap_sizes, img_metas, dev):
         """(A, 4) level-concatenated anchors and the (B, A) mask of anchors that are valid and inside their image
-        (anchor_head.py:200-207): constants of (feature-map sizes, image shapes), cached under exactly those."""
+        (anchor_head.py:200-207, core/anchor/utils.py:20-46): constants of (feature-map sizes, image shapes), cached under
+        exactly those."""
         border = self.train_cfg.allowed_border
-        key = (tuple(tuple(int(v) for v in f) for f in featmap_sizes),
-               tuple((tuple(m['img_shape'][:2]), tuple(m['pad_shape'][:2])) for m in img_metas), str(dev), border)
-        cache = self.__dict__.setdefault('_inside_cache', {})
-        if key not in cache:
-            if len(cache) > 64:
-                cache.clear()
+
+        def make():
             anchor_list, valid_flag_list = self.get_anchors(featmap_sizes, img_metas, device=dev)
             flat_anchors = torch.cat(anchor_list[0])
             valid = torch.stack([torch.cat(v) for v in valid_flag_list])
@@ -233,8 +250,17 @@ class AnchorHead(nn.Module):
                 lim = const_tensor([[m['img_shape'][1], m['img_shape'][0]] for m in img_metas], dev, flat_anchors.dtype)
                 valid = valid & (flat_anchors[None, :, 0] >= -border) & (flat_anchors[None, :, 1] >= -border) & \
                     (flat_anchors[None, :, 2] < lim[:, 0:1] + border) & (flat_anchors[None, :, 3] < lim[:, 1:2] + border)
-            cache[key] = (flat_anchors.contiguous(), valid.contiguous())
-        return cache[key]
+            return flat_anchors, valid
+        key = (self._shape_key(featmap_sizes), tuple((tuple(m['img_shape'][:2]), tuple(m['pad_shape'][:2])) for m in img_metas),
+               str(dev), border)
+        return self._cached('_inside_cache', 64, key, make)
+
+    def _level_cuts(self, cls_scores, nms_pre):
+        """Per level: its number of anchors, how many of them the cut to nms_pre keeps (all when nms_pre <= 0) and its first
+        column in the level-concatenated order."""
+        Ns = [int(c.shape[2] * c.shape[3]) * self.num_anchors for c in cls_scores]
+        ks = [n if nms_pre <= 0 else min(nms_pre, n) for n in Ns]
+        return Ns, ks, [sum(Ns[:l]) for l in range(len(Ns))]
 
     def loss_fused(self, cls_scores, bbox_preds, gt_bboxes, gt_labels, img_metas):
         from ..core.bbox import batched_max_iou_assign, pad_gt_batch
@@ -328,19 +354,11 @@ class AnchorHead(nn.Module):
         dev = cls_scores[0].device
         C, na = self.cls_out_channels, self.num_anchors
         featmap_sizes = [c.shape[-2:] for c in cls_scores]
-        Ns = [int(c.shape[2] * c.shape[3]) * na for c in cls_scores]
-        nms_pre = cfg.get('nms_pre', -1)
-        ks = [n if nms_pre <= 0 or n <= nms_pre else nms_pre for n in Ns]
-        total, offs = sum(Ns), [sum(Ns[:l]) for l in range(L)]
+        Ns, ks, offs = self._level_cuts(cls_scores, cfg.get('nms_pre', -1))
+        total = sum(Ns)
         cls_scores = [c.detach() for c in cls_scores]
-        # keyed on the map sizes themselves: transposed (portrait / landscape) batches have equal products
-        ck = (tuple(tuple(int(v) for v in f) for f in featmap_sizes), tuple(ks), str(dev))
-        cache = self.__dict__.setdefault('_bbox_cache', {})
-        if ck not in cache:
-            if len(cache) > 32:
-                cache.clear()
-            cache[ck] = torch.cat(self.anchor_generator.grid_anchors(featmap_sizes, device=dev))
-        anchors = cache[ck]
+        anchors = self._cached('_bbox_cache', 32, (self._shape_key(featmap_sizes), tuple(ks), str(dev)),
+                               lambda: torch.cat(self.anchor_generator.grid_anchors(featmap_sizes, device=dev)))
         cut = [l for l in range(L) if ks[l] < Ns[l]]
         pieces = [torch.arange(offs[l], offs[l] + Ns[l], device=dev)[None].expand(B, Ns[l]) for l in range(L)]
         if cut:

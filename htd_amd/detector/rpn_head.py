@@ -1,22 +1,23 @@
-"""RPN head of HTD: forward, targets + loss, proposal generation.
+"""RPN head of HTD: forward, the batched loss, proposal generation.
 
-Reference: dense_heads/rpn_head.py:12-168 (RPNHead), anchor_head.py:14-682 (AnchorHead: targets/loss/
-get_bboxes), base_dense_head.py:22-59 (forward_train), rpn_test_mixin.py:24-37 (simple_test_rpn).
-Same registry name, constructor kwargs, state_dict keys (rpn_conv / rpn_cls / rpn_reg) and return
-structures.  What differs is execution: proposal generation handles ALL images and levels of the batch
-together -- one stable sort per level over the (B, A_l) score matrix, one decode, ONE batched NMS
-launch whose segments are the (image, level) pairs -- instead of a Python loop over images with a
-sort + NMS each (rpn_head.py:78-168).  The kept set, its order and its values are the same.
+Reference: dense_heads/rpn_head.py:12-168 (RPNHead), rpn_test_mixin.py:24-37 (simple_test_rpn).  As there, RPNHead is an
+AnchorHead (detector/anchor_heads.py) with one class: the constructor, get_anchors, get_targets, the reference-order loss
+(`loss_tensor`, here under the name `loss_per_image`), `_anchors_inside`, forward_train and the shape-keyed caches are
+inherited.  Same registry name, constructor kwargs, state_dict keys (rpn_conv / rpn_cls / rpn_reg) and return structures.
+What this file adds is execution.  The loss of the production path assigns, samples and sums over the whole batch
+(`loss_batched`).  Proposal generation handles ALL images and levels of the batch together -- one ranking per level over
+the (B, A_l) score matrix, one decode, ONE batched NMS launch whose segments are the (image, level) pairs -- instead of a
+Python loop over images with a sort + NMS each (rpn_head.py:78-168).  The kept set, its order and its values are the same.
 """
 import torch
-import torch.nn as nn
 
-from ..core import (anchor_inside_flags, images_to_levels, multi_apply, unmap)
-from ..core.bbox import delta2bbox, delta2bbox_clip_device
+from ..core import multi_apply
+from ..core.bbox import delta2bbox_clip_device
 from ..core.misc import arange_cached, const_tensor
 from .. import mmcv_ops as M
 from ..mmcv_ops import nms_sorted_mask
-from ..registry import (HEADS, build_anchor_generator, build_assigner, build_bbox_coder, build_loss, build_sampler)
+from ..registry import HEADS
+from .anchor_heads import AnchorHead
 from .bricks import Conv2d, normal_init
 
 
@@ -134,31 +135,12 @@ class _RPNGatherHeads(torch.autograd.Function):
 
 
 @HEADS.register_module()
-class RPNHead(nn.Module):
-    def __init__(self, in_channels, feat_channels=256,
-                 anchor_generator=dict(type='AnchorGenerator', scales=[8, 16, 32], ratios=[0.5, 1.0, 2.0],
-                                       strides=[4, 8, 16, 32, 64]),
-                 bbox_coder=dict(type='DeltaXYWHBBoxCoder', clip_border=True, target_means=(.0, .0, .0, .0),
-                                 target_stds=(1.0, 1.0, 1.0, 1.0)),
-                 reg_decoded_bbox=False,
-                 loss_cls=dict(type='CrossEntropyLoss', use_sigmoid=True, loss_weight=1.0),
-                 loss_bbox=dict(type='SmoothL1Loss', beta=1.0 / 9.0, loss_weight=1.0), train_cfg=None, test_cfg=None):
-        super().__init__()
-        self.in_channels, self.num_classes, self.feat_channels = in_channels, 1, feat_channels
-        self.use_sigmoid_cls = loss_cls.get('use_sigmoid', False)
-        assert self.use_sigmoid_cls and not reg_decoded_bbox, 'HTD configs use a sigmoid RPN with delta targets'
-        self.sampling = True
-        self.cls_out_channels = self.num_classes
-        self.reg_decoded_bbox = reg_decoded_bbox
-        self.bbox_coder = build_bbox_coder(bbox_coder)
-        self.loss_cls = build_loss(loss_cls)
-        self.loss_bbox = build_loss(loss_bbox)
-        self.train_cfg, self.test_cfg = train_cfg, test_cfg
-        if self.train_cfg:
-            self.assigner = build_assigner(self.train_cfg.assigner)
-            self.sampler = build_sampler(self.train_cfg.sampler, context=self)
-        self.anchor_generator = build_anchor_generator(anchor_generator)
-        self.num_anchors = self.anchor_generator.num_base_anchors[0]
+class RPNHead(AnchorHead):
+    def __init__(self, in_channels, **kwargs):
+        super().__init__(1, in_channels, **kwargs)
+        assert self.use_sigmoid_cls and not self.reg_decoded_bbox, 'HTD configs use a sigmoid RPN with delta targets'
+
+    def _init_layers(self):
         self.rpn_conv = Conv2d(self.in_channels, self.feat_channels, 3, padding=1)
         self.rpn_cls = Conv2d(self.feat_channels, self.num_anchors * self.cls_out_channels, 1)
         self.rpn_reg = Conv2d(self.feat_channels, self.num_anchors * 4, 1)
@@ -224,14 +206,6 @@ class RPNHead(nn.Module):
             reg.append(r)
         return cls, reg
 
-    def forward_train(self, x, img_metas, gt_bboxes, gt_labels=None, gt_bboxes_ignore=None, proposal_cfg=None,
-                      **kwargs):
-        outs = self(x)
-        losses = self.loss(*outs, gt_bboxes, img_metas, gt_bboxes_ignore=gt_bboxes_ignore)
-        if proposal_cfg is None:
-            return losses
-        return losses, self.get_bboxes(*outs, img_metas, cfg=proposal_cfg, padded=kwargs.get('padded', False))
-
     def simple_test_rpn(self, x, img_metas):
         return self.get_bboxes(*self(x), img_metas)
 
@@ -247,58 +221,6 @@ class RPNHead(nn.Module):
         return [merge_aug_proposals(p, m, self.test_cfg) for p, m in zip(aug_proposals, aug_img_metas)]
 
     # ------------------------------------------------------------------ targets + loss
-    def get_anchors(self, featmap_sizes, img_metas, device='cuda'):
-        mlvl = self.anchor_generator.grid_anchors(featmap_sizes, device)
-        anchor_list = [mlvl for _ in img_metas]
-        valid_flag_list = [self.anchor_generator.valid_flags(featmap_sizes, m['pad_shape'], device)
-                           for m in img_metas]
-        return anchor_list, valid_flag_list
-
-    def _get_targets_single(self, flat_anchors, valid_flags, gt_bboxes, gt_bboxes_ignore, img_meta):
-        """anchor_head.py:172-269 with gt_labels=None (RPN): fg label 0, bg label num_classes (=1)."""
-        inside = anchor_inside_flags(flat_anchors, valid_flags, img_meta['img_shape'][:2],
-                                     self.train_cfg.allowed_border)
-        anchors = flat_anchors[inside, :]
-        assign_result = self.assigner.assign(anchors, gt_bboxes, gt_bboxes_ignore, None)
-        sr = self.sampler.sample(assign_result, anchors, gt_bboxes)
-        n = anchors.shape[0]
-        bbox_targets = torch.zeros_like(anchors)
-        bbox_weights = torch.zeros_like(anchors)
-        labels = anchors.new_full((n, ), self.num_classes, dtype=torch.long)
-        label_weights = anchors.new_zeros(n, dtype=torch.float)
-        if len(sr.pos_inds) > 0:
-            bbox_targets[sr.pos_inds, :] = self.bbox_coder.encode(sr.pos_bboxes, sr.pos_gt_bboxes)
-            bbox_weights[sr.pos_inds, :] = 1.0
-            labels[sr.pos_inds] = 0
-            label_weights[sr.pos_inds] = 1.0 if self.train_cfg.pos_weight <= 0 else self.train_cfg.pos_weight
-        if len(sr.neg_inds) > 0:
-            label_weights[sr.neg_inds] = 1.0
-        total = flat_anchors.size(0)
-        return (unmap(labels, total, inside, fill=self.num_classes), unmap(label_weights, total, inside),
-                unmap(bbox_targets, total, inside), unmap(bbox_weights, total, inside), sr.pos_inds, sr.neg_inds)
-
-    def get_targets(self, anchor_list, valid_flag_list, gt_bboxes_list, img_metas, gt_bboxes_ignore_list=None):
-        num_imgs = len(img_metas)
-        num_level_anchors = [a.size(0) for a in anchor_list[0]]
-        flat_anchors = torch.cat(anchor_list[0])
-        if gt_bboxes_ignore_list is None:
-            gt_bboxes_ignore_list = [None] * num_imgs
-        res = [self._get_targets_single(flat_anchors, torch.cat(valid_flag_list[i]), gt_bboxes_list[i],
-                                        gt_bboxes_ignore_list[i], img_metas[i]) for i in range(num_imgs)]
-        num_total_pos = sum(max(r[4].numel(), 1) for r in res)
-        num_total_neg = sum(max(r[5].numel(), 1) for r in res)
-        lv = [images_to_levels([r[k] for r in res], num_level_anchors) for k in range(4)]
-        return lv[0], lv[1], lv[2], lv[3], num_total_pos, num_total_neg
-
-    def loss_single(self, cls_score, bbox_pred, labels, label_weights, bbox_targets, bbox_weights, num_total_samples):
-        cls_score = cls_score.permute(0, 2, 3, 1).reshape(-1, self.cls_out_channels)
-        loss_cls = self.loss_cls(cls_score, labels.reshape(-1), label_weights.reshape(-1),
-                                 avg_factor=num_total_samples)
-        bbox_pred = bbox_pred.permute(0, 2, 3, 1).reshape(-1, 4)
-        loss_bbox = self.loss_bbox(bbox_pred, bbox_targets.reshape(-1, 4), bbox_weights.reshape(-1, 4),
-                                   avg_factor=num_total_samples)
-        return loss_cls, loss_bbox
-
     def loss(self, cls_scores, bbox_preds, gt_bboxes, img_metas, gt_bboxes_ignore=None):
         """Exact reference order of operations (per image, per level) when a permutation source is installed
         (`core.set_randperm`, used by parity tests to replay the CPU generator); otherwise the batched,
@@ -308,28 +230,6 @@ class RPNHead(nn.Module):
                 self.assigner.ignore_iof_thr <= 0 and isinstance(self.assigner.neg_iou_thr, float):
             return self.loss_batched(cls_scores, bbox_preds, gt_bboxes, img_metas)
         return self.loss_per_image(cls_scores, bbox_preds, gt_bboxes, img_metas, gt_bboxes_ignore)
-
-    def _anchors_inside(self, featmap_sizes, img_metas, dev):
-        """(A,4) level-concatenated anchors and the (B,A) mask of anchors that are valid and inside their image
-        (anchor_head.py:200-207, core/anchor/utils.py:20-46): constants of (feature sizes, image shapes), cached."""
-        border = self.train_cfg.allowed_border
-        key = (tuple(tuple(int(v) for v in f) for f in featmap_sizes),
-               tuple((tuple(m['img_shape'][:2]), tuple(m['pad_shape'][:2])) for m in img_metas), str(dev), border)
-        cache = self.__dict__.setdefault('_inside_cache', {})
-        if key not in cache:
-            if len(cache) > 64:
-                cache.clear()
-            anchor_list, valid_flag_list = self.get_anchors(featmap_sizes, img_metas, device=dev)
-            flat_anchors = torch.cat(anchor_list[0])
-            valid = torch.stack([torch.cat(v) for v in valid_flag_list])                   # (B,A)
-            lim = const_tensor([[m['img_shape'][1], m['img_shape'][0]] for m in img_metas], dev, flat_anchors.dtype)
-            if border >= 0:
-                inside = valid & (flat_anchors[None, :, 0] >= -border) & (flat_anchors[None, :, 1] >= -border) & \
-                    (flat_anchors[None, :, 2] < lim[:, 0:1] + border) & (flat_anchors[None, :, 3] < lim[:, 1:2] + border)
-            else:
-                inside = valid
-            cache[key] = (flat_anchors, inside)
-        return cache[key]
 
     # -------------------------------------------------------------- batched targets + loss (production path)
     def loss_batched(self, cls_scores, bbox_preds, gt_bboxes, img_metas, keys=None):
@@ -394,14 +294,9 @@ class RPNHead(nn.Module):
 
     # -------------------------------------------------------------- reference-order path
     def loss_per_image(self, cls_scores, bbox_preds, gt_bboxes, img_metas, gt_bboxes_ignore=None):
-        featmap_sizes = [f.size()[-2:] for f in cls_scores]
-        assert len(featmap_sizes) == self.anchor_generator.num_levels
-        anchor_list, valid_flag_list = self.get_anchors(featmap_sizes, img_metas, device=cls_scores[0].device)
-        (labels, label_weights, bbox_targets, bbox_weights, num_pos, num_neg) = self.get_targets(
-            anchor_list, valid_flag_list, gt_bboxes, img_metas, gt_bboxes_ignore_list=gt_bboxes_ignore)
-        losses_cls, losses_bbox = multi_apply(self.loss_single, cls_scores, bbox_preds, labels, label_weights,
-                                              bbox_targets, bbox_weights, num_total_samples=num_pos + num_neg)
-        return dict(loss_rpn_cls=losses_cls, loss_rpn_bbox=losses_bbox)
+        """AnchorHead's tensor-form loss without labels (foreground is class 0), under the RPN's names."""
+        losses = self.loss_tensor(cls_scores, bbox_preds, gt_bboxes, None, img_metas, gt_bboxes_ignore)
+        return dict(loss_rpn_cls=losses['loss_cls'], loss_rpn_bbox=losses['loss_bbox'])
 
     # ------------------------------------------------------------------ proposals
     @torch.no_grad()
@@ -410,56 +305,68 @@ class RPNHead(nn.Module):
         padded=True: -> (dets (B, nms_post, 5) zero rows past k_i, k (B,) on the device) without reading k back."""
         cfg = self.test_cfg if cfg is None else cfg
         assert len(cls_scores) == len(bbox_preds)
-        B = cls_scores[0].size(0)
         dev = cls_scores[0].device
-        featmap_sizes = [c.shape[-2:] for c in cls_scores]
-        mlvl_anchors = None                                 # (made on demand: the flat path keeps its concatenation cached)
-        scores_l, deltas_l, anchors_l, seg_sizes = [], [], [], []
         record = getattr(self, 'record_trail', False)       # tests: which candidates survive, in which order
-        flat_ids, level_off = [], 0
-        L = len(cls_scores)
-        Ns = [int(c.shape[1] * c.shape[2] * c.shape[3]) for c in cls_scores]
-        ks = [n if cfg.nms_pre <= 0 else min(cfg.nms_pre, n) for n in Ns]
+        Ns, ks, offs = self._level_cuts(cls_scores, cfg.nms_pre)
         fused = dev.type == 'cuda' and max(ks) <= M.TOPK_KMAX and cls_scores[0].dtype == torch.float32
-        if fused:
-            # every (image, level) ranking of the call in one segmented top-k (htd_segmented_topk): the sorted first nms_pre of
-            # `scores.sort(descending=True)` (rpn_head.py:122-133), equal scores by ascending anchor index
-            total = sum(Ns)
-            if getattr(cls_scores, 'flat', None) is not None:
-                sig = cls_scores.flat.detach().sigmoid()
-            else:
-                sig = torch.cat([c.detach().permute(0, 2, 3, 1).reshape(B, -1) for c in cls_scores], 1).sigmoid_()
-            offs = [sum(Ns[:l]) for l in range(L)]
-            top_idx, top_val = M.segmented_topk(sig, [(b * total + offs[l], Ns[l], ks[l]) for b in range(B) for l in range(L)])
-            top_idx, top_val = top_idx.view(B, sum(ks)), top_val.view(B, sum(ks))
-        flat_ok = fused and getattr(cls_scores, 'flat', None) is not None and getattr(bbox_preds, 'flat', None) is not None and \
-            not record
-        if flat_ok:
-            # the levels' candidates through ONE gather each: rank inside (image, level) + the level's first anchor = index into
-            # the flat per-anchor tensors and the level-concatenated anchors (constants of the map sizes: cached)
-            # keyed on the map sizes, not on their products: transposed (portrait / landscape) maps have equal Ns
-            ck = (tuple(tuple(int(v) for v in f) for f in featmap_sizes), tuple(ks), str(dev))
-            cache = self.__dict__.setdefault('_prop_cache', {})
-            if ck not in cache:
-                if len(cache) > 32:
-                    cache.clear()
-                mlvl_anchors = self.anchor_generator.grid_anchors(featmap_sizes, device=dev)
-                col_off = torch.cat([torch.full((k, ), offs[l], dtype=torch.int64) for l, k in enumerate(ks)]).to(dev)
-                lvl_ids = torch.cat([torch.full((k, ), float(l)) for l, k in enumerate(ks)]).to(dev)
-                cache[ck] = (col_off, lvl_ids, torch.cat(mlvl_anchors))
-            col_off, lvl_ids, all_anchors = cache[ck]
-            gidx = top_idx + col_off[None]
-            scores_l, seg_sizes = [top_val], list(ks)
-            deltas_l = [torch.gather(bbox_preds.flat.detach(), 1, gidx[..., None].expand(B, gidx.size(1), 4))]
-            anchors_l = [all_anchors[gidx]]
-        koff = 0
-        if not flat_ok:
+        top = self._rank_levels(cls_scores, Ns, ks, offs) if fused else None
+        if fused and getattr(cls_scores, 'flat', None) is not None and getattr(bbox_preds, 'flat', None) is not None and \
+                not record:
+            scores, deltas, anchors, lvl_ids, flat_ids = self._candidates_flat(cls_scores, bbox_preds, ks, offs, top)
+        else:
+            scores, deltas, anchors, lvl_ids, flat_ids = self._candidates_per_level(cls_scores, bbox_preds, Ns, ks, top, record)
+        proposals = self._decode(anchors, deltas, scores.shape, img_metas)
+        if cfg.min_bbox_size > 0:
+            w = proposals[..., 2] - proposals[..., 0]
+            h = proposals[..., 3] - proposals[..., 1]
+            valid = (w >= cfg.min_bbox_size) & (h >= cfg.min_bbox_size)
+            if not bool(valid.all()):
+                return self._nms_per_image(proposals, scores, valid, ks, cfg, padded)
+        return self._nms_segmented(proposals, scores, lvl_ids, flat_ids, ks, cfg, fused, padded)
+
+    def _rank_levels(self, cls_scores, Ns, ks, offs):
+        """-> (top_idx, top_val), each (B, sum(ks)): every (image, level) ranking of the call in one segmented top-k
+        (htd_segmented_topk): the sorted first nms_pre of `scores.sort(descending=True)` (rpn_head.py:122-133), equal scores by
+        ascending anchor index.  top_idx counts inside its level."""
+        B, L, total = cls_scores[0].size(0), len(cls_scores), sum(Ns)
+        if getattr(cls_scores, 'flat', None) is not None:
+            sig = cls_scores.flat.detach().sigmoid()
+        else:
+            sig = torch.cat([c.detach().permute(0, 2, 3, 1).reshape(B, -1) for c in cls_scores], 1).sigmoid_()
+        top_idx, top_val = M.segmented_topk(sig, [(b * total + offs[l], Ns[l], ks[l]) for b in range(B) for l in range(L)])
+        return top_idx.view(B, sum(ks)), top_val.view(B, sum(ks))
+
+    def _candidates_flat(self, cls_scores, bbox_preds, ks, offs, top):
+        """The levels' candidates through ONE gather each: rank inside (image, level) + the level's first anchor = index into
+        the flat per-anchor tensors (RPNHead.forward made them) and the level-concatenated anchors (constants of the map
+        sizes: cached).  -> scores (B, K), deltas (B, K, 4), anchors (B, K, 4), level id of every column (K,), None."""
+        B, dev = cls_scores[0].size(0), cls_scores[0].device
+        featmap_sizes = [c.shape[-2:] for c in cls_scores]
+        top_idx, top_val = top
+
+        def make():
             mlvl_anchors = self.anchor_generator.grid_anchors(featmap_sizes, device=dev)
-        for lvl in range(L if not flat_ok else 0):
+            col_off = torch.cat([torch.full((k, ), offs[l], dtype=torch.int64) for l, k in enumerate(ks)]).to(dev)
+            lvl_ids = torch.cat([torch.full((k, ), float(l)) for l, k in enumerate(ks)]).to(dev)
+            return col_off, lvl_ids, torch.cat(mlvl_anchors)
+        key = (self._shape_key(featmap_sizes), tuple(ks), str(dev))
+        col_off, lvl_ids, all_anchors = self._cached('_prop_cache', 32, key, make)
+        gidx = top_idx + col_off[None]
+        deltas = torch.gather(bbox_preds.flat.detach(), 1, gidx[..., None].expand(B, gidx.size(1), 4))
+        return top_val, deltas, all_anchors[gidx], lvl_ids, None
+
+    def _candidates_per_level(self, cls_scores, bbox_preds, Ns, ks, top, record):
+        """Level by level, from the rankings of `top` or, without them (CPU, nms_pre beyond the top-k kernel), a stable sort.
+        -> scores, deltas, anchors as _candidates_flat, None (the NMS stage makes the level ids), and with `record` the flat
+        anchor index (over the levels) of every candidate, per level."""
+        B, dev = cls_scores[0].size(0), cls_scores[0].device
+        mlvl_anchors = self.anchor_generator.grid_anchors([c.shape[-2:] for c in cls_scores], device=dev)
+        scores_l, deltas_l, anchors_l, flat_ids = [], [], [], [] if record else None
+        koff = level_off = 0
+        for lvl, k in enumerate(ks):
             d = bbox_preds[lvl].detach().permute(0, 2, 3, 1).reshape(B, -1, 4)
-            k = ks[lvl]
-            if fused:
-                ranked, idx = top_val[:, koff:koff + k], top_idx[:, koff:koff + k]
+            if top is not None:
+                idx, ranked = top[0][:, koff:koff + k], top[1][:, koff:koff + k]
                 koff += k
             else:
                 s = cls_scores[lvl].detach().permute(0, 2, 3, 1).reshape(B, -1).sigmoid()
@@ -468,41 +375,44 @@ class RPNHead(nn.Module):
             scores_l.append(ranked)
             deltas_l.append(torch.gather(d, 1, idx[..., None].expand(B, k, 4)))
             anchors_l.append(mlvl_anchors[lvl][idx])
-            seg_sizes.append(k)
             if record:
                 flat_ids.append(idx + level_off)
                 level_off += Ns[lvl]
-        one = len(scores_l) == 1
-        scores = scores_l[0] if one else torch.cat(scores_l, 1)     # (B, K): level-major, descending inside a level
-        K = scores.size(1)
-        deltas = (deltas_l[0] if one else torch.cat(deltas_l, 1)).reshape(B * K, 4)
-        anchors = (anchors_l[0] if one else torch.cat(anchors_l, 1)).reshape(B * K, 4)
-        lim = const_tensor([[m['img_shape'][1], m['img_shape'][0]] for m in img_metas], dev, torch.float32) \
+        if len(ks) == 1:
+            return scores_l[0], deltas_l[0], anchors_l[0], None, flat_ids
+        # (B, K): level-major, descending inside a level
+        return torch.cat(scores_l, 1), torch.cat(deltas_l, 1), torch.cat(anchors_l, 1), None, flat_ids
+
+    def _decode(self, anchors, deltas, shape, img_metas):
+        """(B, K, 4) proposals of the candidates, clipped to their image when the coder says so."""
+        B, K = shape
+        lim = const_tensor([[m['img_shape'][1], m['img_shape'][0]] for m in img_metas], anchors.device, torch.float32) \
             if self.bbox_coder.clip_border else None                                      # (B, 2) w,h
-        proposals = delta2bbox_clip_device(anchors, deltas, self.bbox_coder.means, self.bbox_coder.stds, lim, None,
-                                           K).view(B, K, 4)
-        valid = None
-        if cfg.min_bbox_size > 0:
-            w = proposals[..., 2] - proposals[..., 0]
-            h = proposals[..., 3] - proposals[..., 1]
-            valid = (w >= cfg.min_bbox_size) & (h >= cfg.min_bbox_size)
-            if bool(valid.all()):
-                valid = None
-        if valid is not None:
-            # rare path (min_bbox_size is 0 in every HTD config): fall back to the per-image operator
-            from ..mmcv_ops import batched_nms
-            ids = torch.cat([scores.new_full((k, ), i, dtype=torch.long) for i, k in enumerate(seg_sizes)])
-            out = []
-            for b in range(B):
-                v = valid[b]
-                dets, _ = batched_nms(proposals[b][v], scores[b][v], ids[v], dict(type='nms', iou_threshold=cfg.nms_thr))
-                out.append(dets[:cfg.nms_post])
-            if padded:
-                n_keep = const_tensor([int(d.size(0)) for d in out], dev, torch.int64)
-                return torch.stack([torch.nn.functional.pad(d, (0, 0, 0, cfg.nms_post - d.size(0))) for d in out]), n_keep
-            return out
+        return delta2bbox_clip_device(anchors.reshape(B * K, 4), deltas.reshape(B * K, 4), self.bbox_coder.means,
+                                      self.bbox_coder.stds, lim, None, K).view(B, K, 4)
+
+    def _nms_per_image(self, proposals, scores, valid, seg_sizes, cfg, padded):
+        """Candidates below min_bbox_size exist (rare: it is 0 in every HTD config): the per-image operator on the rest."""
+        from ..mmcv_ops import batched_nms
+        ids = torch.cat([scores.new_full((k, ), i, dtype=torch.long) for i, k in enumerate(seg_sizes)])
+        out = []
+        for b in range(scores.size(0)):
+            v = valid[b]
+            dets, _ = batched_nms(proposals[b][v], scores[b][v], ids[v], dict(type='nms', iou_threshold=cfg.nms_thr))
+            out.append(dets[:cfg.nms_post])
+        if padded:
+            n_keep = const_tensor([int(d.size(0)) for d in out], scores.device, torch.int64)
+            return torch.stack([torch.nn.functional.pad(d, (0, 0, 0, cfg.nms_post - d.size(0))) for d in out]), n_keep
+        return out
+
+    def _nms_segmented(self, proposals, scores, ids, flat_ids, seg_sizes, cfg, fused, padded):
+        """One NMS launch over the (image, level) segments, the first nms_post survivors of every image in descending score
+        order, packed as get_bboxes returns them.  flat_ids given: the trail of the candidates is left on the head."""
+        B, K = scores.shape
+        dev = scores.device
         # level id as class: shift by id*(max+1) like batched_nms does (per image), one segment per (image, level)
-        ids = lvl_ids if flat_ok else torch.cat([scores.new_full((k, ), i) for i, k in enumerate(seg_sizes)])
+        if ids is None:
+            ids = torch.cat([scores.new_full((k, ), i) for i, k in enumerate(seg_sizes)])
         max_coord = proposals.reshape(B, -1).max(dim=1)[0]
         shifted = proposals + (ids.view(1, K) * (max_coord.view(B, 1) + 1)).unsqueeze(-1)
         offs = [0]
@@ -521,7 +431,7 @@ class RPNHead(nn.Module):
         else:
             top, order = masked.sort(dim=1, descending=True, stable=True)
             order = order[:, :cfg.nms_post]
-        if record:
+        if flat_ids is not None:
             # rows of the level-concatenated candidate list in kept order (= `keep` of rpn_head.py:166-168) and the
             # anchor each of them is (flat index over the levels); entries past n_keep[b] are meaningless
             self._last_proposal_trail = (order, torch.gather(torch.cat(flat_ids, 1), 1, order), n_keep)

@@ -4,11 +4,9 @@ Reference: detectors/single_stage.py:9-149 (extract_feat :52-57, forward_train :
 detectors/retinanet.py:5-17.  The dense head does the work (detector/anchor_heads.py); results of a batch leave the device in
 one copy (core.bbox.bbox2result_many).
 """
-import torch
-
 from ..core.bbox import bbox2result_many
 from ..registry import DETECTORS, build_backbone, build_head, build_neck
-from .two_stage import BaseDetector, TwoStageDetector
+from .two_stage import BaseDetector
 
 
 @DETECTORS.register_module()
@@ -33,32 +31,13 @@ class SingleStageDetector(BaseDetector):
             self.neck.init_weights()
         self.bbox_head.init_weights()
 
-    def extract_feat(self, img):
-        x = self.backbone(img)
-        return self.neck(x) if self.with_neck else x
-
     def forward_dummy(self, img):
         return self.bbox_head(self.extract_feat(img))
 
-    def _plain_weights(self):
-        """Trainable fp32 convolution weights of neck and head: the operands of this step's data gradients (dense.flip_many)."""
-        ws = getattr(self, '_plain_weight_list', None)
-        if ws is None:
-            ws = [m.weight for part in (getattr(self, 'neck', None), self.bbox_head) if part is not None for m in part.modules()
-                  if isinstance(m, torch.nn.Conv2d) and m.groups == 1 and m.weight.requires_grad]
-            self._plain_weight_list = ws
-        return ws
-
     def forward_train(self, img, img_metas, gt_bboxes, gt_labels, gt_bboxes_ignore=None):
-        if img.is_cuda:
-            from .. import dense
-            dense.new_step()
-            if torch.is_grad_enabled():
-                dense.flip_many(self._plain_weights())
+        self._begin_train_step(img)
         x = self.extract_feat(img)
         return self.bbox_head.forward_train(x, img_metas, gt_bboxes, gt_labels, gt_bboxes_ignore)
-
-    _drop_step_caches = staticmethod(TwoStageDetector._drop_step_caches)
 
     def simple_test(self, img, img_metas, rescale=False):
         self._drop_step_caches(img)

@@ -32,6 +32,45 @@ class BaseDetector(nn.Module):
     def with_rpn(self):
         return getattr(self, 'rpn_head', None) is not None
 
+    def extract_feat(self, img):
+        x = self.backbone(img)
+        return self.neck(x) if self.with_neck else x
+
+    def _plain_weights(self):
+        """Trainable fp32 weights of the convolutions / Linear layers outside the backbone (whose stages fold and flip their
+        own): the operands of this step's data gradients."""
+        ws = getattr(self, '_plain_weight_list', None)
+        if ws is None:
+            ws = []
+            # a two-stage detector has the first three of these, a single-stage one neck and bbox_head
+            for name in ('neck', 'rpn_head', 'roi_head', 'bbox_head'):
+                part = getattr(self, name, None)
+                if part is None:
+                    continue
+                for m in part.modules():
+                    if isinstance(m, (nn.Conv2d, nn.Linear)) and getattr(m, 'groups', 1) == 1 and m.weight.requires_grad:
+                        ws.append(m.weight)
+            self._plain_weight_list = ws
+        return ws
+
+    def _begin_train_step(self, img):
+        """What every forward_train starts with: dense's per-step caches emptied, this step's flipped weights made."""
+        if img.is_cuda:
+            from .. import dense
+            dense.new_step()
+            if torch.is_grad_enabled():
+                # the dgrad images of every plain convolution / Linear of neck and heads in one launch (dense.flip_many)
+                dense.flip_many(self._plain_weights())
+
+    @staticmethod
+    def _drop_step_caches(img):
+        """A test pass with autograd ENABLED folds BN into fresh weight tensors on every call (the training branch of
+        frozen_bn_fold_many); their plane / flipped images are keyed by those tensors and would pile up in dense's per-step
+        caches, one backbone of weights per call.  Under no_grad the folded weights are cached and so are their images."""
+        if img.is_cuda and torch.is_grad_enabled():
+            from .. import dense
+            dense.new_step()
+
     def forward_test(self, imgs, img_metas, **kwargs):
         for var, name in [(imgs, 'imgs'), (img_metas, 'img_metas')]:
             if not isinstance(var, list):
@@ -169,10 +208,6 @@ class TwoStageDetector(BaseDetector):
         if getattr(self, 'roi_head', None) is not None:
             self.roi_head.init_weights(pretrained)
 
-    def extract_feat(self, img):
-        x = self.backbone(img)
-        return self.neck(x) if self.with_neck else x
-
     def extract_feats(self, imgs):
         """detectors/base.py:51-63: one feature pyramid per test-time augmentation."""
         assert isinstance(imgs, list)
@@ -187,12 +222,7 @@ class TwoStageDetector(BaseDetector):
 
     def forward_train(self, img, img_metas, gt_bboxes, gt_labels, gt_bboxes_ignore=None, gt_masks=None,
                       proposals=None, **kwargs):
-        if img.is_cuda:
-            from .. import dense
-            dense.new_step()
-            if torch.is_grad_enabled():
-                # the dgrad images of every plain convolution / Linear of neck and heads in one launch (dense.flip_many)
-                dense.flip_many(self._plain_weights())
+        self._begin_train_step(img)
         x = self.extract_feat(img)
         losses = dict()
         x32 = x if x[0].dtype == torch.float32 else tuple(f.float() for f in x)     # RoI head: fp32 (force_fp32 sites)
@@ -216,30 +246,6 @@ class TwoStageDetector(BaseDetector):
         losses.update(self.roi_head.forward_train(x32, img_metas, proposal_list, gt_bboxes, gt_labels,
                                                   gt_bboxes_ignore, gt_masks, **kwargs))
         return losses
-
-    def _plain_weights(self):
-        """Trainable fp32 weights of the convolutions / Linear layers outside the backbone (whose stages fold and flip their
-        own): the operands of this step's data gradients."""
-        ws = getattr(self, '_plain_weight_list', None)
-        if ws is None:
-            ws = []
-            for part in (getattr(self, 'neck', None), getattr(self, 'rpn_head', None), getattr(self, 'roi_head', None)):
-                if part is None:
-                    continue
-                for m in part.modules():
-                    if isinstance(m, (nn.Conv2d, nn.Linear)) and getattr(m, 'groups', 1) == 1 and m.weight.requires_grad:
-                        ws.append(m.weight)
-            self._plain_weight_list = ws
-        return ws
-
-    @staticmethod
-    def _drop_step_caches(img):
-        """A test pass with autograd ENABLED folds BN into fresh weight tensors on every call (the training branch of
-        frozen_bn_fold_many); their plane / flipped images are keyed by those tensors and would pile up in dense's per-step
-        caches, one backbone of weights per call.  Under no_grad the folded weights are cached and so are their images."""
-        if img.is_cuda and torch.is_grad_enabled():
-            from .. import dense
-            dense.new_step()
 
     def simple_test(self, img, img_metas, proposals=None, rescale=False):
         assert self.with_bbox, 'Bbox head must be implemented.'
