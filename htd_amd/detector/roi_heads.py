@@ -2,9 +2,10 @@
 
 Reference: roi_heads/standard_roi_head.py:9-311 with test_mixins.py:52-96, roi_heads/cascade_roi_head.py:12-507
 (+ base_roi_head.py:8-106).  Same registry names, kwargs, sub-module names (bbox_roi_extractor / bbox_head, indexed per stage in
-the cascade), loss keys (loss_cls, acc, loss_bbox; s{i}.* in the cascade) and return structures.  Like HTDRoIHead they train on
-fixed-size tensors without a host/device synchronisation when the configuration allows it (forward_train_static), fall back
-to the per-image lists otherwise, and post-process a whole test batch in one pass.
+the cascade), loss keys (loss_cls, acc, loss_bbox; s{i}.* in the cascade) and return structures.  They train on fixed-size
+tensors without a host/device synchronisation when the configuration allows it (forward_train_static), fall back to the
+per-image lists otherwise, and post-process a whole test batch in one pass.  HTDRoIHead (htd_roi_head.py) is a CascadeRoIHead:
+the module functions, _BBoxRoIHead and the cascade's constructor, gates and stage loops here are its own too.
 
 Outside this path, each raising an error that names the key: mask branches, shared_head, aug_test.
 """
@@ -48,6 +49,46 @@ def static_targets(head, S):
     return labels, lw, bt, bw
 
 
+def batched_targets(head, sampling_results, cfg):
+    """BBoxHead.get_targets (bbox_head.py:85-139) for the whole batch in a handful of launches: rows are [pos_i ; neg_i] per
+    image, positives carry their gt label and encoded deltas (their gt box for a head with reg_decoded_bbox), everything has
+    weight 1 (pos_weight <= 0), negatives the background label."""
+    if cfg.pos_weight > 0:
+        return head.get_targets(sampling_results, None, None, cfg)
+    npos = [r.pos_bboxes.size(0) for r in sampling_results]
+    nneg = [r.neg_bboxes.size(0) for r in sampling_results]
+    N = sum(npos) + sum(nneg)
+    dev = sampling_results[0].pos_bboxes.device
+    pos_rows, start = [], 0
+    for a, b in zip(npos, nneg):
+        pos_rows.append(torch.arange(start, start + a, device=dev))
+        start += a + b
+    pos_rows = torch.cat(pos_rows)
+    pos_b = torch.cat([r.pos_bboxes for r in sampling_results])
+    labels = pos_b.new_full((N, ), head.num_classes, dtype=torch.long)
+    bbox_targets = pos_b.new_zeros(N, 4)
+    bbox_weights = pos_b.new_zeros(N, 4)
+    if pos_rows.numel():
+        labels[pos_rows] = torch.cat([r.pos_gt_labels for r in sampling_results])
+        pos_gt = torch.cat([r.pos_gt_bboxes for r in sampling_results])
+        # a head in decoded mode regresses against the gt box itself (bbox_head.py:118-124)
+        bbox_targets[pos_rows] = pos_gt if head.reg_decoded_bbox else head.bbox_coder.encode(pos_b, pos_gt)
+        bbox_weights.index_fill_(0, pos_rows, 1.0)
+    return labels, pos_b.new_ones(N), bbox_targets, bbox_weights
+
+
+def static_refine(head, S, bbox_pred, lim):
+    """BBoxHead.refine_bboxes (bbox_head.py:227-304) on the fixed slots of a StaticSamples, for a class-agnostic regressor:
+    decode, clip to lim (B,2) [w,h], drop the gt-born rows.  -> boxes (B,n,4), keep (B,n): the next stage's candidates."""
+    from ..core.bbox import delta2bbox_clip_device
+    B, n = S.valid.shape
+    with torch.no_grad():
+        keep = S.valid & ~S.pos_is_gt
+        boxes = delta2bbox_clip_device(S.boxes.view(-1, 4), bbox_pred, head.bbox_coder.means, head.bbox_coder.stds, lim,
+                                       keep.view(-1), n).view(B, n, 4)
+    return boxes, keep
+
+
 def _static_stage_ok(head, assigner, sampler, cfg):
     """One stage of the sync-free training path: batched assignment and sampling, unit sample weights, and a decoded-box head
     only with a loss the fused kernel takes."""
@@ -78,7 +119,7 @@ def _refine_rows(head, rois, bbox_pred, sampling_results, img_metas):
 
 
 class _BBoxRoIHead(nn.Module):
-    """What the two heads share: the unsupported keys, the sampling switches and the whole-batch test post-processing."""
+    """What every RoI head shares: the unsupported keys, the sampling switches and the whole-batch test post-processing."""
     batched_test = True      # post-process the whole batch in one pass (False: the per-image loop of the reference)
 
     def _reject_unsupported(self, mask_roi_extractor, mask_head, shared_head):
@@ -188,7 +229,7 @@ class StandardRoIHead(_BBoxRoIHead):
                                              gt_bboxes_ignore)
         rois = bbox2roi([res.bboxes for res in sampling_results])
         res = self._bbox_forward(x, rois)
-        targets = self.bbox_head.get_targets(sampling_results, gt_bboxes, gt_labels, self.train_cfg)
+        targets = batched_targets(self.bbox_head, sampling_results, self.train_cfg)
         return dict(self.bbox_head.loss(res['cls_score'], res['bbox_pred'], rois, *targets))
 
     # ------------------------------------------------------------------ train, static shapes
@@ -275,6 +316,10 @@ class CascadeRoIHead(_BBoxRoIHead):
         cls_score, bbox_pred = self.bbox_head[stage](bbox_feats)
         return dict(cls_score=cls_score, bbox_pred=bbox_pred, bbox_feats=bbox_feats)
 
+    def _bbox_forward_train(self, stage, x, rois, sampling_results, **kw):
+        """A stage's forward in the per-image training loop; a head that treats the sampled positives apart overrides it."""
+        return self._bbox_forward(stage, x, rois, **kw)
+
     def _taps(self, x):
         same = len({e.num_inputs for e in self.bbox_roi_extractor}) == 1
         return M.PyramidTaps(x[:self.bbox_roi_extractor[0].num_inputs]) if same and x[0].is_cuda else x
@@ -285,7 +330,8 @@ class CascadeRoIHead(_BBoxRoIHead):
             losses[f's{stage}.{name}'] = value * lw if 'loss' in name else value
 
     # ------------------------------------------------------------------ train
-    def forward_train(self, x, img_metas, proposal_list, gt_bboxes, gt_labels, gt_bboxes_ignore=None, gt_masks=None):
+    def forward_train(self, x, img_metas, proposal_list, gt_bboxes, gt_labels, gt_bboxes_ignore=None, gt_masks=None, **kw):
+        """kw: handed on to every stage's _bbox_forward."""
         if gt_masks is not None:
             raise NotImplementedError('gt_masks: CascadeRoIHead has no mask branch')
         losses = dict()
@@ -298,8 +344,8 @@ class CascadeRoIHead(_BBoxRoIHead):
             sampling_results = assign_and_sample(self.bbox_assigner[i], self.bbox_sampler[i], proposal_list, gt_bboxes,
                                                  gt_labels, gt_bboxes_ignore)
             rois = bbox2roi([res.bboxes for res in sampling_results])
-            res = self._bbox_forward(i, feats, rois)
-            targets = head.get_targets(sampling_results, gt_bboxes, gt_labels, self.train_cfg[i])
+            res = self._bbox_forward_train(i, feats, rois, sampling_results, **kw)
+            targets = batched_targets(head, sampling_results, self.train_cfg[i])
             self._add_stage_losses(losses, i, head.loss(res['cls_score'], res['bbox_pred'], rois, *targets))
             if i < self.num_stages - 1:
                 with torch.no_grad():
@@ -325,12 +371,11 @@ class CascadeRoIHead(_BBoxRoIHead):
     def forward_train_static(self, x, img_metas, proposals, n_keep, gt_bboxes, gt_labels):
         """forward_train on fixed-size tensors: proposals (B,P,5) zero-padded past n_keep (B,) [device].  Numerically the
         per-image path with the same samples; nothing is read back to the host."""
-        from ..core.bbox import delta2bbox_clip_device, static_assign_and_sample
+        from ..core.bbox import static_assign_and_sample
         losses = dict()
-        B, P = proposals.shape[:2]
         dev = proposals.device
         boxes = proposals[..., :4]
-        keep = arange_cached(P, dev)[None, :] < n_keep[:, None]
+        keep = arange_cached(proposals.size(1), dev)[None, :] < n_keep[:, None]
         lim = const_tensor([[m['img_shape'][1], m['img_shape'][0]] for m in img_metas], dev, torch.float32)
         feats = self._taps(x)
         trail = []
@@ -344,18 +389,14 @@ class CascadeRoIHead(_BBoxRoIHead):
             self._add_stage_losses(losses, i, head.loss(res['cls_score'], res['bbox_pred'], rois, *static_targets(head, S),
                                                         num_samples=S.valid.sum()))
             if i < self.num_stages - 1:
-                with torch.no_grad():        # refine_bboxes (bbox_head.py:227-304): decode, clip, drop the gt-born rows
-                    n = S.valid.size(1)
-                    keep = S.valid & ~S.pos_is_gt
-                    boxes = delta2bbox_clip_device(S.boxes.view(-1, 4), res['bbox_pred'], head.bbox_coder.means,
-                                                   head.bbox_coder.stds, lim, keep.view(-1), n).view(B, n, 4)
+                boxes, keep = static_refine(head, S, res['bbox_pred'], lim)
         self._last_static = tuple(trail)      # exposed for tests
         return losses
 
     # ------------------------------------------------------------------ test
-    def simple_test_bboxes(self, x, proposal_list, img_metas, rescale=False):
+    def simple_test_bboxes(self, x, proposal_list, img_metas, rescale=False, **kw):
         """cascade_roi_head.py:290-350 -> (det_bboxes list, det_labels list) on the device: the logits averaged over the stages,
-        the last stage's deltas decoded on the boxes the stages before it refined."""
+        the last stage's deltas decoded on the boxes the stages before it refined.  kw: handed on to every _bbox_forward."""
         rois = bbox2roi(proposal_list)
         n_per = tuple(len(p) for p in proposal_list)
         batched = self._batched_test_ok(self.bbox_head, rois, img_metas, rescale)
@@ -364,7 +405,7 @@ class CascadeRoIHead(_BBoxRoIHead):
             img_of, hw = self._row_limits(rois, img_metas)
         ms_scores = []
         for i in range(self.num_stages):
-            res = self._bbox_forward(i, x, rois)
+            res = self._bbox_forward(i, x, rois, **kw)
             ms_scores.append(res['cls_score'])
             if i < self.num_stages - 1:
                 label = res['cls_score'][:, :-1].argmax(dim=1)
@@ -373,7 +414,7 @@ class CascadeRoIHead(_BBoxRoIHead):
                 else:
                     rois = torch.cat([self.bbox_head[i].regress_by_class(r, l, p, m) for r, l, p, m in
                                       zip(rois.split(n_per), label.split(n_per), res['bbox_pred'].split(n_per), img_metas)])
-        cls_score = sum(ms_scores) / float(len(ms_scores))
+        cls_score = sum(ms_scores[1:], ms_scores[0]) / float(len(ms_scores))
         head = self.bbox_head[-1]
         if batched:
             return self._get_bboxes_images(head, rois, cls_score, res['bbox_pred'], img_of, hw, img_metas, rescale)

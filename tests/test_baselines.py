@@ -84,6 +84,32 @@ def test_builder_and_unsupported_keys():
             build_baseline_detector(kind).roi_head.aug_test([], [], [])
 
 
+def test_htd_roi_head_is_a_cascade_head_with_the_same_parameter_layout():
+    """HTDRoIHead builds on CascadeRoIHead; its sub-modules register in the order that lays out the Trainer's flat buffer and the
+    optimizer state of existing checkpoints (extractors, heads, then the global-context head), and the keys the HTD configs do
+    not support raise like the baselines' do."""
+    from htd_amd.configs import build_htd_detector, htd_config
+    from htd_amd.detector.roi_heads import CascadeRoIHead
+    det = build_htd_detector(cfg=htd_config(50))
+    rh = det.roi_head
+    assert isinstance(rh, CascadeRoIHead) and rh.with_bbox and not rh.with_mask and not rh.with_shared_head
+    assert [n for n, _ in rh.named_children()] == ['bbox_roi_extractor', 'bbox_head', 'glbctx_head']
+    keys = [k for k in det.state_dict() if k.startswith('roi_head.')]
+    assert list(det.state_dict())[-len(keys):] == keys and len(keys) == 52
+    assert keys[:2] == ['roi_head.bbox_roi_extractor.1.conv1.weight', 'roi_head.bbox_roi_extractor.1.conv1.bias']
+    assert list(dict.fromkeys(k.split('.')[1] for k in keys)) == ['bbox_roi_extractor', 'bbox_head', 'glbctx_head']
+    assert keys[-1] == 'roi_head.glbctx_head.fc.bias'
+    assert keys[-4:-1] == ['roi_head.glbctx_head.convs.3.conv.weight', 'roi_head.glbctx_head.convs.3.conv.bias',
+                           'roi_head.glbctx_head.fc.weight']
+    assert rh.can_train_static() is True
+    for key, value in (('mask_head', dict(type='FCNMaskHead')), ('mask_roi_extractor', dict(type='SingleRoIExtractor')),
+                       ('shared_head', dict(type='ResLayer'))):
+        cfg = htd_config(50)
+        cfg.model.roi_head[key] = value
+        with pytest.raises(NotImplementedError, match=key):
+            build_htd_detector(cfg=cfg)
+
+
 def test_l1_loss_matches_the_reference_fp64(golden):
     from htd_amd.detector.losses import L1Loss
     g = golden('baselines')

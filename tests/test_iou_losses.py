@@ -207,9 +207,10 @@ def test_detector_with_giou_heads_builds_and_trains_static():
 
 
 def test_batched_targets_of_a_decoded_head_are_the_gt_boxes():
-    """HTDRoIHead._targets for a head with reg_decoded_bbox: positives carry their gt box, everything else zeros with weight 0 --
+    """roi_heads.batched_targets for a head with reg_decoded_bbox: positives carry their gt box, everything else zeros with weight 0 --
     what BBoxHead.get_targets gives image by image."""
     from htd_amd.configs import build_htd_detector
+    from htd_amd.detector.roi_heads import batched_targets
     rh = build_htd_detector(cfg=_giou_cfg('GIoULoss', None)).roi_head
     gen = torch.Generator().manual_seed(0)
 
@@ -219,12 +220,12 @@ def test_batched_targets_of_a_decoded_head_are_the_gt_boxes():
     res = [types.SimpleNamespace(pos_bboxes=boxes(a), neg_bboxes=boxes(b), pos_gt_bboxes=boxes(a),
                                  pos_gt_labels=torch.randint(0, 80, (a, ), generator=gen)) for a, b in ((3, 5), (0, 4), (2, 0))]
     for stage in (0, 1):
-        got = rh._targets(stage, res, rh.train_cfg[stage])
+        got = batched_targets(rh.bbox_head[stage], res, rh.train_cfg[stage])
         want = rh.bbox_head[stage].get_targets(res, None, None, rh.train_cfg[stage])
         for a, b in zip(got, want):
             assert a.dtype == b.dtype and torch.equal(a, b)
     assert torch.equal(got[2][:3], rh.bbox_head[1].bbox_coder.encode(res[0].pos_bboxes, res[0].pos_gt_bboxes))
-    assert torch.equal(rh._targets(0, res, rh.train_cfg[0])[2][:3], res[0].pos_gt_bboxes)
+    assert torch.equal(batched_targets(rh.bbox_head[0], res, rh.train_cfg[0])[2][:3], res[0].pos_gt_bboxes)
 
 
 def test_cfg_options_reach_the_bbox_heads():

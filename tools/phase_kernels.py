@@ -27,7 +27,7 @@ def wrap(owner, name, tag=None):
     setattr(owner, name, inner)
 
 
-wrap(rh_mod.HTDRoIHead, '_static_targets')
+wrap(rh_mod, 'static_targets')          # the name forward_train_static calls
 import htd_amd.core.bbox
 wrap(htd_amd.core.bbox, 'static_assign_and_sample')
 wrap(htd_amd.core.bbox, 'batched_max_iou_assign')

@@ -6,6 +6,7 @@ import torch
 from htd_amd.configs import build_htd_detector
 from htd_amd.runner import synthetic_batch
 from htd_amd.core import bbox2roi
+from htd_amd.detector.roi_heads import assign_and_sample
 
 dev = torch.device('cuda:0')
 torch.manual_seed(0)
@@ -28,7 +29,7 @@ for it in range(N + 2):
     x = tuple(t.detach().requires_grad_() for t in x)
     gtb, gtl, metas = data['gt_bboxes'], data['gt_labels'], data['img_metas']
     torch.cuda.synchronize(); t = time.perf_counter()
-    sr = h._assign_and_sample(0, props, gtb, gtl, [None] * 4); t = lap('s0 assign+sample', t)
+    sr = assign_and_sample(h.bbox_assigner[0], h.bbox_sampler[0], props, gtb, gtl, [None] * 4); t = lap('s0 assign+sample', t)
     mc, g = h.glbctx_head(x); lg = h.glbctx_head.loss(mc, gtl); t = lap('sfa', t)
     rois = bbox2roi([r.bboxes for r in sr]); t = lap('s0 bbox2roi', t)
     res = h._bbox_forward(0, x, rois, g); t = lap('s0 extract+head', t)
@@ -38,9 +39,9 @@ for it in range(N + 2):
         rl = torch.where(tg[0] == 80, res['cls_score'][:, :-1].argmax(1), tg[0])
         pl = h.bbox_head[0].refine_bboxes(rois, rl, res['bbox_pred'], [r.pos_is_gt for r in sr], metas)
     t = lap('refine', t)
-    sr1 = h._assign_and_sample(1, pl, gtb, gtl, [None] * 4); t = lap('s1 assign+sample', t)
+    sr1 = assign_and_sample(h.bbox_assigner[1], h.bbox_sampler[1], pl, gtb, gtl, [None] * 4); t = lap('s1 assign+sample', t)
     rois1 = bbox2roi([r.bboxes for r in sr1]); t = lap('s1 bbox2roi', t)
-    res1 = h._bbox_forward(1, x, rois1, g, sr1); t = lap('s1 extract+BA+pgraph+head', t)
+    res1 = h._bbox_forward_train(1, x, rois1, sr1, g); t = lap('s1 extract+BA+pgraph+head', t)
     tg1 = h.bbox_head[1].get_targets(sr1, gtb, gtl, h.train_cfg[1]); t = lap('s1 targets', t)
     l1 = h.bbox_head[1].loss(res1['cls_score'], res1['bbox_pred'], rois1, *tg1); t = lap('s1 loss', t)
 for k, v in acc.items():
