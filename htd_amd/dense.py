@@ -16,6 +16,7 @@ from torch.autograd.function import once_differentiable
 from torch.multiprocessing.reductions import StorageWeakRef as _StorageWeakRef
 
 from . import capi
+from .mmcv_ops import chain_outputs
 
 CL = torch.channels_last
 _P = capi.ptr
@@ -909,12 +910,21 @@ def _wgrad_raw(x, g, weight, stride, padding, dilation, bias=None, overlap=True)
     return gw, gb
 
 
+def _dgrad_joined(galias, g, weight, x_shape, stride, padding, dilation):
+    """Data gradient of a chained convolution plus the gradient handed to its alias (None: nothing handed): the handed map
+    rides the data-gradient epilogue as `accum` where it can (same dtype and shape, and stride 1: the strided kernels have no
+    such operand), else it is added afterwards."""
+    fuse = galias is not None and stride == 1 and galias.dtype == g.dtype and tuple(galias.shape) == tuple(x_shape)
+    gx = _dgrad_raw(g, weight, x_shape, stride, padding, dilation, accum=galias.contiguous(memory_format=CL) if fuse else None)
+    return gx if (galias is None or fuse) else gx + galias
+
+
 class Conv2dFunction(Function):
     @staticmethod
     def forward(ctx, x, weight, bias, residual, stride, padding, dilation, relu, res_up=False, chain=False):
         """chain=True: also returns an identity alias of x.  A later consumer of x that reads the alias instead hands its
         gradient to THIS node's backward, where it joins in the data-gradient epilogue (`accum`) -- one gradient map
-        reaches x's producer and autograd has nothing to add (mmcv_ops.PyramidTaps does the same for the RoIAligns)."""
+        reaches x's producer and autograd has nothing to add (the gradient hand-off of DESIGN.md)."""
         _need_gpu(x, 'conv2d')
         src = x
         x = x.contiguous(memory_format=CL)
@@ -926,11 +936,7 @@ class Conv2dFunction(Function):
         ctx.cfg = (stride, padding, dilation, bool(relu), bias is not None, residual is not None)
         ctx.res_up = tuple(res.shape) if (res_up and res is not None) else None
         ctx.bias_ref = b                                  # only its address is used (gradient sink lookup)
-        ctx.chain = bool(chain)
-        if chain:
-            ctx.set_materialize_grads(False)              # an unused alias arrives as None, not as a map of zeros
-            return y, src.view_as(src)
-        return y
+        return chain_outputs(ctx, y, (src, ), chain)
 
     @staticmethod
     @once_differentiable
@@ -951,13 +957,7 @@ class Conv2dFunction(Function):
                 g = _mask_raw(g, y)
         elif want_b and not need_w:
             gb = _colsum_raw(g, None, ctx.bias_ref)[1]
-        gx = None
-        if need_x:
-            fuse = galias is not None and stride == 1 and galias.dtype == g.dtype and tuple(galias.shape) == tuple(x.shape)
-            gx = _dgrad_raw(g, weight, x.shape, stride, padding, dilation,
-                            accum=galias.contiguous(memory_format=CL) if fuse else None)
-            if galias is not None and not fuse:
-                gx = gx + galias
+        gx = _dgrad_joined(galias, g, weight, x.shape, stride, padding, dilation) if need_x else None
         # a same-size residual gets `g` ITSELF as its gradient (below): autograd may then accumulate into that tensor in
         # place on the main stream, so this layer's weight gradient must not still be reading it on the side stream
         aliases_g = has_res and need_r and ctx.res_up is None
@@ -992,17 +992,14 @@ class ConvReluHeadFunction(Function):
         h = _fwd_raw(x, w1, b1, None, 1, padding, 1, True)
         y = _fwd_raw(h, w2, b2, None, 1, 0, 1, False)
         ctx.save_for_backward(x, w1, w2, h)
-        ctx.cfg = (int(padding), b1, b2, bool(chain))          # the biases: only their addresses are used (sink lookup)
-        if chain:
-            ctx.set_materialize_grads(False)
-            return y, src.view_as(src)
-        return y
+        ctx.cfg = (int(padding), b1, b2)                       # the biases: only their addresses are used (sink lookup)
+        return chain_outputs(ctx, y, (src, ), chain)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, gy, galias=None):
         x, w1, w2, h = ctx.saved_tensors
-        padding, b1, b2, chain = ctx.cfg
+        padding, b1, b2 = ctx.cfg
         if gy is None:
             return (galias, ) + (None, ) * 6
         need_x, need_w1, need_b1, need_w2, need_b2 = ctx.needs_input_grad[:5]
@@ -1017,14 +1014,7 @@ class ConvReluHeadFunction(Function):
             gw1, gb1 = _wgrad_raw(x, gh, w1, 1, padding, 1, b1 if (need_b1 and b1 is not None) else None)
         elif need_b1 and b1 is not None:
             gb1 = _colsum_raw(gh, None, b1)[1]
-        gx = None
-        if need_x:
-            fuse = galias is not None and galias.dtype == gh.dtype and tuple(galias.shape) == tuple(x.shape)
-            gx = _dgrad_raw(gh, w1, x.shape, 1, padding, 1, accum=galias.contiguous(memory_format=CL) if fuse else None)
-            if galias is not None and not fuse:
-                gx = gx + galias
-        elif galias is not None:
-            gx = galias
+        gx = _dgrad_joined(galias, gh, w1, x.shape, 1, padding, 1) if need_x else galias
         return gx, gw1, gb1, gw2, gb2, None, None
 
 
@@ -1127,15 +1117,13 @@ class ResStageFunction(Function):
         the bias gradients come out of the wgrad launches: no separate pass over any gradient map;
       * the identity / downsample branch joins through `accum` in the conv1 dgrad epilogue (no separate add);
       * blocks after the first hand their predecessor a gradient already masked by the predecessor's output ReLU.
-    args: x, strides (tuple), dilation, has_ds (tuple of bool), chain, then per block w1,b1,w2,b2,w3,b3[,wd,bd].
-    chain=True: also returns an identity alias of x (see Conv2dFunction): a later consumer of x -- the FPN lateral of this
-    pyramid level -- reads the alias, and its gradient joins in the first block's data-gradient epilogues (`accum`) instead
-    of a full-map add by autograd (C3: 138 MB, C4: 69 MB per step)."""
+    args: x, strides (tuple), dilation, has_ds (tuple of bool), then per block w1,b1,w2,b2,w3,b3[,wd,bd].
+    The stage's input is also read by the FPN lateral of its pyramid level: autograd adds those two gradient maps (a stage
+    that starts with a strided block, as stages 2-4 of every ResNet do, could not take the lateral's map into its epilogues)."""
 
     @staticmethod
-    def forward(ctx, x, strides, dilation, has_ds, chain, *params):
+    def forward(ctx, x, strides, dilation, has_ds, *params):
         _need_gpu(x, 'res_stage')
-        src = x
         x = x.contiguous(memory_format=CL)
         params = [t.contiguous(memory_format=CL) if t.dim() == 4 else t.contiguous() for t in params]
         saved, k = [], 0
@@ -1158,17 +1146,12 @@ class ResStageFunction(Function):
         ctx.save_for_backward(*saved, *params)
         ctx.cfg = (strides, dilation, has_ds)
         ctx.flipped = [take_flipped(t) if t.dim() == 4 else None for t in params]      # same indexing as params
-        if chain:
-            ctx.set_materialize_grads(False)              # an unused alias arrives as None, not as a map of zeros
-            return x, src.view_as(src)
         return x
 
     @staticmethod
     @once_differentiable
-    def backward(ctx, g, galias=None):
+    def backward(ctx, g):
         strides, dilation, has_ds = ctx.cfg
-        if g is None:                                     # (chain) the stage's own output was not used
-            return (galias, None, None, None, None) + (None, ) * (len(ctx.saved_tensors) - 4 * len(strides))
         nb = len(strides)
         saved, params = ctx.saved_tensors[:4 * nb], ctx.saved_tensors[4 * nb:]
         flipped = ctx.flipped
@@ -1179,14 +1162,12 @@ class ResStageFunction(Function):
         need = ctx.needs_input_grad
         grads = [None] * len(params)
         g = g.contiguous(memory_format=CL)
-        if galias is not None:
-            galias = galias.contiguous(memory_format=CL)
         premasked = False
         for i in range(nb - 1, -1, -1):
             x, h1, h2, out = saved[4 * i:4 * i + 4]
             k, stride, ds = offs[i], strides[i], has_ds[i]
             w1, b1, w2, b2, w3, b3 = params[k:k + 6]
-            pneed = need[5 + k:5 + k + (8 if ds else 6)]
+            pneed = need[4 + k:4 + k + (8 if ds else 6)]
             first = i == 0
             need_x = need[0] if first else True
             # bias gradients are by-products of the wgrad launches (column sums of the staged gy tiles); a conv whose
@@ -1218,20 +1199,14 @@ class ResStageFunction(Function):
                 if pneed[6]:
                     grads[k + 6] = _wgrad_raw(x, gm3, wd, stride, 0, 1)[0]
                 grads[k + 7] = gb3 if pneed[7] else None
-                # (first block: the chained consumer's gradient of x rides this epilogue, then conv1's below)
-                acc = _dgrad_raw(gm3, wd, x.shape, stride, 0, 1, wT=flipped[k + 6],
-                                 accum=galias if first else None) if need_x else None
-            elif first and galias is not None and need_x:
-                acc = gm3 + galias                        # (no downsample branch in the first block: not a ResNet stage)
+                acc = _dgrad_raw(gm3, wd, x.shape, stride, 0, 1, wT=flipped[k + 6]) if need_x else None
             if need_x:
                 g = _dgrad_raw(gm1, w1, x.shape, 1, 0, 1, mask_src=None if first else x, accum=acc, wT=flipped[k],
                                g_planes=gm1p)
                 premasked = not first
             else:
                 g = None
-        if g is None and galias is not None and need[0]:
-            g = galias
-        return (g, None, None, None, None, *grads)
+        return (g, None, None, None, *grads)
 
 
 def conv2d_bf16(x, weight, bias=None, stride=1, padding=0, dilation=1, relu=False, residual=None, res_up=False):

@@ -121,10 +121,7 @@ class AdptRoIExtractor(BaseRoIExtractor):
             lvl_feats = M.roi_align_all_levels(feats, rois, l0.output_size, [l.spatial_scale for l in self.roi_layers[:L]],
                                                l0.sampling_ratio, l0.aligned)
         elif isinstance(feats, M.PyramidTaps):        # chained gradient maps (see mmcv_ops.PyramidTaps)
-            lvl_feats = []
-            for i in range(L):
-                f, feats.levels[i] = self.roi_layers[i](feats.levels[i], rois, chain=True)
-                lvl_feats.append(f)
+            lvl_feats = [feats.tap(lambda f, i=i: self.roi_layers[i](f, rois, chain=True), i)[0] for i in range(L)]
         else:
             lvl_feats = [self.roi_layers[i](feats[i], rois) for i in range(L)]
         if rois.is_cuda and torch.is_grad_enabled() and any(f.requires_grad for f in lvl_feats):

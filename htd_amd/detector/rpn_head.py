@@ -168,7 +168,7 @@ class RPNHead(AnchorHead):
                       ([self.rpn_cls.weight.new_zeros(pad, *self.rpn_cls.weight.shape[1:])] if pad else []))
         b = torch.cat([self.rpn_cls.bias, self.rpn_reg.bias] + ([self.rpn_cls.bias.new_zeros(pad)] if pad else []))
         cls, reg, merged = [], [], []
-        taps = isinstance(feats, M.PyramidTaps)      # the pyramid as a chain of consumers: see Conv2dFunction(chain=True)
+        taps = isinstance(feats, M.PyramidTaps)      # the pyramid as a chain of consumers (the gradient hand-off of DESIGN.md)
         from .. import dense
         if torch.is_grad_enabled() and w.requires_grad:
             # five levels read these two tensors: their gradients collect in one buffer each (dense.temp_grad_sink)
@@ -178,9 +178,8 @@ class RPNHead(AnchorHead):
             x = feats[i]
             if x.dtype == torch.float32 and x.size(1) % 8 == 0:
                 # 3x3 + ReLU + merged 1x1 heads as one autograd node (the hidden map's ReLU mask rides the head's dgrad)
-                y = dense.conv_relu_head(x, self.rpn_conv.weight, self.rpn_conv.bias, w, b, self.rpn_conv.padding[0], taps)
-                if taps:
-                    y, feats.levels[i] = y
+                conv = (self.rpn_conv.weight, self.rpn_conv.bias, w, b, self.rpn_conv.padding[0])
+                y = feats.tap(lambda f: dense.conv_relu_head(f, *conv, True), i)[0] if taps else dense.conv_relu_head(x, *conv)
             else:
                 h = self.rpn_conv(x, relu=True)
                 if h.dtype != torch.float32:     # bf16 pyramid: the heads and all box math stay fp32

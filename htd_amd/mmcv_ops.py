@@ -69,23 +69,64 @@ class PyramidTaps:
         return len(self.levels)
 
     def __getitem__(self, i):
-        return self.levels[i] if not isinstance(i, slice) else self.levels[i]
+        return self.levels[i]
+
+    def tap(self, consumer, first=0, count=1):
+        """consumer(*levels[first:first + count]) -> (*outs, one alias per level): the aliases become the levels the next
+        consumer reads; -> outs (a tuple)"""
+        res = consumer(*self.levels[first:first + count])
+        self.levels[first:first + count] = res[-count:]
+        return res[:-count]
 
 
-def _grad_buffer(galias, shape, device, dtype):
-    """Gradient map to scatter into: the one handed down the tap chain when usable, else fresh zeros."""
-    if galias is not None and galias.dtype == dtype and tuple(galias.shape) == tuple(shape) and \
-            galias.is_contiguous(memory_format=CL):
-        return galias
-    buf = torch.empty(shape, device=device, dtype=dtype, memory_format=CL).zero_()
-    if galias is not None:
-        buf += galias
-    return buf
+def chain_outputs(ctx, outs, srcs, chain):
+    """What the forward of a node of the gradient hand-off returns: `outs` (a tensor or a tuple), and with `chain`
+    an identity alias of every tensor of `srcs` behind them.  Outputs and aliases nobody used arrive in backward as None, not
+    as full-size maps of zeros: every such backward passes a handed map on, or returns nothing, when its own output is None."""
+    ctx.set_materialize_grads(False)
+    if not chain:
+        return outs
+    return (*(outs if isinstance(outs, tuple) else (outs, )), *[t.view_as(t) for t in srcs])
+
+
+def _grad_map(handed, shape, dtype, device, zero=False):
+    """The map a node's backward writes its share of a gradient into -> (map, acc).  A gradient handed to the node's alias is
+    that map itself when a kernel can write it in place (right dtype and shape, channels-last): acc = 1, and the maximum it may
+    carry is void (dense.drop_amax: modified behind torch's back).  Otherwise a fresh map: a copy of the handed gradient
+    (acc = 1), or with nothing handed uninitialised (acc = 0: the kernel writes every element), zero-filled on request (the
+    scatter kernels, which only add)."""
+    if handed is not None and handed.dtype == dtype and tuple(handed.shape) == tuple(shape) and \
+            handed.is_contiguous(memory_format=CL):
+        _drop_amax(handed)
+        return handed, 1
+    gf = torch.empty(shape, device=device, dtype=dtype, memory_format=CL)
+    if handed is not None:
+        gf.copy_(handed)
+        return gf, 1
+    return (gf.zero_() if zero else gf), 0
+
+
+def _level_maps(handed, write, shapes, dtype, device):
+    """_grad_map of every level a multi-level gather launch writes (write[i]) -> (maps, accs); (None, 0) for the others"""
+    pairs = [_grad_map(handed[i], shape, dtype, device) if write[i] else (None, 0) for i, shape in enumerate(shapes)]
+    return [m for m, _ in pairs], [a for _, a in pairs]
+
+
+def _roi_level_tables(shapes, scales, *tensor_lists, accs=None):
+    """The per-level arguments of a multi-level launch as ctypes arrays -> [one pointer table per tensor list (None: NULL)..., Hs,
+    Ws, scales(, accs)]"""
+    L = len(shapes)
+    tabs = [(ctypes.c_void_p * L)(*[t.data_ptr() if t is not None else None for t in ts]) for ts in tensor_lists]
+    tabs += [(ctypes.c_int * L)(*[s_[2] for s_ in shapes]), (ctypes.c_int * L)(*[s_[3] for s_ in shapes]),
+             (ctypes.c_float * L)(*[float(v) for v in scales])]
+    if accs is not None:
+        tabs.append((ctypes.c_int * L)(*accs))
+    return tabs
 
 
 # RoIAlign backward: 'gather' (default) -- a wavefront owns a strip of feature-map pixels and sums the RoIs covering it in
 # RoI order: no float atomics, bit-stable, every pixel written once (no memset); 'scatter' -- the atomic kernels.
-ROI_BWD = __import__('os').environ.get('HTD_ROI_BWD', 'gather')
+ROI_BWD = os.environ.get('HTD_ROI_BWD', 'gather')
 ROI_BWD_ONE_LAUNCH = True        # gather form: all levels of a SingleRoIExtractor in one launch (False: one launch per level)
 
 
@@ -94,20 +135,10 @@ def _roi_align_bwd(g, rois, lvls, level, galias, shape, ph, pw, scale, sr, align
     B, C, H, W = shape
     n = rois.size(0)
     if ROI_BWD != 'gather' or ph > 8 or pw > 8:
-        gf = _grad_buffer(galias, shape, g.device, g.dtype)
+        gf, _ = _grad_map(galias, shape, g.dtype, g.device, zero=True)
         capi.call('htd_roi_align_bwd', _P(g), _P(rois), _P(lvls), level, _P(gf), n, B, C, H, W, ph, pw, scale, sr, aligned, _S())
         return gf
-    usable = galias is not None and galias.dtype == g.dtype and tuple(galias.shape) == tuple(shape) and \
-        galias.is_contiguous(memory_format=CL)
-    if usable:
-        gf, acc = galias, 1
-        _drop_amax(gf)             # modified in place behind torch's back: a carried maximum (dense.tag_amax) is void
-    else:
-        gf = torch.empty(shape, device=g.device, dtype=g.dtype, memory_format=CL)
-        acc = 0
-        if galias is not None:
-            gf.copy_(galias)
-            acc = 1
+    gf, acc = _grad_map(galias, shape, g.dtype, g.device)
     ws = torch.empty(capi.lib().htd_roi_align_bwd_gather_workspace_bytes(n), dtype=torch.uint8, device=g.device)
     # algorithmic bytes: the map written once (+ read when accumulating) + every RoI's 7x7xC gradient read once
     work = ('byte', 4.0 * (B * H * W * C * (1 + acc) + n * ph * pw * C)) if level in (0, None) or lvls is None else ('byte', 0.0)
@@ -139,30 +170,9 @@ def _roi_align_levels_bwd(g, rois, lvls, handed, need, shapes, ph, pw, scales, s
     """Gradient maps of every level that needs one, ONE launch (htd_roi_align_levels_bwd_gather): handed[i] (+)= RoIAlign_i^T(g),
     or a fresh map where nothing was handed down."""
     L, n = len(shapes), rois.size(0)
-    maps, accs = [], []
-    for i, shape in enumerate(shapes):
-        if not need[i]:
-            maps.append(None)
-            accs.append(0)
-            continue
-        ga = handed[i]
-        usable = ga is not None and ga.dtype == g.dtype and tuple(ga.shape) == tuple(shape) and ga.is_contiguous(memory_format=CL)
-        if usable:
-            _drop_amax(ga)
-            maps.append(ga)
-            accs.append(1)
-        else:
-            gf = torch.empty(shape, device=g.device, dtype=g.dtype, memory_format=CL)
-            if ga is not None:
-                gf.copy_(ga)
-            maps.append(gf)
-            accs.append(1 if ga is not None else 0)
+    maps, accs = _level_maps(handed, need, shapes, g.dtype, g.device)
     ws = torch.empty(L * capi.lib().htd_roi_align_bwd_gather_workspace_bytes(n), dtype=torch.uint8, device=g.device)
-    ptrs = (ctypes.c_void_p * L)(*[m.data_ptr() if m is not None else None for m in maps])
-    Hs = (ctypes.c_int * L)(*[s_[2] for s_ in shapes])
-    Ws = (ctypes.c_int * L)(*[s_[3] for s_ in shapes])
-    sc = (ctypes.c_float * L)(*[float(v) for v in scales])
-    ac = (ctypes.c_int * L)(*accs)
+    ptrs, Hs, Ws, sc, ac = _roi_level_tables(shapes, scales, maps, accs=accs)
     B, C = shapes[0][0], shapes[0][1]
     # algorithmic bytes: every map written once (+ read when accumulating) + every RoI's 7x7xC gradient read once
     work = ('byte', 4.0 * (sum(s_[0] * s_[2] * s_[3] * C * (1 + a) for s_, a, m in zip(shapes, accs, maps) if m is not None) +
@@ -186,8 +196,7 @@ class RoIAlignFunction(Function):
         _need_gpu(feat, 'roi_align')
         if rois.dim() != 2 or rois.size(1) != 5:
             raise AssertionError('RoI must be (idx, x1, y1, x2, y2)!')  # roi_align.py:136
-        src = feat
-        feat = nhwc(_f32(feat, 'roi_align'))
+        src, feat = feat, nhwc(_f32(feat, 'roi_align'))
         rois = _f32(rois, 'roi_align').contiguous()
         ph, pw = _pair(output_size)
         B, C, H, W = feat.shape
@@ -197,9 +206,7 @@ class RoIAlignFunction(Function):
                   float(spatial_scale), int(sampling_ratio), int(bool(aligned)), _S())
         ctx.save_for_backward(rois)
         ctx.args = ((B, C, H, W), ph, pw, float(spatial_scale), int(sampling_ratio), int(bool(aligned)))
-        ctx.chain = bool(chain)
-        ctx.set_materialize_grads(False)      # an unused alias must arrive as None, not as a full-size zero map
-        return (out, src.view_as(src)) if chain else out
+        return chain_outputs(ctx, out, (src, ), chain)
 
     @staticmethod
     @once_differentiable
@@ -211,7 +218,7 @@ class RoIAlignFunction(Function):
         if grad_out is None:
             return (galias, ) + (None, ) * 6
         grad_out = nhwc(grad_out)
-        gfeat = _roi_align_bwd(grad_out, rois, None, 0, galias if ctx.chain else None, (B, C, H, W), ph, pw, scale, sr, aligned)
+        gfeat = _roi_align_bwd(grad_out, rois, None, 0, galias, (B, C, H, W), ph, pw, scale, sr, aligned)
         return gfeat, None, None, None, None, None, None
 
 
@@ -250,11 +257,8 @@ def roi_align_levels(feats, rois, target_lvls, output_size, scales, sampling_rat
     (N,C,ph,pw) tensor: level i's kernel only touches RoIs with target_lvls == i.  No nonzero(), no
     scatter, no host sync.  Differentiable w.r.t. every feats[i].  feats may be a PyramidTaps (chained gradients)."""
     if isinstance(feats, PyramidTaps):
-        n = len(scales)
-        res = _RoIAlignLevels.apply(rois, target_lvls, output_size, tuple(scales), sampling_ratio, aligned, True,
-                                    *feats.levels[:n])
-        feats.levels[:n] = list(res[1:])
-        return res[0]
+        return feats.tap(lambda *fs: _RoIAlignLevels.apply(rois, target_lvls, output_size, tuple(scales), sampling_ratio, aligned,
+                                                           True, *fs), 0, len(scales))[0]
     return _RoIAlignLevels.apply(rois, target_lvls, output_size, tuple(scales), sampling_ratio, aligned, False, *feats)
 
 
@@ -262,26 +266,19 @@ class _RoIAlignLevels(Function):
     @staticmethod
     def forward(ctx, rois, lvls, output_size, scales, sampling_ratio, aligned, chain, *feats):
         _need_gpu(feats[0], 'roi_align')
-        srcs = feats
         ph, pw = _pair(output_size)
         rois = _f32(rois, 'roi_align').contiguous()
         lvls = lvls.to(torch.int64).contiguous()
         n, C = rois.size(0), feats[0].size(1)
         # every RoI is written by exactly one level's launch (map_roi_levels clamps to [0, L)): no zero fill
         out = torch.empty((n, C, ph, pw), device=rois.device, dtype=torch.float32, memory_format=CL)
-        shapes, fs = [], []
-        for f in feats:
-            f = nhwc(_f32(f, 'roi_align'))
-            fs.append(f)
-            shapes.append((f.size(0), C, f.size(2), f.size(3)))
+        fs = [nhwc(_f32(f, 'roi_align')) for f in feats]
+        shapes = [(f.size(0), C, f.size(2), f.size(3)) for f in fs]
         L = len(fs)
         if n:
             # one launch for all levels; algorithmic bytes: each RoI is pooled on ONE level: write ph*pw*C*4 B,
             # read its footprint, mid-range 21x21 px of the 14..28 px the level mapping yields
-            ptrs = (ctypes.c_void_p * L)(*[f.data_ptr() for f in fs])
-            Hs = (ctypes.c_int * L)(*[s_[2] for s_ in shapes])
-            Ws = (ctypes.c_int * L)(*[s_[3] for s_ in shapes])
-            sc = (ctypes.c_float * L)(*[float(v) for v in scales])
+            ptrs, Hs, Ws, sc = _roi_level_tables(shapes, scales, fs)
             work = ('byte', n * C * 4.0 * (ph * pw + 21 * 21))
             from . import dense
             if dense.emits('roi'):
@@ -295,19 +292,17 @@ class _RoIAlignLevels(Function):
                           int(sampling_ratio), int(bool(aligned)), _S(), work=work)
         ctx.save_for_backward(rois, lvls)
         ctx.args = (shapes, ph, pw, scales, int(sampling_ratio), int(bool(aligned)))
-        ctx.chain = bool(chain)
-        ctx.set_materialize_grads(False)      # unused aliases must arrive as None, not as full-size zero maps
-        return (out, *[f.view_as(f) for f in srcs]) if chain else out
+        return chain_outputs(ctx, out, feats, chain)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g, *galias):
         rois, lvls = ctx.saved_tensors
         shapes, ph, pw, scales, sr, aligned = ctx.args
+        handed = list(galias) or [None] * len(shapes)          # (no aliases without chain)
         if g is None:                            # pooled features unused: hand the chained maps on unchanged
-            return (None, ) * 7 + tuple(galias[i] if (ctx.chain and i < len(galias)) else None for i in range(len(shapes)))
+            return (None, ) * 7 + tuple(handed)
         g = nhwc(g)
-        handed = [galias[i] if (ctx.chain and i < len(galias)) else None for i in range(len(shapes))]
         need = [bool(ctx.needs_input_grad[7 + i]) for i in range(len(shapes))]
         if ROI_BWD == 'gather' and ROI_BWD_ONE_LAUNCH and ph <= 8 and pw <= 8 and rois.size(0) > 0 and len(shapes) <= 6 and any(need):
             grads = _roi_align_levels_bwd(g, rois, lvls, handed, need, shapes, ph, pw, scales, sr, aligned)
@@ -332,7 +327,6 @@ class _RoIAlignAllLevels(Function):
         _need_gpu(feats[0], 'roi_align')
         if rois.dim() != 2 or rois.size(1) != 5:
             raise AssertionError('RoI must be (idx, x1, y1, x2, y2)!')  # roi_align.py:136
-        srcs = feats
         ph, pw = _pair(output_size)
         rois = _f32(rois, 'roi_align').contiguous()
         n, C, L = rois.size(0), feats[0].size(1), len(feats)
@@ -340,18 +334,12 @@ class _RoIAlignAllLevels(Function):
         shapes = [(f.size(0), C, f.size(2), f.size(3)) for f in fs]
         outs = [torch.empty((n, C, ph, pw), device=rois.device, dtype=torch.float32, memory_format=CL) for _ in range(L)]
         if n:
-            ptrs = (ctypes.c_void_p * L)(*[f.data_ptr() for f in fs])
-            optr = (ctypes.c_void_p * L)(*[o.data_ptr() for o in outs])
-            Hs = (ctypes.c_int * L)(*[s_[2] for s_ in shapes])
-            Ws = (ctypes.c_int * L)(*[s_[3] for s_ in shapes])
-            sc = (ctypes.c_float * L)(*[float(v) for v in scales])
+            ptrs, optr, Hs, Ws, sc = _roi_level_tables(shapes, scales, fs, outs)
             capi.call('htd_roi_align_all_levels_fwd', ptrs, Hs, Ws, sc, L, _P(rois), optr, n, shapes[0][0], C, ph, pw,
                       int(sampling_ratio), int(bool(aligned)), _S(), work=('byte', L * n * C * 4.0 * ph * pw))
         ctx.save_for_backward(rois)
         ctx.args = (shapes, ph, pw, tuple(float(v) for v in scales), int(sampling_ratio), int(bool(aligned)))
-        ctx.chain = bool(chain)
-        ctx.set_materialize_grads(False)      # unused outputs / aliases arrive as None, not as full-size zero maps
-        return (*outs, *[f.view_as(f) for f in srcs]) if chain else tuple(outs)
+        return chain_outputs(ctx, tuple(outs), feats, chain)
 
     @staticmethod
     @once_differentiable
@@ -360,7 +348,7 @@ class _RoIAlignAllLevels(Function):
         shapes, ph, pw, scales, sr, aligned = ctx.args
         L, n = len(shapes), rois.size(0)
         gouts = [nhwc(g) if g is not None else None for g in grads[:L]]
-        handed = [grads[L + i] if (ctx.chain and L + i < len(grads)) else None for i in range(L)]
+        handed = list(grads[L:]) or [None] * L                 # (no aliases without chain)
         need = [bool(ctx.needs_input_grad[6 + i]) for i in range(L)]
         dev = rois.device
         if n == 0 or ROI_BWD != 'gather' or ph > 8 or pw > 8 or L > 6:
@@ -371,33 +359,12 @@ class _RoIAlignAllLevels(Function):
                     continue
                 res.append(_roi_align_bwd(gouts[i], rois, None, 0, handed[i], shape, ph, pw, scales[i], sr, aligned))
             return (None, ) * 6 + tuple(res)
-        maps, accs = [], []
-        for i, shape in enumerate(shapes):
-            if not need[i] or gouts[i] is None:
-                maps.append(None)
-                accs.append(0)
-                continue
-            ga = handed[i]
-            usable = ga is not None and ga.dtype == torch.float32 and tuple(ga.shape) == tuple(shape) and \
-                ga.is_contiguous(memory_format=CL)
-            if usable:
-                _drop_amax(ga)
-                maps.append(ga)
-                accs.append(1)
-            else:
-                gf = torch.empty(shape, device=dev, dtype=torch.float32, memory_format=CL)
-                if ga is not None:
-                    gf.copy_(ga)
-                maps.append(gf)
-                accs.append(1 if ga is not None else 0)
+        # (a level whose output nobody used gets no launch share: its handed map, if any, goes on unchanged)
+        maps, accs = _level_maps(handed, [need[i] and gouts[i] is not None for i in range(L)], shapes, torch.float32, dev)
         if any(m is not None for m in maps):
             ws = torch.empty(L * capi.lib().htd_roi_align_bwd_gather_workspace_bytes(n), dtype=torch.uint8, device=dev)
-            gptr = (ctypes.c_void_p * L)(*[g.data_ptr() if (g is not None and m is not None) else None for g, m in zip(gouts, maps)])
-            mptr = (ctypes.c_void_p * L)(*[m.data_ptr() if m is not None else None for m in maps])
-            Hs = (ctypes.c_int * L)(*[s_[2] for s_ in shapes])
-            Ws = (ctypes.c_int * L)(*[s_[3] for s_ in shapes])
-            sc = (ctypes.c_float * L)(*scales)
-            ac = (ctypes.c_int * L)(*accs)
+            gused = [g if m is not None else None for g, m in zip(gouts, maps)]
+            gptr, mptr, Hs, Ws, sc, ac = _roi_level_tables(shapes, scales, gused, maps, accs=accs)
             B, C = shapes[0][0], shapes[0][1]
             work = ('byte', 4.0 * sum(s_[0] * s_[2] * s_[3] * C * (1 + a) + n * ph * pw * C
                                       for s_, a, m in zip(shapes, accs, maps) if m is not None))
@@ -416,9 +383,8 @@ def roi_align_all_levels(feats, rois, output_size, scales, sampling_ratio=0, ali
     """[RoIAlign(feats[i], rois) for i] in one launch each way.  feats: list of maps or a PyramidTaps (chained gradients)."""
     L = len(scales)
     if isinstance(feats, PyramidTaps):
-        res = _RoIAlignAllLevels.apply(rois, output_size, tuple(scales), sampling_ratio, aligned, True, *feats.levels[:L])
-        feats.levels[:L] = list(res[L:])
-        return list(res[:L])
+        return list(feats.tap(lambda *fs: _RoIAlignAllLevels.apply(rois, output_size, tuple(scales), sampling_ratio, aligned, True,
+                                                                   *fs), 0, L))
     return list(_RoIAlignAllLevels.apply(rois, output_size, tuple(scales), sampling_ratio, aligned, False, *list(feats)[:L]))
 
 
@@ -767,16 +733,12 @@ class GlobalAvgPoolFunction(Function):
         THIS node's backward, which adds the pooling's share into it in place (htd_global_avg_pool_bwd_acc) -- x's producer
         gets one gradient map and autograd has nothing to add (BA: four (n,256,7,7) adds per step)."""
         _need_gpu(x, 'global_avg_pool')
-        src = x
-        x = nhwc(_f32(x, 'global_avg_pool'))
+        src, x = x, nhwc(_f32(x, 'global_avg_pool'))
         n, C, h, w = x.shape
         out = torch.empty(n, C, device=x.device, dtype=x.dtype)
         capi.call('htd_global_avg_pool_fwd', _P(x), _P(out), n, h * w, C, _S())
         ctx.shape = (n, C, h, w)
-        if chain:
-            ctx.set_materialize_grads(False)
-            return out.view(n, C, 1, 1), src.view_as(src)
-        return out.view(n, C, 1, 1)
+        return chain_outputs(ctx, out.view(n, C, 1, 1), (src, ), chain)
 
     @staticmethod
     @once_differentiable
@@ -788,14 +750,9 @@ class GlobalAvgPoolFunction(Function):
         if C % 4:         # the forward kernel takes any C, the backward kernels move float4 of channels: plain tensor arithmetic
             gx = (g / float(h * w)).view(n, C, 1, 1).expand(n, C, h, w)
             return (gx.contiguous(memory_format=CL) if galias is None else gx + galias), None
-        if galias is not None and galias.dtype == g.dtype and tuple(galias.shape) == (n, C, h, w) and \
-                galias.is_contiguous(memory_format=CL):
-            _drop_amax(galias)
-            capi.call('htd_global_avg_pool_bwd_acc', _P(g), _P(galias), n, h * w, C, _S())
-            return galias, None
-        gx = torch.empty((n, C, h, w), device=g.device, dtype=g.dtype, memory_format=CL)
-        capi.call('htd_global_avg_pool_bwd', _P(g), _P(gx), n, h * w, C, _S())
-        return (gx if galias is None else gx + galias), None
+        gx, acc = _grad_map(galias, (n, C, h, w), g.dtype, g.device)
+        capi.call('htd_global_avg_pool_bwd_acc' if acc else 'htd_global_avg_pool_bwd', _P(g), _P(gx), n, h * w, C, _S())
+        return gx, None
 
 
 def global_avg_pool(x, chain=False):

@@ -648,7 +648,8 @@ def test_global_avg_pool(dev, n, C, hw):
 def test_global_avg_pool_chain(dev, n, C, hw, consumer):
     """chain=True (the path the BA extractor trains on): the node also returns an alias of x, and a second consumer's gradient of
     that alias is handed to this node, which adds g / P into it in place with htd_global_avg_pool_bwd_acc (gap_bwd_kernel, acc = 1)
-    when it is channels-last; a gradient in another layout, or none, takes the plain kernel and a tensor add.  Integers: exact at
+    when it is channels-last; a gradient in another layout is copied into a channels-last map first, none takes the plain kernel.
+    Integers: exact at
     P a power of two, within the float bound otherwise."""
     from htd_amd import mmcv_ops as M
     h, w = hw
