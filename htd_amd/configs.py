@@ -135,6 +135,26 @@ def cascade_rcnn_config(depth=50):
     return _baseline_config(cascade_rcnn_model(depth), train_cfg, depth)
 
 
+def faster_rcnn_gn_ws_model(depth=50):
+    """configs/gn+ws/faster_rcnn_r50_fpn_gn_ws-all_1x_coco.py over faster_rcnn_model: weight-standardised convolutions and
+    GroupNorm(32) in the backbone, the neck and a Shared4Conv1FCBBoxHead."""
+    conv_cfg, norm_cfg = dict(type='ConvWS'), dict(type='GN', num_groups=32, requires_grad=True)
+    model = faster_rcnn_model(depth)
+    model['pretrained'] = f'open-mmlab://jhu/resnet{depth}_gn_ws'
+    model['backbone'].update(conv_cfg=dict(conv_cfg), norm_cfg=dict(norm_cfg))
+    model['neck'].update(conv_cfg=dict(conv_cfg), norm_cfg=dict(norm_cfg))
+    model['roi_head']['bbox_head'].update(type='Shared4Conv1FCBBoxHead', conv_out_channels=256, conv_cfg=dict(conv_cfg),
+                                          norm_cfg=dict(norm_cfg))
+    return model
+
+
+def faster_rcnn_gn_ws_config(depth=50):
+    """faster_rcnn_r{depth}_fpn_gn_ws-all_1x_coco: faster_rcnn_config with the GN+WS model."""
+    cfg = faster_rcnn_config(depth)
+    cfg.model = ConfigDict(faster_rcnn_gn_ws_model(depth))
+    return cfg
+
+
 def retinanet_model(depth=50):
     """configs/_base_/models/retinanet_r50_fpn.py: P3-P7 (P6, P7 by stride-2 convolutions from C5), nine anchors per position,
     focal loss on 80 sigmoid classes and L1 on the deltas."""
@@ -275,16 +295,16 @@ def build_htd_detector(depth=50, dcn=False, cfg=None, bf16=False, resnext=False)
 
 
 def build_baseline_detector(kind='faster_rcnn', depth=50, cfg=None, bf16=False):
-    """kind = 'faster_rcnn' | 'cascade_rcnn' -> the detector of faster_rcnn_config / cascade_rcnn_config (or of `cfg`), with
-    the `pretrained` URL of the reference's config dropped: weights come from a checkpoint or from init_weights.  bf16 as in
+    """kind = 'faster_rcnn' | 'cascade_rcnn' | 'faster_rcnn_gn_ws' -> the detector of faster_rcnn_config / cascade_rcnn_config /
+    faster_rcnn_gn_ws_config (or of `cfg`), with the `pretrained` URL of the reference's config dropped: weights come from a checkpoint or from init_weights.  bf16 as in
     build_htd_detector."""
-    makers = dict(faster_rcnn=faster_rcnn_config, cascade_rcnn=cascade_rcnn_config)
+    makers = dict(faster_rcnn=faster_rcnn_config, cascade_rcnn=cascade_rcnn_config, faster_rcnn_gn_ws=faster_rcnn_gn_ws_config)
     if cfg is None:
         if kind not in makers:
             raise ValueError(f'build_baseline_detector: kind must be one of {sorted(makers)}, got {kind!r}')
         cfg = makers[kind](depth)
     cfg = copy.deepcopy(cfg)
-    if str(cfg.model.get('pretrained') or '').startswith('torchvision://'):
+    if str(cfg.model.get('pretrained') or '').startswith(('torchvision://', 'open-mmlab://')):
         cfg.model.pretrained = None
     return build_htd_detector(cfg=cfg, bf16=bf16)
 

@@ -1408,3 +1408,11 @@ extern "C" int htd_rows_add(const float *g, const int64_t *rows, float *gx, int6
     return htd::check_launch("rows_add");
 }
 
+// colsum_rows_kernel for the other translation units (group_norm_map.hip): out0[c] / out1[c] = the sum of rows [0, rows) /
+// [rows, 2 * rows) of ws[..][n], in its fixed order
+namespace htd {
+void launch_colsum_rows(const float *ws, float *out0, float *out1, int n, int rows, hipStream_t s)
+{
+    hipLaunchKernelGGL(colsum_rows_kernel, dim3((unsigned)ceil_div(n, 16), 2), dim3(256), 0, s, ws, out0, out1, n, rows);
+}
+}  // namespace htd

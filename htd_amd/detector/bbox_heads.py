@@ -467,3 +467,12 @@ class Shared2FCBBoxHead(ConvFCBBoxHead):
     def __init__(self, fc_out_channels=1024, *args, **kwargs):
         super().__init__(num_shared_convs=0, num_shared_fcs=2, num_cls_convs=0, num_cls_fcs=0, num_reg_convs=0,
                          num_reg_fcs=0, fc_out_channels=fc_out_channels, *args, **kwargs)
+
+
+@HEADS.register_module()
+class Shared4Conv1FCBBoxHead(ConvFCBBoxHead):
+    """convfc_bbox_head.py:192-205: four shared 3x3 ConvModules (ConvWS + GN in configs/gn+ws) on the 7x7 RoI tiles, then one FC."""
+
+    def __init__(self, fc_out_channels=1024, *args, **kwargs):
+        super().__init__(num_shared_convs=4, num_shared_fcs=1, num_cls_convs=0, num_cls_fcs=0, num_reg_convs=0,
+                         num_reg_fcs=0, fc_out_channels=fc_out_channels, *args, **kwargs)

@@ -55,6 +55,27 @@ class Conv2d(nn.Conv2d):
         return dense_conv2d(x, w, b, self.stride[0], self.padding[0], self.dilation[0], relu, residual, residual_up, chain)
 
 
+@CONV_LAYERS.register_module('ConvWS')
+class ConvWS2d(Conv2d):
+    """mmcv.cnn.ConvWS2d (conv_cfg=dict(type='ConvWS'), configs/gn+ws): the convolution runs on the standardised weight
+    (w - mean) / (std + eps) of each output channel.  mmcv-knowledge: mmcv 1.2.1, torch.std (unbiased) and eps beside the
+    root.  The parameter stays `weight`; the standardised image takes the route of the folded BatchNorm weights."""
+
+    def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, groups=1, bias=True,
+                 eps=1e-5):
+        super().__init__(in_channels, out_channels, kernel_size, stride=stride, padding=padding, dilation=dilation,
+                         groups=groups, bias=bias)
+        self.eps = eps
+
+    def standardized_weight(self):
+        return M.weight_standardize(self.weight, self.eps)
+
+    def forward(self, x, relu=False, residual=None, weight=None, bias=None, residual_up=False, chain=False):
+        assert weight is None, 'ConvWS2d standardises its own weight'
+        return super().forward(x, relu=relu, residual=residual, weight=self.standardized_weight(), bias=bias,
+                               residual_up=residual_up, chain=chain)
+
+
 def build_conv_layer(cfg, *args, **kwargs):
     cfg_ = dict(type='Conv2d') if cfg is None else dict(cfg)
     layer_type = cfg_.pop('type')
@@ -303,7 +324,8 @@ def constant_init(module, val, bias=0):
 
 class ConvModule(nn.Module):
     """conv -> norm -> ReLU block (mmcv.cnn.ConvModule with order conv/norm/act, bias='auto').
-    GroupNorm+ReLU runs as one fused HIP kernel; a ReLU with no norm is fused into the conv epilogue."""
+    GroupNorm+ReLU runs as one fused HIP kernel (mmcv_ops.use_group_norm_map says which: whole maps or RoI tiles); a ReLU with
+    no norm is fused into the conv epilogue."""
 
     def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, groups=1,
                  bias='auto', conv_cfg=None, norm_cfg=None, act_cfg=dict(type='ReLU'), inplace=True, **unused):
@@ -347,6 +369,8 @@ class ConvModule(nn.Module):
             x = x.float()
         norm = self.norm
         if isinstance(norm, nn.GroupNorm):
+            if M.use_group_norm_map(x, norm.num_groups):                 # whole maps (backbone, neck); RoI tiles keep the tile kernels
+                return M.group_norm_map(x, norm.weight, norm.bias, norm.num_groups, norm.eps, self.with_activation)
             return M.group_norm_relu(x, norm.weight, norm.bias, norm.num_groups, norm.eps, self.with_activation)
         x = norm(x)
         return F.relu(x) if self.with_activation else x

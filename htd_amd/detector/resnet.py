@@ -17,14 +17,26 @@ from torch.nn.modules.batchnorm import _BatchNorm
 from .. import mmcv_ops as M
 from ..dense import ResStageBf16Function, ResStageFunction
 from ..registry import BACKBONES
-from .bricks import build_conv_layer, build_norm_layer, constant_init, frozen_bn_fold, frozen_bn_fold_many, kaiming_init
+from .bricks import ConvWS2d, build_conv_layer, build_norm_layer, constant_init, frozen_bn_fold, frozen_bn_fold_many, kaiming_init
 
 CL = torch.channels_last
 FUSE_BF16_STAGE = os.environ.get('HTD_BF16_STAGE', '1') != '0'
 
 
 def conv_bn(conv, bn, x, relu=False, residual=None):
-    """conv -> BN (-> + residual) (-> ReLU) as one fused conv when BN uses its running statistics."""
+    """conv -> BN (-> + residual) (-> ReLU) as one fused conv when BN uses its running statistics.  A GroupNorm (norm_cfg
+    type 'GN', configs/gn, configs/gn+ws) has no statistics to fold: conv, then ONE normalising pass that also adds the
+    residual and applies the ReLU (mmcv_ops.group_norm_map), in train and eval mode alike."""
+    if isinstance(bn, nn.GroupNorm):
+        y = conv(x)
+        if y.is_cuda and y.dtype == torch.float32:
+            return M.group_norm_map(y, bn.weight, bn.bias, bn.num_groups, bn.eps, relu, residual)
+        y = bn(y)
+        if residual is not None:
+            y = y + residual
+        return torch.relu(y) if relu else y
+    if isinstance(conv, ConvWS2d):
+        raise NotImplementedError('ConvWS under a BatchNorm: no config has it (the BN fold would have to follow the standardisation)')
     if bn.training:
         y = bn(conv(x))
         if residual is not None:

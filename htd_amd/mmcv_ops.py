@@ -810,6 +810,130 @@ def group_norm_relu(x, weight, bias, num_groups, eps=1e-5, relu=True):
     return GroupNormReLUFunction.apply(x, weight, bias, num_groups, eps, relu)
 
 
+class GroupNormMapFunction(Function):
+    """y = [relu](GN(x) [+ residual]) on a whole feature map (csrc/group_norm_map.hip): a sample is spread over many workgroups
+    by position slabs, where GroupNormReLUFunction's kernels give it one -- the GroupNorm behind every convolution of a
+    norm_cfg=dict(type='GN') backbone / neck.  Two launches forward, three backward, no float atomics."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, num_groups, eps, relu, residual):
+        _need_gpu(x, 'group_norm_map')
+        x = nhwc(_f32(x, 'group_norm_map'))
+        n, C, h, w = x.shape
+        if residual is not None:
+            if residual.shape != x.shape:
+                raise ValueError(f'group_norm_map: residual {tuple(residual.shape)} against x {tuple(x.shape)}')
+            residual = nhwc(_f32(residual, 'group_norm_map'))
+        y = torch.empty_like(x, memory_format=CL)
+        mean = torch.empty(n, num_groups, device=x.device, dtype=x.dtype)
+        rstd = torch.empty_like(mean)
+        L = capi.lib()
+        ws = torch.empty(L.htd_group_norm_map_workspace_bytes(n, h * w, C, int(num_groups)), dtype=torch.uint8, device=x.device)
+        from . import dense
+        slot = dense._amax_slot(x.device) if (n > 0 and L.htd_conv2d_set_h2(-1) == 1) else None
+        capi.call('htd_group_norm_map_fwd', _P(x), _P(residual), _P(weight), _P(bias), _P(y), _P(mean), _P(rstd), n, h * w, C,
+                  int(num_groups), float(eps), int(bool(relu)), _P(ws), _P(slot), _S(),
+                  work=('byte', 4.0 * x.numel() * (3 + (residual is not None))))
+        if slot is not None:              # max |y| for the convolution behind this layer (H2 arithmetic, dense.carried_amax)
+            dense.tag_amax(y, slot)
+        ctx.save_for_backward(x, y, weight, mean, rstd)
+        ctx.meta = (int(num_groups), int(bool(relu)), residual is not None)
+        ctx.bias_ref = bias                   # only its address is used (gradient sink lookup)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        x, y, weight, mean, rstd = ctx.saved_tensors
+        G, relu, has_res = ctx.meta
+        n, C, h, w = x.shape
+        gy = nhwc(gy)
+        gx = torch.empty_like(x, memory_format=CL)
+        # the residual's gradient is the masked gy; without a ReLU that is gy itself and the kernel writes nothing
+        gres = torch.empty_like(x, memory_format=CL) if (has_res and relu and ctx.needs_input_grad[6]) else None
+        from . import dense
+        gw = dense.grad_out(weight)           # straight into the flat gradient buffer when the parameters are registered there
+        gb = dense.grad_out(ctx.bias_ref) if ctx.bias_ref is not None and ctx.bias_ref.shape == weight.shape else torch.empty_like(weight)
+        L = capi.lib()
+        ws = torch.empty(L.htd_group_norm_map_workspace_bytes(n, h * w, C, G), dtype=torch.uint8, device=x.device)
+        slot = dense._amax_slot(x.device) if (n > 0 and L.htd_conv2d_set_h2(-1) == 1) else None
+        capi.call('htd_group_norm_map_bwd', _P(x), _P(y), _P(weight), _P(mean), _P(rstd), _P(gy), _P(gx), _P(gres), _P(gw),
+                  _P(gb), n, h * w, C, G, relu, _P(ws), _P(slot), _S(),
+                  work=('byte', 4.0 * x.numel() * (7 + (gres is not None))))
+        if slot is not None:
+            dense.tag_amax(gx, slot)
+        if has_res and not relu and ctx.needs_input_grad[6]:
+            gres = gy
+        return gx, gw, gb, None, None, None, gres
+
+
+def group_norm_map(x, weight, bias, num_groups, eps=1e-5, relu=True, residual=None):
+    """[relu](GroupNorm(x) [+ residual]) with the whole-map kernels; GPU fp32, C % 4 == 0, 64 <= C <= 2048, C / num_groups a
+    power of two in [2, 64] (anything else raises)."""
+    return GroupNormMapFunction.apply(x, weight, bias, num_groups, eps, relu, residual)
+
+
+def use_group_norm_map(x, num_groups=None):
+    """Which GroupNorm kernels take the (n, C, h, w) tensor x.  The RoI-tile kernels of group_norm_relu give a sample one workgroup:
+    right for thousands of tiles.  The map kernels take what those cannot cover: fewer samples than the part has compute units
+    (n < 256) and more positions than any RoI tile of any config has (h * w > 14 * 14) -- where they support the shape (C % 4 == 0,
+    64 <= C <= 2048, C / num_groups a power of two in [2, 64]); any other layer stays where it ran before."""
+    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.size(0) < 256 and x.size(2) * x.size(3) > 196):
+        return False
+    C = x.size(1)
+    if C % 4 or C < 64 or C > 2048:
+        return False
+    if num_groups is None:
+        return True
+    cpg = C // num_groups if num_groups > 0 and C % num_groups == 0 else 0
+    return 2 <= cpg <= 64 and cpg & (cpg - 1) == 0
+
+
+def _weight_standardize_ref(w, eps):
+    """mmcv-knowledge (mmcv 1.2.1 ConvWS2d / conv_ws_2d): per output channel, unbiased std, eps added to the std."""
+    flat = w.reshape(w.size(0), -1)
+    mean = flat.mean(dim=1, keepdim=True)
+    std = flat.std(dim=1, keepdim=True)
+    return ((flat - mean) / (std + eps)).view_as(w)
+
+
+class WeightStandardizeFunction(Function):
+    """One launch forward (htd_weight_standardize_fwd, keeps each row's mean and 1 / (std + eps)), one backward."""
+
+    @staticmethod
+    def forward(ctx, w, eps):
+        w = w.contiguous(memory_format=CL) if w.dim() == 4 else w.contiguous()        # KRSC: a row is contiguous
+        Co = w.size(0)
+        K = w.numel() // max(Co, 1)
+        out = torch.empty_like(w, memory_format=CL) if w.dim() == 4 else torch.empty_like(w)
+        mean = torch.empty(Co, device=w.device, dtype=w.dtype)
+        inv = torch.empty_like(mean)
+        capi.call('htd_weight_standardize_fwd', _P(w), _P(out), _P(mean), _P(inv), Co, K, float(eps), _S())
+        ctx.save_for_backward(w, mean, inv)
+        ctx.eps = float(eps)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        w, mean, inv = ctx.saved_tensors
+        Co = w.size(0)
+        K = w.numel() // Co
+        g = g.contiguous(memory_format=CL) if w.dim() == 4 else g.contiguous()
+        from . import dense
+        gw = dense.grad_out(w)
+        capi.call('htd_weight_standardize_bwd', _P(w), _P(mean), _P(inv), _P(g), _P(gw), Co, K, ctx.eps, _S())
+        return gw, None
+
+
+def weight_standardize(w, eps=1e-5):
+    """(w - mean) / (std + eps) per output channel over Ci * kh * kw (mmcv-knowledge: ConvWS2d of mmcv 1.2.1: torch.std, i.e.
+    the unbiased estimator, eps beside the root).  GPU fp32: the HIP kernels; otherwise the tensor formula."""
+    if w.is_cuda and w.dtype == torch.float32:
+        return WeightStandardizeFunction.apply(w, eps)
+    return _weight_standardize_ref(w, eps)
+
+
 # ====================================================================== optimizer step
 PARAM_EPOCH = 0
 

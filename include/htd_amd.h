@@ -475,6 +475,41 @@ int htd_fuse_global_bwd_global_ws(const float *grad, const float *rois, float *g
                                   void *workspace, void *stream);
 
 /* ------------------------------------------------------------------------------------
+ * GroupNorm over whole feature maps (csrc/group_norm_map.hip): what torch.nn.GroupNorm does behind every convolution of a
+ * norm_cfg=dict(type='GN', num_groups=32) model (mmcv.cnn.build_norm_layer; backbones/resnet.py:138-194,
+ * necks/fpn.py:69-87, bbox_heads/convfc_bbox_head.py), with the residual add and the ReLU of the bottleneck
+ * (backbones/resnet.py:249-280) in the same pass:
+ *   y = [relu](GN(x) [+ residual]),  x / y / residual [n][P][C] fp32, groups of C / G adjacent channels, mean / rstd [n][G].
+ * A sample is cut into slabs of htd_group_norm_map_slab(P, C) positions, one workgroup each; per-slab partial results go
+ * through `workspace` (htd_group_norm_map_workspace_bytes, 16-byte aligned, shared by both passes) and are combined in a
+ * fixed order: no float atomics, equal bits on every run.  Shapes: C % 4 == 0, 64 <= C <= 2048, C / G a power of two in
+ * [2, 64]; anything else returns HTD_ERR_ARG before a launch.  n = 0 launches nothing (bwd: ggamma = gbeta = 0).
+ * bwd: gx, ggamma, gbeta overwritten; gres (may be NULL) gets the residual's gradient, the ReLU-masked gy -- with relu = 0
+ * that is gy itself and nothing is written.  amax_out (may be NULL) as in htd_group_norm_relu_fwd_amax: max |y| / max |gx|
+ * joins the device scalar with at most one unsigned atomicMax per workgroup, NaN on top.
+ * ---------------------------------------------------------------------------------- */
+int htd_group_norm_map_slab(int P, int C);
+int64_t htd_group_norm_map_workspace_bytes(int64_t n, int P, int C, int G);
+int htd_group_norm_map_fwd(const float *x, const float *residual, const float *gamma, const float *beta, float *y, float *mean,
+                           float *rstd, int64_t n, int P, int C, int G, float eps, int relu, void *workspace, float *amax_out,
+                           void *stream);
+int htd_group_norm_map_bwd(const float *x, const float *y, const float *gamma, const float *mean, const float *rstd,
+                           const float *gy, float *gx, float *gres, float *ggamma, float *gbeta, int64_t n, int P, int C, int G,
+                           int relu, void *workspace, float *amax_out, void *stream);
+
+/* ------------------------------------------------------------------------------------
+ * Weight standardisation of mmcv's ConvWS2d (conv_cfg=dict(type='ConvWS'), configs/gn+ws; mmcv-knowledge: mmcv 1.2.1
+ * mmcv/cnn/bricks/conv_ws.py, whose source the reference tree does not carry):
+ *   w_hat[co][k] = (w[co][k] - mean_co) * inv_co,  inv_co = 1 / (std_co + eps),  std unbiased (torch.std) over the KRSC row of
+ *   K = kh*kw*Ci >= 2 weights, eps beside the root.  fwd keeps mean [Co] and inv [Co]; bwd maps the gradient of w_hat to w:
+ *   h = g*inv - c * (sum g*c) * inv^2 / ((K-1)*std), gw = h - mean(h), c = w - mean.  Sums in a fixed order.  A constant
+ *   row (std = 0) is outside the contract.
+ * ---------------------------------------------------------------------------------- */
+int htd_weight_standardize_fwd(const float *w, float *w_hat, float *mean, float *inv, int Co, int K, float eps, void *stream);
+int htd_weight_standardize_bwd(const float *w, const float *mean, const float *inv, const float *g_hat, float *gw, int Co, int K,
+                               float eps, void *stream);
+
+/* ------------------------------------------------------------------------------------
  * Frozen-statistics BatchNorm (norm_eval=True, backbones/resnet.py:640-649) folded into the preceding
  * convolution: w'[co][k] = w[co][k]*s, b'[co] = beta - mean*s, s = gamma/sqrt(var+eps), k over kh*kw*Ci (KRSC
  * row).  bwd maps the gradients of the folded tensors back: gw = gw'*s, gbeta = gb',
