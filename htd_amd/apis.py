@@ -149,6 +149,9 @@ def check_supported(cfg):
     grad_clip = (cfg.get('optimizer_config') or {}).get('grad_clip')
     if grad_clip is not None:
         raise NotImplementedError(f'optimizer_config.grad_clip: only None is supported, got {grad_clip!r}')
+    paramwise = (cfg.get('optimizer') or {}).get('paramwise_cfg')
+    if paramwise:
+        raise NotImplementedError(f'optimizer.paramwise_cfg: per-parameter rates and decays are not supported, got {paramwise!r}')
     for hook in (cfg.get('log_config') or {}).get('hooks', []):
         if hook.get('type') != 'TextLoggerHook':
             raise NotImplementedError(f"log_config.hooks: {hook.get('type')!r} is not supported, only TextLoggerHook")

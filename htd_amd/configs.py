@@ -5,8 +5,8 @@ load unchanged through `htd_amd.Config.fromfile` (same `type=` names and kwargs)
 
 The two baselines HTD is measured against come the same way: faster_rcnn_config (configs/faster_rcnn/
 faster_rcnn_r50_fpn_1x_coco.py) and cascade_rcnn_config (configs/cascade_rcnn/cascade_rcnn_r50_fpn_1x_coco.py), with
-their `_base_` chains merged, and so does the single-stage baseline retinanet_config (configs/retinanet/
-retinanet_r50_fpn_1x_coco.py).
+their `_base_` chains merged, and so do the single-stage baselines retinanet_config (configs/retinanet/
+retinanet_r50_fpn_1x_coco.py) and fcos_config (the two configs/fcos/fcos_*_r50_caffe_fpn_gn-head_4x4_1x_coco.py).
 """
 import copy
 
@@ -184,6 +184,52 @@ def retinanet_config(depth=50):
     return cfg
 
 
+FCOS_VARIANTS = ('gn-head', 'center-normbbox-centeronreg-giou')
+
+
+def fcos_model(depth=50, variant='gn-head'):
+    """configs/fcos/fcos_r50_caffe_fpn_gn-head_4x4_1x_coco.py: a caffe-style backbone with frozen BN, P3-P7 with P6 / P7 by
+    convolutions on the ReLU of the output P5, a GroupNorm(32) FCOSHead with IoULoss.  variant 'center-normbbox-centeronreg-giou'
+    (configs/fcos/fcos_center-normbbox-centeronreg-giou_r50_caffe_fpn_gn-head_4x4_1x_coco.py): centre sampling, stride-normalised
+    distances, the centerness on the regression tower, conv biases and GIoULoss."""
+    if variant not in FCOS_VARIANTS:
+        raise ValueError(f'fcos_model: variant must be one of {FCOS_VARIANTS}, got {variant!r}')
+    tricks = variant != 'gn-head'
+    head = dict(type='FCOSHead', num_classes=80, in_channels=256, stacked_convs=4, feat_channels=256,
+                strides=[8, 16, 32, 64, 128],
+                loss_cls=dict(type='FocalLoss', use_sigmoid=True, gamma=2.0, alpha=0.25, loss_weight=1.0),
+                loss_bbox=dict(type='GIoULoss' if tricks else 'IoULoss', loss_weight=1.0),
+                loss_centerness=dict(type='CrossEntropyLoss', use_sigmoid=True, loss_weight=1.0))
+    if tricks:
+        head.update(norm_on_bbox=True, centerness_on_reg=True, dcn_on_last_conv=False, center_sampling=True, conv_bias=True)
+    return dict(
+        type='FCOS', pretrained=f"open-mmlab://{'detectron2' if tricks else 'detectron'}/resnet{depth}_caffe",
+        backbone=dict(type='ResNet', depth=depth, num_stages=4, out_indices=(0, 1, 2, 3), frozen_stages=1,
+                      norm_cfg=dict(type='BN', requires_grad=False), norm_eval=True, style='caffe'),
+        neck=dict(type='FPN', in_channels=[256, 512, 1024, 2048], out_channels=256, start_level=1, add_extra_convs=True,
+                  extra_convs_on_inputs=False, num_outs=5, relu_before_extra_convs=True),
+        bbox_head=head)
+
+
+def fcos_config(depth=50, variant='gn-head'):
+    """The two FCOS configs of fcos_model, 4 images per GPU, lr 0.01 with doubled, undecayed biases (paramwise_cfg); the plain
+    one clips gradients at norm 35 and warms up at a constant third of the rate, the other warms up linearly without clipping.
+    (`python -m htd_amd.train` refuses paramwise_cfg, grad_clip and constant warm-up: apis.check_supported.)"""
+    cfg = _baseline_config(
+        fcos_model(depth, variant),
+        dict(assigner=dict(type='MaxIoUAssigner', pos_iou_thr=0.5, neg_iou_thr=0.4, min_pos_iou=0, ignore_iof_thr=-1),
+             allowed_border=-1, pos_weight=-1, debug=False), depth)
+    tricks = variant != 'gn-head'
+    cfg.test_cfg = ConfigDict(nms_pre=1000, min_bbox_size=0, score_thr=0.05,
+                              nms=dict(type='nms', iou_threshold=0.6 if tricks else 0.5), max_per_img=100)
+    cfg.optimizer = ConfigDict(type='SGD', lr=0.01, momentum=0.9, weight_decay=0.0001,
+                               paramwise_cfg=dict(bias_lr_mult=2., bias_decay_mult=0.))
+    cfg.optimizer_config = ConfigDict(grad_clip=None if tricks else dict(max_norm=35, norm_type=2))
+    cfg.lr_config = ConfigDict(policy='step', warmup='linear' if tricks else 'constant', warmup_iters=500, warmup_ratio=1.0 / 3,
+                               step=[8, 11])
+    return cfg
+
+
 IMG_NORM_CFG = dict(mean=[123.675, 116.28, 103.53], std=[58.395, 57.12, 57.375], to_rgb=True)
 
 
@@ -295,10 +341,11 @@ def build_htd_detector(depth=50, dcn=False, cfg=None, bf16=False, resnext=False)
 
 
 def build_baseline_detector(kind='faster_rcnn', depth=50, cfg=None, bf16=False):
-    """kind = 'faster_rcnn' | 'cascade_rcnn' | 'faster_rcnn_gn_ws' -> the detector of faster_rcnn_config / cascade_rcnn_config /
-    faster_rcnn_gn_ws_config (or of `cfg`), with the `pretrained` URL of the reference's config dropped: weights come from a checkpoint or from init_weights.  bf16 as in
-    build_htd_detector."""
-    makers = dict(faster_rcnn=faster_rcnn_config, cascade_rcnn=cascade_rcnn_config, faster_rcnn_gn_ws=faster_rcnn_gn_ws_config)
+    """kind = 'faster_rcnn' | 'cascade_rcnn' | 'faster_rcnn_gn_ws' | 'fcos' | 'fcos_center' -> the detector of faster_rcnn_config /
+    cascade_rcnn_config / faster_rcnn_gn_ws_config / fcos_config (its two variants) (or of `cfg`), with the `pretrained` URL of the
+    reference's config dropped: weights come from a checkpoint or from init_weights.  bf16 as in build_htd_detector."""
+    makers = dict(faster_rcnn=faster_rcnn_config, cascade_rcnn=cascade_rcnn_config, faster_rcnn_gn_ws=faster_rcnn_gn_ws_config,
+                  fcos=fcos_config, fcos_center=lambda d: fcos_config(d, 'center-normbbox-centeronreg-giou'))
     if cfg is None:
         if kind not in makers:
             raise ValueError(f'build_baseline_detector: kind must be one of {sorted(makers)}, got {kind!r}')

@@ -229,6 +229,17 @@ class PseudoSampler:
 
 
 # ------------------------------------------------------------------ coder
+def distance2bbox(points, distance, max_shape=None):
+    """mmdet/core/bbox/transforms.py:119-140: points (n, 2) [x, y] and distances (n, 4) [left, top, right, bottom] -> boxes (n, 4),
+    clamped to the image of shape max_shape = (h, w, ...) when given."""
+    x1, y1 = points[:, 0] - distance[:, 0], points[:, 1] - distance[:, 1]
+    x2, y2 = points[:, 0] + distance[:, 2], points[:, 1] + distance[:, 3]
+    if max_shape is not None:
+        x1, x2 = x1.clamp(min=0, max=max_shape[1]), x2.clamp(min=0, max=max_shape[1])
+        y1, y2 = y1.clamp(min=0, max=max_shape[0]), y2.clamp(min=0, max=max_shape[0])
+    return torch.stack([x1, y1, x2, y2], -1)
+
+
 def bbox2delta(proposals, gt, means=(0., 0., 0., 0.), stds=(1., 1., 1., 1.)):
     assert proposals.size() == gt.size()
     proposals, gt = proposals.float(), gt.float()

@@ -29,12 +29,13 @@ def multiclass_nms(multi_bboxes, multi_scores, score_thr, nms_cfg, max_num=-1, s
     return dets, labels[keep]
 
 
-def multiclass_nms_images(multi_bboxes, multi_scores, img_of, num_imgs, score_thr, nms_cfg, max_num=-1):
+def multiclass_nms_images(multi_bboxes, multi_scores, img_of, num_imgs, score_thr, nms_cfg, max_num=-1, score_factors=None):
     """multiclass_nms of EVERY image of a batch in one pass: rows of multi_bboxes / multi_scores belong to image
     img_of[row] (int64, rows grouped by image in ascending order).  -> (dets list, labels list), element i bit-identical to
     multiclass_nms(rows of image i): the per-image class shift idx * (max coordinate of that image's candidates + 1), the
     stable score order and the cut to max_num are the per-image ones; (image, class) pairs are the segments of one NMS launch.
-    Hard NMS only -- callers route soft_nms (a sequential per-class decay) through the per-image form."""
+    Hard NMS only -- callers route soft_nms (a sequential per-class decay) through the per-image form.  score_factors (n,):
+    as in multiclass_nms, the scores that pass score_thr are multiplied by their row's factor before the NMS (FCOS centerness)."""
     from ..mmcv_ops import nms_sorted_mask
     cfg = dict(nms_cfg)
     assert cfg.pop('type', 'nms') == 'nms'
@@ -55,7 +56,8 @@ def multiclass_nms_images(multi_bboxes, multi_scores, img_of, num_imgs, score_th
     empty = (multi_bboxes.new_zeros((0, 5)), multi_bboxes.new_zeros((0, ), dtype=torch.long))
     if pos.size(0) == 0:
         return [empty[0]] * num_imgs, [empty[1]] * num_imgs
-    boxes, sc, labels = bboxes[valid], scores[valid], pos[:, 1]
+    boxes, labels = bboxes[valid], pos[:, 1]
+    sc = scores[valid] if score_factors is None else (scores * score_factors[:, None])[valid]
     img = img_of[pos[:, 0]]
     if class_agnostic:
         boxes_for_nms, seg_id = boxes, img

@@ -4,9 +4,10 @@ Reference: dense_heads/anchor_head.py:14-682 (AnchorHead: forward, get_anchors, 
 base_dense_head.py:22-59 (forward_train), retina_head.py:8-114 (RetinaHead).  Same registry names, constructor kwargs,
 state_dict keys (cls_convs / reg_convs / retina_cls / retina_reg) and return structures.  AnchorHead is also the base of RPNHead
 (detector/rpn_head.py), as in the reference: anchors, per-image targets (gt_labels None: foreground is class 0), the
-reference-order loss and forward_train are written once, here.  So are the constants of the pyramid's map shapes: `_shape_key`
-makes their cache key, `_cached` fetches them, and `_anchors_inside`, the RPN's proposal constants and the level-concatenated
-anchors of `_get_bboxes_batched` all go through the two.
+reference-order loss are written once, here; forward_train, simple_test and the cache of constants of the pyramid's map shapes
+(`_shape_key` makes their key, `_cached` fetches them) come from BaseDenseHead (detector/base_dense_head.py), which the
+anchor-free heads share: `_anchors_inside`, the RPN's proposal constants and the level-concatenated anchors of
+`_get_bboxes_batched` all go through the two.
 
 `loss` has two forms, like RPNHead.loss.  The tensor form follows the reference's order of operations (per image targets, per
 level losses) and works with any loss modules, `reg_decoded_bbox`, ignore boxes and on the CPU.  The fused form -- FocalLoss with
@@ -29,6 +30,7 @@ from ..core import anchor_inside_flags, images_to_levels, multi_apply, unmap
 from ..core.misc import const_tensor
 from .. import mmcv_ops as M
 from ..registry import HEADS, build_anchor_generator, build_assigner, build_bbox_coder, build_loss, build_sampler
+from .base_dense_head import BaseDenseHead
 from .bricks import Conv2d, ConvModule, normal_init
 
 RETINA_FUSED = os.environ.get('HTD_RETINA_FUSED', '1') != '0'       # 0: the tensor-path loss (A/B runs)
@@ -41,7 +43,7 @@ def bias_init_with_prob(prior_prob):
 
 
 @HEADS.register_module()
-class AnchorHead(nn.Module):
+class AnchorHead(BaseDenseHead):
     def __init__(self, num_classes, in_channels, feat_channels=256,
                  anchor_generator=dict(type='AnchorGenerator', scales=[8, 16, 32], ratios=[0.5, 1.0, 2.0],
                                        strides=[4, 8, 16, 32, 64]),
@@ -88,20 +90,6 @@ class AnchorHead(nn.Module):
 
     def forward(self, feats):
         return multi_apply(self.forward_single, feats)
-
-    def forward_train(self, x, img_metas, gt_bboxes, gt_labels=None, gt_bboxes_ignore=None, proposal_cfg=None, **kwargs):
-        """base_dense_head.py:22-59."""
-        outs = self(x)
-        if gt_labels is None:
-            losses = self.loss(*outs, gt_bboxes, img_metas, gt_bboxes_ignore=gt_bboxes_ignore)
-        else:
-            losses = self.loss(*outs, gt_bboxes, gt_labels, img_metas, gt_bboxes_ignore=gt_bboxes_ignore)
-        if proposal_cfg is None:
-            return losses
-        return losses, self.get_bboxes(*outs, img_metas, cfg=proposal_cfg, **kwargs)
-
-    def simple_test(self, feats, img_metas, rescale=False):
-        return self.get_bboxes(*self(feats), img_metas, rescale=rescale)
 
     # ------------------------------------------------------------------ targets
     def get_anchors(self, featmap_sizes, img_metas, device='cuda'):
@@ -221,21 +209,6 @@ class AnchorHead(nn.Module):
                 for t in list(cls_scores) + list(bbox_preds))       # (other layouts, e.g. NCHW-contiguous maps: the tensor path)
 
     # ------------------------------------------------------------------ constants of the map shapes
-    @staticmethod
-    def _shape_key(featmap_sizes):
-        """Cache key of whatever is computed from the pyramid's map sizes: the (h, w) pairs themselves, never their products --
-        a portrait and a landscape batch have the same number of anchors on every level and different anchors."""
-        return tuple(tuple(int(v) for v in f) for f in featmap_sizes)
-
-    def _cached(self, name, cap, key, make):
-        """self.<name>[key], made by make() on a miss; a cache that has grown past `cap` entries is emptied first."""
-        cache = self.__dict__.setdefault(name, {})
-        if key not in cache:
-            if len(cache) > cap:
-                cache.clear()
-            cache[key] = make()
-        return cache[key]
-
     def _anchors_inside(self, featmap_sizes, img_metas, dev):
         """(A, 4) level-concatenated anchors and the (B, A) mask of anchors that are valid and inside their image
         (anchor_head.py:200-207, core/anchor/utils.py:20-46): constants of (feature-map sizes, image shapes), cached under
@@ -385,9 +358,6 @@ class AnchorHead(nn.Module):
         dets, labels = multiclass_nms_images(boxes.reshape(B * K, 4), scores.reshape(B * K, C + 1), img_of, B, cfg.score_thr,
                                              cfg.nms, cfg.max_per_img)
         return list(zip(dets, labels))
-
-    def aug_test(self, feats, img_metas, rescale=False):
-        raise NotImplementedError('test-time augmentation of dense heads is not part of this package')
 
 
 @HEADS.register_module()

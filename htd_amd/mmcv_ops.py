@@ -1208,3 +1208,143 @@ def retina_keys(cls_maps, na, C):
     keys = torch.empty(B, A, device=cls_maps[0].device, dtype=torch.float32)
     capi.call('htd_retina_keys', ct, cs, pix, len(cls_maps), B, int(na), int(C), _P(keys), _S())
     return keys
+
+
+# ====================================================================== FCOS head (dense_heads/fcos_head.py)
+FCOS_BOX_KINDS = dict(IoULoss=0, GIoULoss=2)          # the `kind` of iou_family_loss (csrc/iou_family.h)
+
+
+def _fcos_levels(featmap_sizes, strides):
+    """-> HOST tables hw [L][2] and strides [L] of the pyramid, and P = sum of h * w."""
+    sizes = [(int(h), int(w)) for h, w in featmap_sizes]
+    strides = [int(s[0] if isinstance(s, (tuple, list)) else s) for s in strides]
+    if len(sizes) != len(strides):
+        raise ValueError(f'fcos ops: {len(sizes)} map sizes for {len(strides)} strides')
+    return _i64s([v for hw in sizes for v in hw]), _i64s(strides), sum(h * w for h, w in sizes)
+
+
+def fcos_targets(featmap_sizes, strides, regress_ranges, gts, gt_valid, center_sampling=False, radius=1.5, norm_on_bbox=False):
+    """htd_fcos_targets: FCOSHead.get_targets and centerness_target of the whole batch in one launch (+ a finishing one).
+    gts (B, K, 4) float32 / gt_valid (B, K) bool as pad_gt_batch leaves them.  -> assigned (B, P) int32 (0 background, k + 1 =
+    gt k), bbox_targets (B, P, 4), ctr_targets (B, P), num_pos (B,) int32, norm (3,) = [sum num_pos + B, max(sum num_pos, 1),
+    sum ctr_targets]; points level-major, nothing read back to the host."""
+    _need_gpu(gts, 'fcos_targets')
+    gts = _f32(gts, 'fcos_targets').contiguous()
+    gt_valid = gt_valid.to(torch.bool).contiguous()
+    B, K = gt_valid.shape
+    hw, st, P = _fcos_levels(featmap_sizes, strides)
+    ranges = (ctypes.c_float * (2 * len(regress_ranges)))(*[float(v) for r in regress_ranges for v in r])
+    if len(regress_ranges) != len(st):
+        raise ValueError(f'fcos_targets: {len(regress_ranges)} regress ranges for {len(st)} levels')
+    dev = gts.device
+    assigned = torch.empty(B, P, dtype=torch.int32, device=dev)
+    bbox_targets = torch.empty(B, P, 4, dtype=torch.float32, device=dev)
+    ctr_targets = torch.empty(B, P, dtype=torch.float32, device=dev)
+    num_pos = torch.empty(B, dtype=torch.int32, device=dev)
+    norm = torch.empty(3, dtype=torch.float32, device=dev)
+    ws = torch.empty(capi.lib().htd_fcos_targets_workspace_bytes(B, P) // 8, dtype=torch.float64, device=dev)
+    capi.call('htd_fcos_targets', hw, st, ranges, len(st), _P(gts), _P(gt_valid), B, K, int(bool(center_sampling)), float(radius),
+              int(bool(norm_on_bbox)), _P(assigned), _P(bbox_targets), _P(ctr_targets), _P(ws), _P(num_pos), _P(norm), _S())
+    return assigned, bbox_targets, ctr_targets, num_pos, norm
+
+
+def fcos_channel_stride(m):
+    """nhwc_channel_stride of a map; a one-channel map (the centerness) is NHWC whatever stride its channel dimension reports."""
+    if m.size(1) == 1 and m.stride(1) != 1:
+        m = m.as_strided(m.size(), (m.stride(0), 1, m.stride(2), m.stride(3)))
+    return nhwc_channel_stride(m)
+
+
+def _fcos_tables(maps):
+    ptrs, strides = [], []
+    for m in maps:
+        sw = fcos_channel_stride(m)
+        if sw is None:
+            raise ValueError('fcos ops: maps must be channels_last (or channel slices of channels_last maps)')
+        ptrs.append(m.data_ptr())
+        strides.append(sw)
+    return _table(ptrs), _i64s(strides)
+
+
+def _like_padded(m, stride):
+    """An uninitialised gradient map in the memory layout of m: channels_last, a slice of a `stride`-channel map when m is one."""
+    full = torch.empty(m.size(0), stride, m.size(2), m.size(3), device=m.device, dtype=torch.float32, memory_format=CL)
+    return full if stride == m.size(1) else full[:, :m.size(1)]
+
+
+class FcosLossFunction(Function):
+    """htd_fcos_loss: the three losses of FCOSHead.loss over every level and image in one launch, which also writes the three
+    finished gradient maps (loss weight and normaliser applied); backward hands them over, after htd_fcos_grad_scale applies
+    incoming gradients other than 1 on the device, in place.  Single use: a second backward through the same forward raises."""
+
+    @staticmethod
+    def forward(ctx, hw, st, C, gt_labels, assigned, bbox_targets, ctr_targets, norm, box_kind, eps, gamma, alpha, cls_weight,
+                box_weight, ctr_weight, *maps):
+        L = len(maps) // 3
+        cls, reg, ctr = maps[:L], maps[L:2 * L], maps[2 * L:]
+        B, K = gt_labels.shape
+        ct, cs = _fcos_tables(cls)
+        rt, rs = _fcos_tables(reg)
+        tt, ts = _fcos_tables(ctr)
+        gcls = [_like_padded(m, s) for m, s in zip(cls, cs)]
+        greg = [_like_padded(m, s) for m, s in zip(reg, rs)]
+        gctr = [_like_padded(m, s) for m, s in zip(ctr, ts)]
+        gct, gcs = _fcos_tables(gcls)
+        grt, grs = _fcos_tables(greg)
+        gtt, gts_ = _fcos_tables(gctr)
+        assert list(gcs) == list(cs) and list(grs) == list(rs) and list(gts_) == list(ts)
+        rows = capi.lib().htd_fcos_loss_partial_rows()
+        partial = torch.empty(rows, 2, device=assigned.device, dtype=torch.float32)
+        capi.call('htd_fcos_loss', ct, cs, rt, rs, tt, ts, hw, st, L, B, int(C), _P(gt_labels), K, _P(assigned), _P(bbox_targets),
+                  _P(ctr_targets), _P(norm), int(box_kind), float(eps), float(gamma), float(alpha), float(cls_weight),
+                  float(box_weight), float(ctr_weight), _P(partial), gct, grt, gtt, _S())
+        ctx.meta = (hw, st, L, B, int(C))
+        ctx.save_for_backward(*gcls, *greg, *gctr)
+        sums = partial.view(2, rows // 2, 2).sum(1)             # [[focal, box], [centerness, 0]]
+        return sums[0, 0] / norm[0] * cls_weight, sums[0, 1] / norm[2].clamp(min=1e-30) * box_weight, \
+            sums[1, 0] / norm[1] * ctr_weight
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_cls, g_box, g_ctr):
+        hw, st, L, B, C = ctx.meta
+        if getattr(ctx, 'scaled', False):
+            raise RuntimeError('fcos_loss: a second backward through the same forward (retain_graph=True) is not supported: '
+                               'the gradient maps were handed over and scaled in place by the first')
+        ctx.scaled = True
+        grads = ctx.saved_tensors
+        gct, gcs = _fcos_tables(grads[:L])
+        grt, grs = _fcos_tables(grads[L:2 * L])
+        gtt, gts_ = _fcos_tables(grads[2 * L:])
+        capi.call('htd_fcos_grad_scale', gct, gcs, grt, grs, gtt, gts_, hw, st, L, B, C, _P(g_cls.float().contiguous()),
+                  _P(g_box.float().contiguous()), _P(g_ctr.float().contiguous()), _S())
+        return (None, ) * 15 + tuple(grads)
+
+
+def fcos_loss(cls_maps, reg_maps, ctr_maps, strides, gt_labels, assigned, bbox_targets, ctr_targets, norm, box_kind, eps=1e-6,
+              gamma=2.0, alpha=0.25, cls_weight=1.0, box_weight=1.0, ctr_weight=1.0):
+    """-> (loss_cls, loss_bbox, loss_centerness) of an FCOS head from its per-level (B, C, h, w) / (B, 4, h, w) / (B, 1, h, w)
+    maps and the outputs of fcos_targets.  box_kind: FCOS_BOX_KINDS[type of the box loss]."""
+    _need_gpu(assigned, 'fcos_loss')
+    for m in list(cls_maps) + list(reg_maps) + list(ctr_maps):
+        _f32(m, 'fcos_loss')
+    hw, st, P = _fcos_levels([m.shape[-2:] for m in cls_maps], strides)
+    if assigned.shape != (cls_maps[0].size(0), P) or assigned.dtype != torch.int32:
+        raise ValueError(f'fcos_loss: assigned must be int32 of shape {(cls_maps[0].size(0), P)}')
+    return FcosLossFunction.apply(hw, st, cls_maps[0].size(1), gt_labels.contiguous(), assigned.contiguous(),
+                                  bbox_targets.contiguous(), ctr_targets.contiguous(), norm, box_kind, eps, gamma, alpha,
+                                  cls_weight, box_weight, ctr_weight, *cls_maps, *reg_maps, *ctr_maps)
+
+
+def fcos_keys(cls_maps, ctr_maps, strides):
+    """(B, P) max_c sigmoid(cls) * sigmoid(centerness) of every point of every level (level-major), one launch (htd_fcos_keys)."""
+    _need_gpu(cls_maps[0], 'fcos_keys')
+    for m in list(cls_maps) + list(ctr_maps):
+        _f32(m, 'fcos_keys')
+    hw, st, P = _fcos_levels([m.shape[-2:] for m in cls_maps], strides)
+    ct, cs = _fcos_tables(cls_maps)
+    tt, ts = _fcos_tables(ctr_maps)
+    B = cls_maps[0].size(0)
+    keys = torch.empty(B, P, device=cls_maps[0].device, dtype=torch.float32)
+    capi.call('htd_fcos_keys', ct, cs, tt, ts, hw, st, len(cls_maps), B, cls_maps[0].size(1), _P(keys), _S())
+    return keys

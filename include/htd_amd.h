@@ -675,6 +675,57 @@ int htd_retina_grad_scale(float *const *grad_cls, const int64_t *cls_stride, flo
 int htd_retina_keys(const float *const *cls, const int64_t *cls_stride, const int64_t *pix, int L, int B, int na, int C,
                     float *keys, void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * FCOS head (dense_heads/fcos_head.py).  The pyramid is given as HOST tables of L <= 8 levels: hw [L][2] = map height and
+ * width, strides [L]; point p of a level is (x, y) = (p % w, p / w) * stride + stride / 2 (get_points,
+ * fcos_head.py:403-413), computed in the kernels: there is no points tensor.  P = sum of h * w; points are level-major.
+ * Maps are HOST tables of L device pointers to channels_last maps [B][h * w][channel stride] read in place (possibly channel
+ * slices of wider maps): classification (C channels), regression (4: l, t, r, b) and centerness (1).
+ * ---------------------------------------------------------------------------------- */
+/* FCOSHead.get_targets / _get_target_single (fcos_head.py:415-558) and centerness_target (:560-576) of the whole batch in one
+ * launch, in the reference's fp32 arithmetic.  ranges [L][2] HOST = regress_ranges; gts [B][K][4] and gt_valid [B][K] padded
+ * as pad_gt_batch leaves them (any K > 0).  A point is a candidate of gt k when min(l, t, r, b) > 0 (center_sampling: against
+ * the gt's centre box of half-width stride * radius clipped to the gt) and ranges[l][0] <= max(l, t, r, b) <= ranges[l][1];
+ * the candidate of the smallest area (x2 - x1) * (y2 - y1) wins, equal areas go to the lower index.
+ *   assigned [B][P]       0 = background, k + 1 = gt k
+ *   bbox_targets [B][P][4] l, t, r, b to the chosen gt (background: to the first gt of the image, as the reference; no gt:
+ *                         zeros), divided by the level's stride when norm_on_bbox
+ *   ctr_targets [B][P]    sqrt(min(l, r) / max(l, r) * min(t, b) / max(t, b)) of the stored targets, 0 on background
+ *   num_pos [B], norm [3] = {sum num_pos + B, max(sum num_pos, 1), sum of ctr_targets}: the three averaging factors of
+ *                         FCOSHead.loss (:224-245), left on the device in a fixed summation order: no host read.
+ * workspace: htd_fcos_targets_workspace_bytes(B, P) bytes, 8-byte aligned.  Every output element is written. */
+int64_t htd_fcos_targets_workspace_bytes(int B, int64_t P);
+int htd_fcos_targets(const int64_t *hw, const int64_t *strides, const float *ranges, int L, const float *gts,
+                     const uint8_t *gt_valid, int B, int K, int center_sampling, double radius, int norm_on_bbox,
+                     int *assigned, float *bbox_targets, float *ctr_targets, void *workspace, int *num_pos, float *norm,
+                     void *stream);
+/* FCOSHead.loss (fcos_head.py:159-253) over all levels in one launch: the focal loss of every point with the label
+ * gt_labels[b][assigned - 1] (background: none), and per positive point the box loss of distance2bbox(point, bbox_pred)
+ * against distance2bbox(point, bbox_target) -- box_kind 0 = IoULoss in the reference's own form (losses/iou_loss.py:11-31),
+ * 2 = GIoULoss (:78-109), eps theirs -- weighted by ctr_targets, and BCE-with-logits of the centerness against ctr_targets.
+ * partial [htd_fcos_loss_partial_rows()][2]: rows 0 .. n/2 - 1 = per-block {sum focal, sum weighted box loss}, rows n/2 .. =
+ * {sum centerness BCE, 0}, unscaled (add in row order: reproducible).  The gradient maps (layout of their inputs) receive
+ * d(cls_weight * focal / norm[0]), d(box_weight * box / norm[2]) and d(ctr_weight * bce / norm[1]); every element is written
+ * exactly once, zeros (padding channels, non-positive points) included.  Without positives the box and centerness sums and
+ * gradients are exactly 0, the reference's `pos_bbox_preds.sum()` branch (:246-248). */
+int htd_fcos_loss_partial_rows(void);
+int htd_fcos_loss(const float *const *cls, const int64_t *cls_stride, const float *const *reg, const int64_t *reg_stride,
+                  const float *const *ctr, const int64_t *ctr_stride, const int64_t *hw, const int64_t *strides, int L,
+                  int B, int C, const int64_t *gt_labels, int K, const int *assigned, const float *bbox_targets,
+                  const float *ctr_targets, const float *norm, int box_kind, double eps, float gamma, float alpha,
+                  float cls_weight, float box_weight, float ctr_weight, float *partial, float *const *grad_cls,
+                  float *const *grad_reg, float *const *grad_ctr, void *stream);
+/* The gradient maps of htd_fcos_loss times the incoming gradients *g_cls / *g_box / *g_ctr (device scalars), in place; a factor
+ * of exactly 1 leaves its maps untouched, decided on the device. */
+int htd_fcos_grad_scale(float *const *grad_cls, const int64_t *cls_stride, float *const *grad_reg,
+                        const int64_t *reg_stride, float *const *grad_ctr, const int64_t *ctr_stride, const int64_t *hw,
+                        const int64_t *strides, int L, int B, int C, const float *g_cls, const float *g_box,
+                        const float *g_ctr, void *stream);
+/* keys [B][P] = max_c sigmoid(cls) * sigmoid(centerness) of every point of every level in one launch: what
+ * FCOSHead._get_bboxes_single (fcos_head.py:364-372) ranks the nms_pre cut by. */
+int htd_fcos_keys(const float *const *cls, const int64_t *cls_stride, const float *const *ctr, const int64_t *ctr_stride,
+                  const int64_t *hw, const int64_t *strides, int L, int B, int C, float *keys, void *stream);
+
 /* nn.MaxPool2d(kernel, stride, padding) of the ResNet stem (backbones/resnet.py:509,629) on NHWC maps
  * x [B][H][W][C] -> y [B][Ho][Wo][C], C % 4 == 0, padding = -inf, floor mode.  idx (may be NULL for inference; int32
  * [B][Ho][Wo][C]) records the input pixel hi*W+wi of the first maximum of each window; bwd sends the gradient there
