@@ -70,6 +70,18 @@ __device__ __forceinline__ void axis_span(float start, float bin, int bin_idx, i
     hi = min((int)c1 + 1, extent - 1);
 }
 
+// Pixel span [lo, hi] touched by all `bins` bins of a RoI along one axis; false: a bin without samples (grid <= 0).  Bin 0 is the
+// far end of a reversed RoI (bin < 0: aligned = 1 with a fixed sampling_ratio samples it like any other), hence the min / max.
+__device__ __forceinline__ bool roi_span(float start, float bin, int bins, int grid, int extent, int &lo, int &hi)
+{
+    int lo0, hi0, lo1, hi1;
+    axis_span(start, bin, 0, grid, extent, lo0, hi0);
+    axis_span(start, bin, bins - 1, grid, extent, lo1, hi1);
+    lo = min(lo0, lo1);
+    hi = max(hi0, hi1);
+    return lo0 <= hi0 && lo1 <= hi1;
+}
+
 __device__ __forceinline__ float lane_bcast(float v, int src)
 {
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), src));
@@ -381,7 +393,7 @@ __global__ __launch_bounds__(WAVES == 1 ? 256 : 64 * WAVES) void roi_align_all_l
 // columns with  gfeat[r][c][:] += sum_q Wx[q][c] * T[q][:]:  ONE atomic per footprint pixel and channel.  The bin-wise
 // form above issues one per (bin, pixel of the bin's span), i.e. about twice as many, because neighbouring bins'
 // bilinear spans overlap -- and the 1.3 TB/s float-atomic rate is what bounds this kernel.
-constexpr int MAXP = 8;
+constexpr int MAXP = 8;              // R.MAXP of tests/roi_align_ref.py: larger outputs take the bin-wise scatter, the gather rejects them
 
 __global__ __launch_bounds__(256) void roi_align_bwd_rows_kernel(const float *__restrict__ gout,
                                                                  const float *__restrict__ rois,
@@ -401,13 +413,9 @@ __global__ __launch_bounds__(256) void roi_align_bwd_rows_kernel(const float *__
     if (roi_level && roi_level[ri] != (int64_t)level) return;  // wave-uniform
     const RoiGeom g = roi_geometry(rois + 5 * ri, scale, ph, pw, sampling_ratio, aligned);
     if (g.batch < 0 || g.batch >= B) return;
-    int r_lo, r_hi, c_lo, c_hi, t0, t1;
-    axis_span(g.start_h, g.bin_h, 0, g.grid_h, H, r_lo, t0);
-    axis_span(g.start_h, g.bin_h, ph - 1, g.grid_h, H, t1, r_hi);
-    if (t0 < r_lo || r_hi < t1) return;                          // empty spans (degenerate RoI)
-    axis_span(g.start_w, g.bin_w, 0, g.grid_w, W, c_lo, t0);
-    axis_span(g.start_w, g.bin_w, pw - 1, g.grid_w, W, t1, c_hi);
-    if (t0 < c_lo || c_hi < t1) return;
+    int r_lo, r_hi, c_lo, c_hi;
+    if (!roi_span(g.start_h, g.bin_h, ph, g.grid_h, H, r_lo, r_hi)) return;   // empty spans (degenerate RoI)
+    if (!roi_span(g.start_w, g.bin_w, pw, g.grid_w, W, c_lo, c_hi)) return;
     const size_t img_base = (size_t)g.batch * H * W * C;
     const float *go = gout + (size_t)ri * ph * pw * C + chunk * 256 + lane;
     bool chk[4];
@@ -486,13 +494,9 @@ __global__ __launch_bounds__(256) void roi_bbox_kernel(const float *__restrict__
     o.b = -1;
     if (!roi_level || roi_level[ri] == (int64_t)level) {
         const RoiGeom g = roi_geometry(rois + 5 * ri, scale, ph, pw, sampling_ratio, aligned);
-        int r_lo, r_hi, c_lo, c_hi, t0, t1;
-        axis_span(g.start_h, g.bin_h, 0, g.grid_h, H, r_lo, t0);
-        axis_span(g.start_h, g.bin_h, ph - 1, g.grid_h, H, t1, r_hi);
-        bool ok = g.batch >= 0 && g.batch < B && !(t0 < r_lo || r_hi < t1);
-        axis_span(g.start_w, g.bin_w, 0, g.grid_w, W, c_lo, t0);
-        axis_span(g.start_w, g.bin_w, pw - 1, g.grid_w, W, t1, c_hi);
-        ok = ok && !(t0 < c_lo || c_hi < t1);
+        int r_lo, r_hi, c_lo, c_hi;
+        bool ok = g.batch >= 0 && g.batch < B && roi_span(g.start_h, g.bin_h, ph, g.grid_h, H, r_lo, r_hi);
+        ok = roi_span(g.start_w, g.bin_w, pw, g.grid_w, W, c_lo, c_hi) && ok;
         if (ok) { o.b = (short)g.batch; o.r_lo = (short)r_lo; o.r_hi = (short)r_hi; o.c_lo = (short)c_lo; o.c_hi = (short)c_hi; }
     }
     box[ri] = o;
@@ -705,7 +709,7 @@ __global__ __launch_bounds__(256, (RS > 1 ? 4 : 1)) void roi_align_bwd_gather_ke
 // strips for 5 120 wavefront slots, and each of them walks ~50 large RoIs one after the other (a few microseconds of
 // dependent latency per RoI) while the rest of the chip idles; P2 then runs alone, 33 600 short strips.  With the levels in
 // one grid -- coarsest first, so the long chains start at once -- the fine levels' strips fill the idle slots.
-constexpr int GL_MAX = 6;
+constexpr int GL_MAX = 6;            // R.GL_MAX of tests/roi_align_ref.py (the gather entry points reject L = 7 in tests/test_gpu_roi_align_ops.py)
 struct GatherLevels {
     float *gfeat[GL_MAX];
     const float *gout[GL_MAX];       // per slot (BA: every level has its own pooled tensor); NULL: the launch's shared grad_out
@@ -796,13 +800,9 @@ __global__ __launch_bounds__(256) void roi_bbox_levels_kernel(const float *__res
     o.b = -1;
     if (!roi_level || roi_level[ri] == (int64_t)t.level[k]) {       // no level list: every RoI on every level (BA)
         const RoiGeom g = roi_geometry(rois + 5 * ri, t.scale[k], ph, pw, sampling_ratio, aligned);
-        int r_lo, r_hi, c_lo, c_hi, t0, t1;
-        axis_span(g.start_h, g.bin_h, 0, g.grid_h, H, r_lo, t0);
-        axis_span(g.start_h, g.bin_h, ph - 1, g.grid_h, H, t1, r_hi);
-        bool ok = g.batch >= 0 && g.batch < B && !(t0 < r_lo || r_hi < t1);
-        axis_span(g.start_w, g.bin_w, 0, g.grid_w, W, c_lo, t0);
-        axis_span(g.start_w, g.bin_w, pw - 1, g.grid_w, W, t1, c_hi);
-        ok = ok && !(t0 < c_lo || c_hi < t1);
+        int r_lo, r_hi, c_lo, c_hi;
+        bool ok = g.batch >= 0 && g.batch < B && roi_span(g.start_h, g.bin_h, ph, g.grid_h, H, r_lo, r_hi);
+        ok = roi_span(g.start_w, g.bin_w, pw, g.grid_w, W, c_lo, c_hi) && ok;
         if (ok) { o.b = (short)g.batch; o.r_lo = (short)r_lo; o.r_hi = (short)r_hi; o.c_lo = (short)c_lo; o.c_hi = (short)c_hi; }
     }
     const_cast<RoiBox *>(t.box[k])[ri] = o;
@@ -815,6 +815,7 @@ __global__ __launch_bounds__(256) void roi_bbox_levels_kernel(const float *__res
 // all RoIs of their image: the split shortens exactly that chain).  So: 2 when every RoI sits on every level, else 1.
 int gather_split(int64_t n, int64_t tiles_min, bool every_level)
 {
+    // 2 without a level list, else 1, 4 only when forced: restated in tests/roi_align_ref.py, held by tests/test_roi_align_ref.py::test_cases_select_every_kernel_form
     static const int forced = getenv("HTD_ROI_BWD_SPLIT") ? atoi(getenv("HTD_ROI_BWD_SPLIT")) : 0;
     if (forced == 1 || forced == 2 || forced == 4) return forced;
     (void)n; (void)tiles_min;
@@ -835,6 +836,7 @@ int launch(bool backward, const float *in, const float *rois, const int64_t *roi
     hipStream_t s = (hipStream_t)stream;
     // few RoIs (BA: two dozen large ones on every level): the bin-wise kernel has 49 waves per RoI to spread a large
     // footprint over; many RoIs: the row-wise kernel halves the atomics
+    // 256, and row_slots below (8 slots stride a taller map from n * chunks = 2048): R.bwd_form, held by tests/test_roi_align_ref.py::test_cases_select_every_kernel_form
     if (backward && ph <= MAXP && pw <= MAXP && n * chunks >= 256) {
         const int row_slots = (int)std::min<int64_t>(H, std::max<int64_t>(8, htd::ceil_div(16384, n * chunks)));   // >= 16k waves
         const int64_t tasks = n * row_slots * chunks;
@@ -845,6 +847,7 @@ int launch(bool backward, const float *in, const float *rois, const int64_t *roi
         return htd::check_launch("roi_align");
     }
     const int64_t tasks = n * ph * pw * chunks;
+    // 8192: R.fwd_form of tests/roi_align_ref.py, held by tests/test_roi_align_ref.py::test_cases_select_every_kernel_form
     if (!backward && tasks < 8192) {        // too few bins to fill the chip with one wavefront each: a workgroup per bin
         hipLaunchKernelGGL(roi_align_fwd_split_kernel<8>, dim3((unsigned)tasks), dim3(512), 0, s, in, rois, roi_level, level, out, B,
                            C, H, W, ph, pw, scale, sr, aligned, chunks);
@@ -935,6 +938,7 @@ extern "C" int htd_roi_align_all_levels_fwd(const float *const *feats, const int
     const int64_t tasks = (int64_t)L * n * ph * pw * chunks;
     HTD_REQUIRE(tasks < (1ll << 31), "roi_align_all_levels: too many tasks");
     hipStream_t s = (hipStream_t)stream;
+    // 4 * 8192: R.all_fwd_form of tests/roi_align_ref.py, held by tests/test_roi_align_ref.py::test_cases_select_every_kernel_form
     if (tasks < 4 * 8192)           // few bins (as htd_roi_align_fwd per level): a workgroup per bin
         hipLaunchKernelGGL(roi_align_all_levels_fwd_kernel<8>, dim3((unsigned)tasks), dim3(512), 0, s, tab, o, rois, n, B, C, L, ph, pw,
                            sampling_ratio, aligned, chunks, tasks);
