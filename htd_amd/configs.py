@@ -6,7 +6,8 @@ load unchanged through `htd_amd.Config.fromfile` (same `type=` names and kwargs)
 The two baselines HTD is measured against come the same way: faster_rcnn_config (configs/faster_rcnn/
 faster_rcnn_r50_fpn_1x_coco.py) and cascade_rcnn_config (configs/cascade_rcnn/cascade_rcnn_r50_fpn_1x_coco.py), with
 their `_base_` chains merged, and so do the single-stage baselines retinanet_config (configs/retinanet/
-retinanet_r50_fpn_1x_coco.py) and fcos_config (the two configs/fcos/fcos_*_r50_caffe_fpn_gn-head_4x4_1x_coco.py).
+retinanet_r50_fpn_1x_coco.py), its GHM variant retinanet_ghm_config (configs/ghm/retinanet_ghm_r50_fpn_1x_coco.py) and
+fcos_config (the two configs/fcos/fcos_*_r50_caffe_fpn_gn-head_4x4_1x_coco.py).
 """
 import copy
 
@@ -181,6 +182,26 @@ def retinanet_config(depth=50):
     cfg.test_cfg = ConfigDict(nms_pre=1000, min_bbox_size=0, score_thr=0.05, nms=dict(type='nms', iou_threshold=0.5),
                               max_per_img=100)
     cfg.optimizer.lr = 0.01
+    return cfg
+
+
+def retinanet_ghm_model(depth=50):
+    """configs/ghm/retinanet_ghm_r{depth}_fpn_1x_coco.py: retinanet_model with GHMC (30 bins, momentum 0.75) in place of the focal
+    loss and GHMR (mu 0.02, 10 bins, momentum 0.7, weight 10) in place of L1."""
+    model = retinanet_model(depth)
+    model['bbox_head'].update(
+        loss_cls=dict(type='GHMC', bins=30, momentum=0.75, use_sigmoid=True, loss_weight=1.0),
+        loss_bbox=dict(type='GHMR', mu=0.02, bins=10, momentum=0.7, loss_weight=10.0))
+    return model
+
+
+def retinanet_ghm_config(depth=50):
+    """retinanet_ghm_r{depth}_fpn_1x_coco: retinanet_config with the GHM model and gradients clipped at norm 35.
+    (`python -m htd_amd.train` refuses grad_clip: apis.check_supported; Trainer.train_step and `python -m htd_amd.test` take the
+    config as it is.)"""
+    cfg = retinanet_config(depth)
+    cfg.model = ConfigDict(retinanet_ghm_model(depth))
+    cfg.optimizer_config = ConfigDict(grad_clip=dict(max_norm=35, norm_type=2))
     return cfg
 
 
@@ -361,3 +382,8 @@ def build_retinanet_detector(depth=50, cfg=None, bf16=False):
     reference's config dropped.  The single-stage baseline has a builder of its own: the kinds of build_baseline_detector are
     the two-stage ones."""
     return build_baseline_detector(cfg=retinanet_config(depth) if cfg is None else cfg, bf16=bf16)
+
+
+def build_retinanet_ghm_detector(depth=50, cfg=None, bf16=False):
+    """The detector of retinanet_ghm_config(depth) (or of `cfg`); build_retinanet_detector with that config gives the same."""
+    return build_baseline_detector(cfg=retinanet_ghm_config(depth) if cfg is None else cfg, bf16=bf16)

@@ -16,13 +16,16 @@ COMMON = ['--offload-arch=' + ARCH, '-O3', '-fPIC', '-std=c++17', '-Wall', '-Wno
 # per-file extra flags: NMS keeps the CPU path's unfused arithmetic (bit-exact keep sets)
 EXTRA = {'nms.hip': ['-ffp-contract=off'], 'box_ops.hip': ['-ffp-contract=off'],
          'image_pipeline.hip': ['-ffp-contract=off'], 'coco_eval.hip': ['-ffp-contract=off'],
-         'voc_eval.hip': ['-ffp-contract=off'], 'fcos.hip': ['-ffp-contract=off']}
+         'voc_eval.hip': ['-ffp-contract=off'], 'fcos.hip': ['-ffp-contract=off'],
+         'ghm_loss.hip': ['-ffp-contract=off']}     # its two passes must bin an element alike
 
 
 # Every *.hip / *.cpp of this directory is a translation unit of the library; what each one replaces (include/htd_amd.h cites
 # the reference interface per entry point):
 #   focal_loss.hip   mmcv.ops.sigmoid_focal_loss (mmdet/models/losses/focal_loss.py:10-87) and AnchorHead.loss of a head without
 #                    sampling over all pyramid levels (dense_heads/anchor_head.py:172-269,288-291,373-488, retina_head.py)
+#   ghm_loss.hip     GHMC / GHMR (mmdet/models/losses/ghm_loss.py:20-172) and AnchorHead.loss with the pair (the level table
+#                    of focal_loss.hip, shared through retina_levels.h)
 #   fcos.hip         FCOSHead's targets, loss and ranking keys (dense_heads/fcos_head.py:159-253,364-372,415-576)
 def sources():
     return sorted(f for f in os.listdir(HERE) if f.endswith('.hip') or f.endswith('.cpp'))

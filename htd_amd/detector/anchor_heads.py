@@ -11,9 +11,10 @@ anchor-free heads share: `_anchors_inside`, the RPN's proposal constants and the
 
 `loss` has two forms, like RPNHead.loss.  The tensor form follows the reference's order of operations (per image targets, per
 level losses) and works with any loss modules, `reg_decoded_bbox`, ignore boxes and on the CPU.  The fused form -- FocalLoss with
-L1Loss / SmoothL1Loss on delta targets, no ignore boxes, fp32 GPU tensors -- assigns the whole batch against the shared anchors
-(htd_max_iou_assign), counts the positives on the device (htd_retina_avg_factor) and takes both losses and both gradients of all
-levels in one launch (htd_retina_loss) that reads the convolution outputs where they are: no labels / label_weights /
+L1Loss / SmoothL1Loss, or GHMC with GHMR, on delta targets, no ignore boxes, fp32 GPU tensors -- assigns the whole batch against
+the shared anchors (htd_max_iou_assign), counts the positives on the device (htd_retina_avg_factor) and takes both losses and
+both gradients of all levels in one launch (htd_retina_loss; htd_ghm_head_loss is three: histogram, weights, loss) that reads
+the convolution outputs where they are: no labels / label_weights /
 bbox_targets / bbox_weights tensors, no permute or concatenation of the logits, no host read.
 
 `get_bboxes` handles the whole batch: one key launch (htd_retina_keys) and one segmented top-k give every (image, level) cut
@@ -32,6 +33,7 @@ from .. import mmcv_ops as M
 from ..registry import HEADS, build_anchor_generator, build_assigner, build_bbox_coder, build_loss, build_sampler
 from .base_dense_head import BaseDenseHead
 from .bricks import Conv2d, ConvModule, normal_init
+from .losses import GHM_KERNEL_BINS, GHMC, GHMR
 
 RETINA_FUSED = os.environ.get('HTD_RETINA_FUSED', '1') != '0'       # 0: the tensor-path loss (A/B runs)
 
@@ -197,16 +199,24 @@ class AnchorHead(BaseDenseHead):
         return dict(loss_cls=losses_cls, loss_bbox=losses_bbox)
 
     def _fused_loss_ok(self, cls_scores, bbox_preds, gt_bboxes, gt_labels, gt_bboxes_ignore):
-        """htd_retina_loss covers FocalLoss + L1Loss / SmoothL1Loss on delta targets without ignore boxes, fp32 on the GPU."""
+        """htd_retina_loss covers FocalLoss + L1Loss / SmoothL1Loss on delta targets without ignore boxes, fp32 on the GPU;
+        htd_ghm_head_loss covers GHMC + GHMR (at most 64 bins each) under the same conditions.  Any other pair, mixed ones such
+        as GHMC + L1Loss included, takes the tensor path."""
         lc, lb = self.loss_cls, self.loss_bbox
         a = getattr(self, 'assigner', None)
+        focal = type(lc).__name__ == 'FocalLoss' and lc.reduction == 'mean' and \
+            type(lb).__name__ in ('SmoothL1Loss', 'L1Loss') and lb.reduction == 'mean'
         return getattr(self, 'fused_loss', RETINA_FUSED) and gt_labels is not None and gt_bboxes_ignore is None and \
-            type(lc).__name__ == 'FocalLoss' and lc.reduction == 'mean' and \
-            type(lb).__name__ in ('SmoothL1Loss', 'L1Loss') and lb.reduction == 'mean' and not self.reg_decoded_bbox and \
+            (focal or self._ghm_pair()) and not self.reg_decoded_bbox and \
             type(a).__name__ == 'MaxIoUAssigner' and a.ignore_iof_thr <= 0 and isinstance(a.neg_iou_thr, float) and \
             (a.gt_max_assign_all or not a.match_low_quality) and len(cls_scores) <= 8 and \
             all(t.is_cuda and t.dtype == torch.float32 and M.nhwc_channel_stride(t) is not None
                 for t in list(cls_scores) + list(bbox_preds))       # (other layouts, e.g. NCHW-contiguous maps: the tensor path)
+
+    def _ghm_pair(self):
+        lc, lb = self.loss_cls, self.loss_bbox
+        return type(lc) is GHMC and type(lb) is GHMR and lc.bins <= GHM_KERNEL_BINS and lb.bins <= GHM_KERNEL_BINS and \
+            lc.edges.is_cuda and lb.edges.is_cuda
 
     # ------------------------------------------------------------------ constants of the map shapes
     def _anchors_inside(self, featmap_sizes, img_metas, dev):
@@ -243,6 +253,13 @@ class AnchorHead(BaseDenseHead):
         flat_anchors, inside = self._anchors_inside(featmap_sizes, img_metas, dev)
         gts, gt_valid, labels = pad_gt_batch(gt_bboxes, gt_labels)
         assigned, _ = batched_max_iou_assign(self.assigner, flat_anchors, inside, gts, gt_valid)
+        if self._ghm_pair():
+            # GHM takes its own normalisers (per level: the valid elements, the weight sum): no avg_factor
+            self._last_assigned = (assigned, None, None)
+            loss_cls, loss_bbox = M.ghm_head_loss(
+                cls_scores, bbox_preds, self.num_anchors, self.cls_out_channels, flat_anchors, gts, labels, assigned,
+                tuple(self.bbox_coder.means), tuple(self.bbox_coder.stds), self.loss_cls, self.loss_bbox)
+            return dict(loss_cls=[loss_cls], loss_bbox=[loss_bbox])
         num_pos, avg = M.retina_avg_factor(assigned)
         self._last_assigned = (assigned, num_pos, avg)          # exposed for tests
         lb = self.loss_bbox

@@ -1,8 +1,8 @@
 """Losses of the HTD path: CrossEntropyLoss (softmax / sigmoid), SmoothL1Loss, L1Loss, the IoU family on decoded boxes
-(IoULoss, BoundedIoULoss, GIoULoss, DIoULoss, CIoULoss), FocalLoss, accuracy.
+(IoULoss, BoundedIoULoss, GIoULoss, DIoULoss, CIoULoss), FocalLoss, GHMC, GHMR, accuracy.
 Reference: mmdet/models/losses/{cross_entropy_loss.py:9-202, smooth_l1_loss.py:8-136, iou_loss.py:11-418,
-utils.py:26-52, focal_loss.py:10-157, accuracy.py:4-48}.  Same constructor kwargs and forward signature (weight, avg_factor,
-reduction_override)."""
+utils.py:26-52, focal_loss.py:10-157, ghm_loss.py:8-172, accuracy.py:4-48}.  Same constructor kwargs and forward signature
+(weight, avg_factor, reduction_override; the GHM pair has the reference's own, ghm_loss.py:50, :127)."""
 import math
 
 import torch
@@ -282,6 +282,103 @@ class FocalLoss(nn.Module):
         reduction = reduction_override if reduction_override else self.reduction
         return self.loss_weight * sigmoid_focal_loss(pred, target, weight, gamma=self.gamma, alpha=self.alpha,
                                                      reduction=reduction, avg_factor=avg_factor)
+
+
+# ---------------------------------------------------------------- gradient harmonising losses (ghm_loss.py:8-172)
+GHM_KERNEL_BINS = 64            # bins the kernels of csrc/ghm_loss.hip take
+
+
+def _expand_onehot_labels(labels, label_weights, label_channels):
+    """ghm_loss.py:8-16 without its nonzero(): (N,) class indices -> (N, C) binary targets (an index outside 0 .. C - 1, the
+    background, gives an all-zero row) and the (N,) weights repeated along the classes."""
+    onehot = labels.view(-1, 1) == torch.arange(label_channels, device=labels.device).view(1, -1)
+    return onehot.to(labels.dtype), label_weights.view(-1, 1).expand(label_weights.size(0), label_channels)
+
+
+def _ghm_weights(g, valid, tot, edges, bins, momentum, acc_sum):
+    """The element weights of both GHM losses (ghm_loss.py:70-90, :151-168) without a host read: the bin of every valid
+    element from the fp32 `edges` (edges[i] <= g < edges[i + 1]), integer bin counts, the moving average in the reference's
+    own arithmetic -- fp32 `mmt * acc_sum[i]` plus the double `(1 - mmt) * num` rounded to fp32 -- applied to the filled bins
+    only, and tot / acc / n per bin (tot / num with momentum 0, formed in double as the reference's Python floats are).
+    tot: 0-dim float64 tensor, already clamped to >= 1.  -> (weights like g, counts (bins,) int64, n 0-dim int64)."""
+    idx = torch.bucketize(g, edges.to(g.dtype), right=True) - 1
+    idx = torch.where(valid & (idx >= 0) & (idx < bins), idx, torch.full_like(idx, bins))      # `bins`: in no bin
+    counts = torch.stack([(idx == i).sum() for i in range(bins)])
+    filled = counts > 0
+    n = filled.sum()
+    if momentum > 0:
+        moved = momentum * acc_sum + ((1 - momentum) * counts.double()).float()
+        acc_sum.copy_(torch.where(filled, moved, acc_sum))
+        per_bin = (acc_sum.reciprocal() * tot.float()).to(g.dtype)         # `tot / tensor` is reciprocal() * tot in torch
+    else:
+        per_bin = (tot / counts.double().clamp(min=1)).to(g.dtype)
+    per_bin = torch.where(filled, per_bin, torch.zeros_like(per_bin)) / n.clamp(min=1)
+    return torch.cat([per_bin, per_bin.new_zeros(1)])[idx], counts, n
+
+
+@LOSSES.register_module()
+class GHMC(nn.Module):
+    """ghm_loss.py:20-94.  forward(pred (N, C) logits, target (N,) class indices or (N, C) binary, label_weight (N,) or
+    (N, C): an element is valid where its weight is > 0).  `avg_factor` and any further argument are ignored, as there.
+    An fp32 GPU matrix with (N,) labels and (N,) weights goes through htd_ghmc_loss (bins <= 64); everything else through
+    the tensor formulation, which reads nothing back to the host either.  `last` keeps (counts, tot, n) of the latest call."""
+
+    def __init__(self, bins=10, momentum=0, use_sigmoid=True, loss_weight=1.0):
+        super().__init__()
+        self.bins, self.momentum = bins, momentum
+        edges = torch.arange(bins + 1).float() / bins
+        edges[-1] += 1e-6
+        self.register_buffer('edges', edges)
+        if momentum > 0:
+            self.register_buffer('acc_sum', torch.zeros(bins))
+        self.use_sigmoid = use_sigmoid
+        if not self.use_sigmoid:
+            raise NotImplementedError
+        self.loss_weight = loss_weight
+
+    def forward(self, pred, target, label_weight, *args, **kwargs):
+        if pred.dim() != target.dim() and pred.is_cuda and pred.dtype == torch.float32 and label_weight.dim() == 1 and \
+                self.bins <= GHM_KERNEL_BINS and self.edges.is_cuda:
+            from .. import mmcv_ops as M
+            return M.ghmc_loss(pred, target, label_weight, self.edges, self.bins, self.momentum,
+                               self.acc_sum if self.momentum > 0 else None, self.loss_weight)
+        if pred.dim() != target.dim():
+            target, label_weight = _expand_onehot_labels(target, label_weight, pred.size(-1))
+        target, label_weight = target.to(pred.dtype), label_weight.float()
+        g = torch.abs(pred.sigmoid().detach() - target)
+        valid = label_weight > 0
+        tot = valid.sum().clamp(min=1).double()
+        weights, counts, n = _ghm_weights(g, valid, tot, self.edges, self.bins, self.momentum, getattr(self, 'acc_sum', None))
+        self.last = (counts, tot, n)
+        loss = F.binary_cross_entropy_with_logits(pred, target, weights, reduction='sum') / tot.to(pred.dtype)
+        return loss * self.loss_weight
+
+
+@LOSSES.register_module()
+class GHMR(nn.Module):
+    """ghm_loss.py:98-172.  forward(pred, target, label_weight, avg_factor=None) on tensors of one shape; tot is the weight
+    sum, `avg_factor` is ignored."""
+
+    def __init__(self, mu=0.02, bins=10, momentum=0, loss_weight=1.0):
+        super().__init__()
+        self.mu, self.bins, self.momentum = mu, bins, momentum
+        edges = torch.arange(bins + 1).float() / bins
+        edges[-1] = 1e3
+        self.register_buffer('edges', edges)
+        if momentum > 0:
+            self.register_buffer('acc_sum', torch.zeros(bins))
+        self.loss_weight = loss_weight
+
+    def forward(self, pred, target, label_weight, avg_factor=None):
+        mu = self.mu
+        diff = pred - target
+        loss = torch.sqrt(diff * diff + mu * mu) - mu
+        g = torch.abs(diff / torch.sqrt(mu * mu + diff * diff)).detach()
+        valid = label_weight > 0
+        tot = label_weight.float().sum().clamp(min=1).double()
+        weights, counts, n = _ghm_weights(g, valid, tot, self.edges, self.bins, self.momentum, getattr(self, 'acc_sum', None))
+        self.last = (counts, tot, n)
+        return (loss * weights).sum() / tot.to(pred.dtype) * self.loss_weight
 
 
 DECODED_BOX_LOSSES = (IoULoss, BoundedIoULoss, GIoULoss, DIoULoss, CIoULoss)       # index = `kind` of htd_roi_head_loss_decoded

@@ -1210,6 +1210,138 @@ def retina_keys(cls_maps, na, C):
     return keys
 
 
+# ====================================================================== GHM losses (mmdet/models/losses/ghm_loss.py)
+GHM_WS_COUNTS, GHM_WS_TOT, GHM_WS_N, GHM_WS_MULT = 0, 1024, 1040, 1056      # word offsets of the workspace (include/htd_amd.h)
+
+
+def ghm_workspace(L, dev):
+    """int32 workspace of the GHM entry points; views of it: ghm_workspace_views."""
+    nbytes = capi.lib().htd_ghm_workspace_bytes(int(L))
+    if nbytes < 0:
+        raise ValueError(f'GHM kernels take 1 .. 8 levels, not {L}')
+    return torch.empty(nbytes // 4, dtype=torch.int32, device=dev)
+
+
+def ghm_workspace_views(ws):
+    """-> counts (2, 8, 64) int32 [loss][level][bin], tot (2, 8) int32, n (2, 8) int32, mult (2, 8, 64) float32."""
+    return (ws[GHM_WS_COUNTS:GHM_WS_TOT].view(2, 8, 64), ws[GHM_WS_TOT:GHM_WS_N].view(2, 8), ws[GHM_WS_N:GHM_WS_MULT].view(2, 8),
+            ws[GHM_WS_MULT:GHM_WS_MULT + 1024].view(torch.float32).view(2, 8, 64))
+
+
+class GHMCLossFunction(Function):
+    """htd_ghmc_loss: histogram, weights and loss + gradient of GHMC.forward in three launches; acc_sum moves in place."""
+
+    @staticmethod
+    def forward(ctx, input, target, weight, edges, bins, momentum, acc_sum, loss_weight):
+        if input.dim() != 2 or target.dim() != 1 or target.size(0) != input.size(0) or target.dtype != torch.int64:
+            raise ValueError('ghmc_loss: input (N, C) float32 and target (N,) int64 expected')
+        if weight.dim() != 1 or weight.size(0) != input.size(0):
+            raise ValueError('ghmc_loss: weight must have one entry per row')
+        _need_gpu(input, 'ghmc_loss')
+        x = _f32(input, 'ghmc_loss').contiguous()
+        N, C = x.shape
+        grad = torch.empty_like(x)
+        ws = ghm_workspace(1, x.device)
+        partial = torch.empty(capi.lib().htd_focal_loss_partial_rows(), 2, device=x.device, dtype=torch.float32)
+        capi.call('htd_ghmc_loss', _P(x), _P(target.contiguous()), _P(weight.float().contiguous()), N, C,
+                  _P(_f32(edges, 'ghmc_loss').contiguous()), int(bins), float(momentum), _P(acc_sum) if momentum > 0 else None,
+                  float(loss_weight), _P(ws), _P(partial), _P(grad), _S())
+        ctx.save_for_backward(grad)
+        ctx.mark_non_differentiable(ws)
+        return partial[:, 0].sum(), ws
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g, _):
+        grad, = ctx.saved_tensors
+        return grad * g, None, None, None, None, None, None, None
+
+
+def ghmc_loss(input, target, weight, edges, bins, momentum=0, acc_sum=None, loss_weight=1.0, return_workspace=False):
+    """GHMC.forward on an fp32 GPU matrix: input (N, C) logits, target (N,) int64 with C = background, weight (N,).  acc_sum
+    (bins,) float32 is updated in place when momentum > 0."""
+    if momentum > 0 and (acc_sum is None or not acc_sum.is_contiguous() or acc_sum.dtype != torch.float32):
+        raise ValueError('ghmc_loss: momentum > 0 needs a contiguous float32 acc_sum')
+    loss, ws = GHMCLossFunction.apply(input, target, weight, edges, bins, momentum, acc_sum, loss_weight)
+    return (loss, ws) if return_workspace else loss
+
+
+class GhmHeadLossFunction(Function):
+    """htd_ghm_head_loss: GHMC + GHMR of an anchor head over every level and image, per-level histograms and weights in the
+    reference's level order, with the finished gradient maps; backward hands them over after htd_retina_grad_scale applies
+    incoming gradients other than 1 in place.  Single use: a second backward through the same forward raises."""
+
+    @staticmethod
+    def forward(ctx, na, C, anchors, gts, gt_labels, assigned, means, stds, ghmc, ghmr, ws, *maps):
+        from .core.bbox import _f4
+        L = len(maps) // 2
+        cls, reg = maps[:L], maps[L:]
+        B, A = assigned.shape
+        K = gts.size(1)
+        ct, cs, pix = _level_tables(cls)
+        rt, rs, _ = _level_tables(reg)
+        dev = assigned.device
+        # the gradient maps take the layout of the maps (slices of wider ones: the padded layout, padding written as zeros)
+        gcls = [torch.empty(m.size(0), s, m.size(2), m.size(3), device=dev, dtype=torch.float32, memory_format=CL)[:, :m.size(1)]
+                for m, s in zip(cls, cs)]
+        greg = [torch.empty(m.size(0), s, m.size(2), m.size(3), device=dev, dtype=torch.float32, memory_format=CL)[:, :m.size(1)]
+                for m, s in zip(reg, rs)]
+        gct, gcs, _ = _level_tables(gcls)
+        grt, grs, _ = _level_tables(greg)
+        assert list(gcs) == list(cs) and list(grs) == list(rs)
+        edges_c, bins_c, mmt_c, acc_c, w_c = ghmc
+        edges_r, bins_r, mmt_r, acc_r, w_r, mu = ghmr
+        partial = torch.empty(capi.lib().htd_focal_loss_partial_rows(), 2, device=dev, dtype=torch.float32)
+        capi.call('htd_ghm_head_loss', ct, cs, rt, rs, pix, L, B, int(na), int(C), _P(anchors), _P(gts), _P(gt_labels), _P(assigned),
+                  A, K, _f4(means), _f4(stds), _P(edges_c), int(bins_c), float(mmt_c), _P(acc_c) if mmt_c > 0 else None,
+                  _P(edges_r), int(bins_r), float(mmt_r), _P(acc_r) if mmt_r > 0 else None, float(mu), float(w_c), float(w_r),
+                  _P(ws), _P(partial), gct, grt, _S())
+        ctx.meta = (int(na), int(C), B, L)
+        ctx.save_for_backward(*gcls, *greg)
+        sums = partial.sum(0)
+        return sums[0], sums[1]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_cls, g_box):
+        na, C, B, L = ctx.meta
+        grads = ctx.saved_tensors
+        gcls, greg = grads[:L], grads[L:]
+        gct, gcs, pix = _level_tables(gcls)
+        grt, grs, _ = _level_tables(greg)
+        if all(s % 4 == 0 for s in gcs):
+            if getattr(ctx, 'scaled', False):
+                raise RuntimeError('ghm_head_loss: a second backward through the same forward (retain_graph=True) is not '
+                                   'supported: the gradient maps were handed over and scaled in place by the first')
+            ctx.scaled = True
+            capi.call('htd_retina_grad_scale', gct, gcs, grt, grs, pix, L, B, na, C, _P(g_cls.float().contiguous()),
+                      _P(g_box.float().contiguous()), _S())
+        else:
+            gcls, greg = [g * g_cls for g in gcls], [g * g_box for g in greg]
+        return (None, ) * 11 + tuple(gcls) + tuple(greg)
+
+
+def ghm_head_loss(cls_maps, reg_maps, na, C, anchors, gts, gt_labels, assigned, means, stds, loss_cls, loss_bbox,
+                  return_workspace=False):
+    """-> (loss_cls, loss_bbox) of an anchor head with the GHMC module loss_cls and the GHMR module loss_bbox from its per-level
+    (B, na * C, h, w) / (B, na * 4, h, w) maps; the modules' acc_sum buffers move in place, L times each in level order."""
+    _need_gpu(assigned, 'ghm_head_loss')
+    for m in list(cls_maps) + list(reg_maps):
+        _f32(m, 'ghm_head_loss')
+    for mod in (loss_cls, loss_bbox):
+        if mod.bins > 64 or not mod.edges.is_cuda or mod.edges.dtype != torch.float32 or not mod.edges.is_contiguous() or \
+                (mod.momentum > 0 and not (mod.acc_sum.is_contiguous() and mod.acc_sum.dtype == torch.float32)):
+            raise ValueError('ghm_head_loss: at most 64 bins, contiguous float32 edges / acc_sum buffers on the GPU')
+    ws = ghm_workspace(len(cls_maps), assigned.device)
+    ghmc = (loss_cls.edges, loss_cls.bins, loss_cls.momentum, loss_cls.acc_sum if loss_cls.momentum > 0 else None,
+            loss_cls.loss_weight)
+    ghmr = (loss_bbox.edges, loss_bbox.bins, loss_bbox.momentum, loss_bbox.acc_sum if loss_bbox.momentum > 0 else None,
+            loss_bbox.loss_weight, loss_bbox.mu)
+    out = GhmHeadLossFunction.apply(na, C, anchors.float().contiguous(), gts.float().contiguous(), gt_labels.contiguous(),
+                                    assigned.contiguous(), means, stds, ghmc, ghmr, ws, *cls_maps, *reg_maps)
+    return (out[0], out[1], ws) if return_workspace else out
+
+
 # ====================================================================== FCOS head (dense_heads/fcos_head.py)
 FCOS_BOX_KINDS = dict(IoULoss=0, GIoULoss=2)          # the `kind` of iou_family_loss (csrc/iou_family.h)
 

@@ -676,6 +676,46 @@ int htd_retina_keys(const float *const *cls, const int64_t *cls_stride, const in
                     float *keys, void *stream);
 
 /* ------------------------------------------------------------------------------------
+ * Gradient harmonising losses (replace mmdet/models/losses/ghm_loss.py: GHMC.forward :50-94, GHMR.forward :127-172, and the
+ * per-level calls of AnchorHead.loss_single, dense_heads/anchor_head.py:373-418, with the pair).  bins <= 64.  edges
+ * [bins + 1] and acc_sum [bins] are the modules' fp32 DEVICE buffers; acc_sum is moved in place (NULL iff momentum == 0).
+ * Each entry point is three launches -- integer histogram, weights, loss + gradient -- and reads nothing back.
+ * workspace: htd_ghm_workspace_bytes(L) bytes (L <= 8, else -1), as 32-bit words afterwards
+ *   counts [2][8][64] int (loss 0 = GHMC, 1 = GHMR; level; bin), tot [2][8] int (valid elements of GHMC, weight sum of
+ *   GHMR, before the max(., 1)), n [2][8] int (filled bins), mult [2][8][64] float = loss_weight / (acc n), 0 for empty bins.
+ * ---------------------------------------------------------------------------------- */
+int64_t htd_ghm_workspace_bytes(int L);
+/* GHMC.forward on logits [N][C], labels [N] int64 (C = background) and weight [N] (an element is valid where weight > 0);
+ * level 0 of the workspace.  partial [htd_focal_loss_partial_rows()][2]: column 0 = per-block sums of the finished loss
+ * (add in row order: reproducible), column 1 = 0; grad [N][C] = its derivative, every element written. */
+int htd_ghmc_loss(const float *logits, const int64_t *labels, const float *weight, int64_t N, int C, const float *edges,
+                  int bins, double momentum, float *acc_sum, float loss_weight, void *workspace, float *partial, float *grad,
+                  void *stream);
+/* AnchorHead.loss with GHMC + GHMR over all L <= 8 levels: tables, anchors, gts, gt_labels, assigned, means4 / stds4, partial
+ * and the gradient maps as in htd_retina_loss (GHM ignores avg_factor and pos_weight; the box targets are bbox2delta formed on
+ * the fly).  The reference calls each loss once per level in level order: histogram, tot and n are per level, and level l's
+ * weights use acc_sum as levels 0 .. l - 1 of this call left it.  partial holds finished losses (loss weights and 1 / tot
+ * included); htd_retina_grad_scale applies incoming gradients to the gradient maps. */
+int htd_ghm_head_loss(const float *const *cls, const int64_t *cls_stride, const float *const *reg, const int64_t *reg_stride,
+                      const int64_t *pix, int L, int B, int na, int C, const float *anchors, const float *gts,
+                      const int64_t *gt_labels, const int64_t *assigned, int A, int K, const float *means4,
+                      const float *stds4, const float *edges_c, int bins_c, double momentum_c, float *acc_sum_c,
+                      const float *edges_r, int bins_r, double momentum_r, float *acc_sum_r, float mu, float cls_weight,
+                      float box_weight, void *workspace, float *partial, float *const *grad_cls, float *const *grad_reg,
+                      void *stream);
+
+/* htd_ghm_head_loss with a choice of its launches, for measurements: bit 0 = histogram (and the clearing of the counts
+ * before it), bit 1 = weights (moves acc_sum), bit 2 = loss + gradient; a launch left out finds the workspace as earlier calls
+ * left it.  launches = 7 is htd_ghm_head_loss. */
+int htd_ghm_head_loss_launches(const float *const *cls, const int64_t *cls_stride, const float *const *reg,
+                               const int64_t *reg_stride, const int64_t *pix, int L, int B, int na, int C, const float *anchors,
+                               const float *gts, const int64_t *gt_labels, const int64_t *assigned, int A, int K,
+                               const float *means4, const float *stds4, const float *edges_c, int bins_c, double momentum_c,
+                               float *acc_sum_c, const float *edges_r, int bins_r, double momentum_r, float *acc_sum_r, float mu,
+                               float cls_weight, float box_weight, void *workspace, float *partial, float *const *grad_cls,
+                               float *const *grad_reg, int launches, void *stream);
+
+/* ------------------------------------------------------------------------------------
  * FCOS head (dense_heads/fcos_head.py).  The pyramid is given as HOST tables of L <= 8 levels: hw [L][2] = map height and
  * width, strides [L]; point p of a level is (x, y) = (p % w, p / w) * stride + stride / 2 (get_points,
  * fcos_head.py:403-413), computed in the kernels: there is no points tensor.  P = sum of h * w; points are level-major.

@@ -1,0 +1,218 @@
+"""GHM without a GPU: GHMC / GHMR against the reference's own run (tests/golden/ghm.npz, written by
+tests/golden/make_golden_ghm.py), their buffers, target forms and empty case, the fp64 restatement the GPU tests use, the
+tensor-path RetinaHead.loss with the pair, the configuration, the state dict, a reference-format checkpoint and the new entry
+points of the C ABI.
+
+GHM is discontinuous in its inputs (an element that crosses a bin edge changes two bin counts), so every seeded input here lies
+1e-4 away from every edge (ghm_util.clear_of_edges; asserted by the generator in fp64): bin counts are compared for equality."""
+import json
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import baselines_util as BU
+import ghm_util as U
+import retina_util as RU
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
+
+
+def T(a):
+    return torch.from_numpy(np.asarray(a))
+
+
+def _module(kind, bins, mmt, **kw):
+    import htd_amd.detector  # noqa: F401
+    from htd_amd.registry import build_loss
+    if kind == 'c':
+        return build_loss(dict(type='GHMC', bins=bins, momentum=mmt, use_sigmoid=True, loss_weight=1.0, **kw))
+    return build_loss(dict(type='GHMR', mu=U.MU, bins=bins, momentum=mmt, loss_weight=1.0, **kw))
+
+
+def _rows(kind, g):
+    if kind == 'c':
+        return [U.ghmc_rows(tag=f'ghm.c{k}') for k in range(3)]
+    return [U.ghmr_rows(tag=f'ghm.r{k}', seed=int(g['r.seed'])) for k in range(3)]
+
+
+@pytest.mark.parametrize('kind', ['c', 'r'])
+@pytest.mark.parametrize('i', range(len(U.GHM_PARAMS)))
+def test_modules_equal_the_reference(golden, i, kind):
+    """Three consecutive calls of one module on different rows: losses in fp64 to 1e-10 and in fp32 to 1e-5 relative, the gradient
+    of the first call in fp64 to 1e-10, bin counts, tot and n equal, acc_sum after every call within rtol 1e-6 (two roundings per
+    update against a contraction of 1 - momentum: about 8 ulp)."""
+    g = golden('ghm')
+    bins, mmt = U.GHM_PARAMS[i]
+    p = f'{kind}.{i}.'
+    for dt, tag, rtol in ((torch.float64, '64', 1e-10), (torch.float32, '32', 1e-5)):
+        mod = _module(kind, bins, mmt)
+        for k, (a, b, w) in enumerate(_rows(kind, g)):
+            pred = a.clone().to(dt).requires_grad_()
+            loss = mod(pred, b, w) if kind == 'c' else mod(pred, b.to(dt), w.to(dt))
+            assert loss.dtype == dt
+            np.testing.assert_allclose(float(loss.detach()), g[p + 'loss' + tag][k], rtol=rtol)
+            counts, tot, n = mod.last
+            assert counts.tolist() == g[p + 'counts'][k].tolist() and float(tot) == g[p + 'tot'][k] and int(n) == g[p + 'n'][k]
+            if mmt > 0:
+                np.testing.assert_allclose(mod.acc_sum.numpy(), g[p + 'acc' + tag][k], rtol=1e-6)
+            if k == 0 and dt == torch.float64:
+                loss.backward()
+                np.testing.assert_allclose(pred.grad.numpy(), g[p + 'grad64'], rtol=1e-10, atol=1e-300)
+
+
+def test_buffers_and_errors():
+    import htd_amd.detector  # noqa: F401
+    from htd_amd.registry import build_loss
+    for kind in ('c', 'r'):
+        m0, m1 = _module(kind, 10, 0), _module(kind, 10, 0.5)
+        assert [k for k, _ in m0.named_buffers()] == ['edges'] and [k for k, _ in m1.named_buffers()] == ['edges', 'acc_sum']
+        assert m1.edges.dtype == torch.float32 and torch.equal(m1.edges, U.edges_of(10, kind))
+        assert torch.equal(m1.acc_sum, torch.zeros(10)) and list(m1.state_dict()) == ['edges', 'acc_sum']
+    assert float(_module('c', 30, 0).edges[-1]) == float(np.float32(1.0) + np.float32(1e-6)) and float(_module('r', 30, 0).edges[-1]) == 1e3
+    with pytest.raises(NotImplementedError):
+        build_loss(dict(type='GHMC', use_sigmoid=False))
+    d = build_loss(dict(type='GHMC'))
+    assert (d.bins, d.momentum, d.loss_weight) == (10, 0, 1.0)
+    d = build_loss(dict(type='GHMR'))
+    assert (d.mu, d.bins, d.momentum, d.loss_weight) == (0.02, 10, 0, 1.0)
+
+
+def test_binary_targets_and_class_indices_agree():
+    pred, labels, weight = U.ghmc_rows(16, 5, tag='ghm.forms')
+    C = pred.size(1)
+    out = []
+    for target, w in ((labels, weight), (RU.onehot(labels, C).long(), weight.view(-1, 1).expand(-1, C)),
+                      (RU.onehot(labels, C).double(), weight.view(-1, 1).expand(-1, C).contiguous())):
+        mod = _module('c', 10, 0.75, )
+        x = pred.double().requires_grad_()
+        loss = mod(x, target, w, avg_factor=123.0)            # avg_factor is ignored
+        loss.backward()
+        out.append((loss.detach(), x.grad, mod.acc_sum.clone()))
+    for o in out[1:]:
+        assert all(torch.equal(a, b) for a, b in zip(out[0], o))
+    assert float(out[0][0]) > 0
+
+
+def test_all_weights_zero():
+    pred, labels, weight = U.ghmc_rows(16, 5, tag='ghm.forms')
+    for kind in ('c', 'r'):
+        mod = _module(kind, 10, 0.75)
+        mod.acc_sum.copy_(torch.arange(10.))
+        if kind == 'c':
+            x = pred.clone().requires_grad_()
+            loss = mod(x, labels, torch.zeros_like(weight))
+        else:
+            a, b, w = U.ghmr_rows(12)
+            x = a.clone().requires_grad_()
+            loss = mod(x, b, torch.zeros_like(w))
+        loss.backward()
+        assert float(loss) == 0.0 and float(x.grad.abs().max()) == 0.0 and torch.equal(mod.acc_sum, torch.arange(10.))
+        assert int(mod.last[2]) == 0 and float(mod.last[1]) == 1.0
+
+
+@pytest.mark.parametrize('kind', ['c', 'r'])
+@pytest.mark.parametrize('i', range(len(U.GHM_PARAMS)))
+def test_fp64_restatement_is_pinned_to_the_reference(golden, i, kind):
+    """ghm_util.ghmc_ref / ghmr_ref (what tests/test_gpu_ghm.py compares the kernels against) equal the reference's fp64 run to
+    1e-10: losses and acc_sum of the three calls, the gradient of the first, counts, tot, n."""
+    g = golden('ghm')
+    bins, mmt = U.GHM_PARAMS[i]
+    p = f'{kind}.{i}.'
+    acc = np.zeros(bins, dtype=np.float32)
+    for k, (a, b, w) in enumerate(_rows(kind, g)):
+        r = (U.ghmc_ref if kind == 'c' else U.ghmr_ref)(a, b, w, bins, mmt, acc)
+        np.testing.assert_allclose(r['loss'], g[p + 'loss64'][k], rtol=1e-10)
+        assert r['counts'].tolist() == g[p + 'counts'][k].tolist() and r['tot'] == g[p + 'tot'][k] and r['n'] == g[p + 'n'][k]
+        if mmt > 0:
+            np.testing.assert_allclose(acc, g[p + 'acc64'][k], rtol=1e-10)
+        if k == 0:
+            np.testing.assert_allclose(r['grad'].numpy(), g[p + 'grad64'], rtol=1e-10, atol=1e-300)
+
+
+def _head():
+    from htd_amd.configs import retinanet_ghm_config
+    from htd_amd.registry import build_head
+    import htd_amd.detector  # noqa: F401
+    cfg = retinanet_ghm_config()
+    spec = cfg.model.bbox_head.to_dict()
+    spec.update(train_cfg=cfg.train_cfg, test_cfg=cfg.test_cfg)
+    return build_head(spec)
+
+
+def test_tensor_path_head_loss_on_the_cpu_matches_the_reference(golden):
+    """RetinaHead.loss with GHMC + GHMR (tensor path: one call of each loss per level, in level order) on ghm_util.head_maps
+    against the reference head, two consecutive calls so the second continues the first's acc_sum: five entries per loss, each
+    to 1e-10 in fp64 and 1e-5 in fp32; acc_sum of both modules after each call to rtol 1e-6."""
+    g = golden('ghm')
+    _, metas, gts, labels = BU.detector_inputs()
+    for dt, tag, rtol in ((torch.float64, '64', 1e-10), (torch.float32, '32', 1e-5)):
+        head = _head()
+        assert type(head.loss_cls).__name__ == 'GHMC' and type(head.loss_bbox).__name__ == 'GHMR' and head.sampling is False
+        cls, reg = U.head_maps(seed=int(g['head.seed']))
+        for call in range(2):
+            cl, rg = [c.to(dt).requires_grad_() for c in cls], [r.to(dt).requires_grad_() for r in reg]
+            losses = head.loss(cl, rg, [T(x).to(dt) for x in gts], [T(x) for x in labels], metas)
+            assert set(losses) == {'loss_cls', 'loss_bbox'} and len(losses['loss_cls']) == 5 and len(losses['loss_bbox']) == 5
+            mine = torch.stack([torch.stack(losses['loss_cls']), torch.stack(losses['loss_bbox'])]).detach()
+            np.testing.assert_allclose(mine.numpy(), g['head.loss' + tag][call], rtol=rtol, atol=1e-300)
+            np.testing.assert_allclose(head.loss_cls.acc_sum.numpy(), g['head.acc_c' + tag][call], rtol=1e-6)
+            np.testing.assert_allclose(head.loss_bbox.acc_sum.numpy(), g['head.acc_r' + tag][call], rtol=1e-6)
+        (sum(losses['loss_cls']) + sum(losses['loss_bbox'])).backward()
+        assert all(torch.isfinite(t.grad).all() for t in cl + rg)
+
+
+def test_ghm_config_equals_the_reference_merged_config():
+    from htd_amd.configs import retinanet_ghm_config, retinanet_ghm_model
+    ref = json.load(open(os.path.join(GOLDEN, 'retinanet_ghm_r50_fpn_1x_coco_cfg.json')))
+    cfg = retinanet_ghm_config()
+    mine = json.loads(json.dumps({k: (cfg[k].to_dict() if hasattr(cfg[k], 'to_dict') else cfg[k]) for k in RU.CFG_KEYS}))
+    assert mine == ref
+    assert mine['optimizer_config'] == dict(grad_clip=dict(max_norm=35, norm_type=2))
+    assert retinanet_ghm_model(101)['backbone']['depth'] == 101
+    with pytest.raises(ValueError):
+        retinanet_ghm_config(34)
+
+
+def test_state_dict_and_reference_format_checkpoint(golden, tmp_path):
+    """The detector's state-dict keys and shapes equal the reference's (the four buffers of the loss modules included), and a
+    checkpoint in the reference's wire format that carries them loads strictly: acc_sum arrives in the modules."""
+    from golden_util import seeded_state_value
+    from htd_amd.checkpoint import load_checkpoint
+    from htd_amd.configs import build_retinanet_detector, build_retinanet_ghm_detector, retinanet_ghm_config
+    g = golden('ghm')
+    det = build_retinanet_ghm_detector()
+    sd = det.state_dict()
+    assert list(sd.keys()) == [str(k) for k in g['state_keys']]
+    assert [list(v.shape) + [0] * (4 - v.dim()) for v in sd.values()] == g['state_shapes'].tolist()
+    assert set(U.STATE_KEYS) <= set(sd.keys())
+    assert type(det).__name__ == 'RetinaNet' and det.bbox_head.sampling is False
+    assert type(build_retinanet_detector(cfg=retinanet_ghm_config()).bbox_head.loss_cls).__name__ == 'GHMC'
+    ref = {}
+    for k, shape in zip(g['state_keys'], g['state_shapes']):
+        k = str(k)
+        if k.endswith('num_batches_tracked'):
+            ref[k] = torch.zeros((), dtype=torch.int64)
+        else:
+            ref[k] = torch.from_numpy(np.asarray(seeded_state_value('det.' + k, [int(s) for s in shape if s])))
+    ref['bbox_head.loss_cls.edges'], ref['bbox_head.loss_bbox.edges'] = U.edges_of(30, 'c'), U.edges_of(10, 'r')
+    ref['bbox_head.loss_cls.acc_sum'], ref['bbox_head.loss_bbox.acc_sum'] = T(g['acc_c']), T(g['acc_r'])
+    path = str(tmp_path / 'epoch_2.pth')
+    torch.save(dict(meta=dict(epoch=2, iter=10, mmdet_version='2.7.0', CLASSES=('person', )),
+                    state_dict={'module.' + k: v for k, v in ref.items()}), path)
+    ckpt = load_checkpoint(det, path, strict=True)
+    assert ckpt['meta']['epoch'] == 2
+    assert torch.equal(det.bbox_head.loss_cls.acc_sum, T(g['acc_c'])) and torch.equal(det.bbox_head.loss_bbox.acc_sum, T(g['acc_r']))
+    assert float(det.bbox_head.loss_cls.acc_sum.sum()) > 0
+
+
+def test_new_abi_symbols_are_declared_and_exported():
+    from htd_amd import capi
+    names = {n for n, _, _ in capi.declared_functions()}
+    want = {'htd_ghm_workspace_bytes', 'htd_ghmc_loss', 'htd_ghm_head_loss'}
+    assert want <= names
+    lib = capi.lib()
+    assert all(hasattr(lib, n) for n in want)
+    assert lib.htd_ghm_workspace_bytes(5) >= 4 * (2 * 5 * 64 * 2 + 4 * 5) and lib.htd_ghm_workspace_bytes(9) < 0
+    assert lib.htd_ghm_workspace_bytes(0) < 0
