@@ -24,9 +24,10 @@ EXTRA = {'nms.hip': ['-ffp-contract=off'], 'box_ops.hip': ['-ffp-contract=off'],
 # the reference interface per entry point):
 #   focal_loss.hip   mmcv.ops.sigmoid_focal_loss (mmdet/models/losses/focal_loss.py:10-87) and AnchorHead.loss of a head without
 #                    sampling over all pyramid levels (dense_heads/anchor_head.py:172-269,288-291,373-488, retina_head.py)
-#   ghm_loss.hip     GHMC / GHMR (mmdet/models/losses/ghm_loss.py:20-172) and AnchorHead.loss with the pair (the level table
-#                    of focal_loss.hip, shared through retina_levels.h)
+#   ghm_loss.hip     GHMC / GHMR (mmdet/models/losses/ghm_loss.py:20-172) and AnchorHead.loss with the pair (the level table,
+#                    map decoding and box targets of focal_loss.hip, shared through retina_levels.h)
 #   fcos.hip         FCOSHead's targets, loss and ranking keys (dense_heads/fcos_head.py:159-253,364-372,415-576)
+# The three share focal_elem.h (the element arithmetic) and loss_units.h (level search, VEC-wide units, matrix units).
 def sources():
     return sorted(f for f in os.listdir(HERE) if f.endswith('.hip') or f.endswith('.cpp'))
 

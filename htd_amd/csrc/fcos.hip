@@ -12,6 +12,7 @@
 #include "common.h"
 #include "focal_elem.h"
 #include "iou_family.h"
+#include "loss_units.h"
 
 namespace {
 
@@ -37,13 +38,6 @@ struct FcosMaps {
     unsigned ts[FCOS_MAX_LEVELS];           // channel stride of the centerness map in floats (>= 1)
     unsigned rrow[FCOS_MAX_LEVELS + 1];     // prefix sums of B * pix: the pixel rows of all levels
 };
-
-__device__ __forceinline__ int level_of(const unsigned *off, int L, unsigned i)
-{
-    int l = 0;
-    while (l + 1 < L && i >= off[l + 1]) ++l;
-    return l;
-}
 
 __device__ __forceinline__ void point_xy(const FcosPoints &pt, int l, unsigned p, float &x, float &y)
 {
@@ -212,12 +206,7 @@ __global__ __launch_bounds__(256) void fcos_loss_kernel(FcosMaps mp, FcosPoints 
             for (int k = 0; k < VEC; ++k) go[k] = 0.f;
             if (c0 < (unsigned)C) {                                                 // (VEC = 4: C % 4 == 0, whole units)
                 float xv[VEC];
-                if (VEC == 4) {
-                    const float4 q = *reinterpret_cast<const float4 *>(x_row + (int64_t)j * 4);
-                    xv[0] = q.x; xv[1 % VEC] = q.y; xv[2 % VEC] = q.z; xv[3 % VEC] = q.w;
-                } else {
-                    xv[0] = x_row[j];
-                }
+                load_unit<VEC>(x_row, j, xv);
 #pragma unroll
                 for (int k = 0; k < VEC; ++k) {
                     float g;
@@ -225,10 +214,7 @@ __global__ __launch_bounds__(256) void fcos_loss_kernel(FcosMaps mp, FcosPoints 
                     go[k] = g * cs;
                 }
             }
-            if (VEC == 4)
-                *reinterpret_cast<float4 *>(g_row + (int64_t)j * 4) = make_float4(go[0], go[1 % VEC], go[2 % VEC], go[3 % VEC]);
-            else
-                g_row[j] = go[0];
+            store_unit<VEC>(g_row, j, go);
         }
     }
     // the points: decode prediction and target against the point (distance2bbox), the box loss weighted by the centerness target

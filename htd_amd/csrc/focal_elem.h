@@ -1,6 +1,6 @@
 // The sigmoid focal loss of one element with its derivative, and the two-sum block reduction of the head-loss kernels: shared
 // by focal_loss.hip (htd_sigmoid_focal_loss, htd_retina_loss) and fcos.hip (htd_fcos_loss), so the dense heads take the same
-// arithmetic.  See focal_loss.hip for the formulation.
+// arithmetic.  See focal_loss.hip for the formulation; how the kernels address their maps is in loss_units.h.
 #pragma once
 #include "common.h"
 

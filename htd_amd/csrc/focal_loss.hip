@@ -27,18 +27,12 @@ __global__ __launch_bounds__(256) void focal_matrix_kernel(const float *__restri
 {
     float sum = 0.f;
     for (int64_t u = (int64_t)blockIdx.x * 256 + threadIdx.x; u < units; u += (int64_t)gridDim.x * 256) {
-        // cols = C / VEC units per row; the 64-bit division only where the index needs it
-        const int64_t row = units <= 0xffffffffLL ? (int64_t)((unsigned)u / (unsigned)cols) : u / cols;
-        const int c0 = (int)(u - row * cols) * VEC;
+        int c0;
+        const int64_t row = matrix_unit<VEC>(u, units, cols, c0);
         const int64_t lab = labels[row];
         const float w = weight ? weight[row] : 1.f;
         float xv[VEC], lo[VEC], go[VEC];
-        if (VEC == 4) {
-            const float4 v = *reinterpret_cast<const float4 *>(x + u * 4);
-            xv[0] = v.x; xv[1 % VEC] = v.y; xv[2 % VEC] = v.z; xv[3 % VEC] = v.w;
-        } else {
-            xv[0] = x[u];
-        }
+        load_unit<VEC>(x, u, xv);
 #pragma unroll
         for (int k = 0; k < VEC; ++k) {
             float g;
@@ -47,13 +41,8 @@ __global__ __launch_bounds__(256) void focal_matrix_kernel(const float *__restri
             go[k] = w * g;
             sum += lo[k];
         }
-        if (VEC == 4) {
-            if (loss_out) *reinterpret_cast<float4 *>(loss_out + u * 4) = make_float4(lo[0], lo[1 % VEC], lo[2 % VEC], lo[3 % VEC]);
-            *reinterpret_cast<float4 *>(grad + u * 4) = make_float4(go[0], go[1 % VEC], go[2 % VEC], go[3 % VEC]);
-        } else {
-            if (loss_out) loss_out[u] = lo[0];
-            grad[u] = go[0];
-        }
+        if (loss_out) store_unit<VEC>(loss_out, u, lo);
+        store_unit<VEC>(grad, u, go);
     }
     __shared__ float red[4];
     sum = htd::wave_sum(sum);
@@ -74,8 +63,7 @@ __device__ __forceinline__ float box_elem(float d, float beta, float &g)
 }
 
 // One unit = VEC classes of one anchor of one pixel of one image (or VEC padding channels), then one unit = the four deltas of
-// one anchor (or four padding channels).  Every unit of every gradient map is stored exactly once, zeros included.  Requires
-// na * C < 2^20 (checked by the caller).
+// one anchor (or four padding channels).  Every unit of every gradient map is stored exactly once, zeros included.
 template <int VEC, bool G2, bool L1>
 __global__ __launch_bounds__(256) void retina_loss_kernel(RetinaLevels lv, int L, int na, int C, const float *__restrict__ anchors,
                                                           const float *__restrict__ gts, const int64_t *__restrict__ gt_labels,
@@ -97,36 +85,20 @@ __global__ __launch_bounds__(256) void retina_loss_kernel(RetinaLevels lv, int L
     const unsigned n_rows = lv.rrow[L];
     const float inv_c = 1.f / (float)C;
     for (unsigned rw = wave; rw < n_rows; rw += gridDim.x * 4u) {
-        int l = 0;
-        while (l + 1 < L && rw >= lv.rrow[l + 1]) ++l;
-        const unsigned row = rw - lv.rrow[l];                                       // b * pix + p
-        const unsigned b = row / lv.pix[l], p = row - b * lv.pix[l];
-        const unsigned cu = lv.cu[l];
-        const int64_t *as_row = assigned + (int64_t)b * A + lv.aoff[l] + p * (unsigned)na;
-        const int64_t *lab_row = gt_labels + (int64_t)b * K;
-        const float *x_row = lv.cls[l] + (int64_t)row * cu * VEC;
-        float *g_row = lv.gcls[l] + (int64_t)row * cu * VEC;
-        for (unsigned j = lane; j < cu; j += 64u) {
+        const ClsRow r = cls_row<VEC>(lv, L, rw, na, assigned, A, gt_labels, K);
+        for (unsigned j = lane; j < r.cu; j += 64u) {
             const unsigned ch = j * VEC;
             float go[VEC];
 #pragma unroll
             for (int k = 0; k < VEC; ++k) go[k] = 0.f;
             if (ch < nc) {
-                unsigned a = (unsigned)(((float)ch + 0.5f) * inv_c);                // ch / C for ch < 2^20 ...
-                a -= (a * (unsigned)C > ch) ? 1u : 0u;                              // ... made exact whatever the rounding
-                a += ((a + 1u) * (unsigned)C <= ch) ? 1u : 0u;
-                const unsigned c0 = ch - a * (unsigned)C;
-                const int64_t as = as_row[a];
+                unsigned c0;
+                const int64_t as = r.as_row[anchor_of_channel(ch, (unsigned)C, inv_c, c0)];
                 if (as >= 0) {
-                    const int64_t lab = as > 0 ? lab_row[as - 1] : (int64_t)C;
+                    const int64_t lab = as > 0 ? r.lab_row[as - 1] : (int64_t)C;
                     const float w = (as > 0 && pos_weight > 0.f) ? pos_weight : 1.f;
                     float xv[VEC];
-                    if (VEC == 4) {
-                        const float4 q = *reinterpret_cast<const float4 *>(x_row + (int64_t)j * 4);
-                        xv[0] = q.x; xv[1 % VEC] = q.y; xv[2 % VEC] = q.z; xv[3 % VEC] = q.w;
-                    } else {
-                        xv[0] = x_row[j];
-                    }
+                    load_unit<VEC>(r.x_row, j, xv);
 #pragma unroll
                     for (int k = 0; k < VEC; ++k) {
                         float g;
@@ -135,47 +107,29 @@ __global__ __launch_bounds__(256) void retina_loss_kernel(RetinaLevels lv, int L
                     }
                 }
             }
-            if (VEC == 4)
-                *reinterpret_cast<float4 *>(g_row + (int64_t)j * 4) = make_float4(go[0], go[1 % VEC], go[2 % VEC], go[3 % VEC]);
-            else
-                g_row[j] = go[0];
+            store_unit<VEC>(r.g_row, j, go);
         }
     }
     // regression maps: a twentieth of the data, one float4 (the four deltas of an anchor) per thread
     for (unsigned u = n_cls + blockIdx.x * 256u + threadIdx.x; u < n_all; u += gridDim.x * 256u) {
-        {
-            int l = 0;
-            while (l + 1 < L && u >= lv.roff[l + 1]) ++l;
-            const unsigned v = u - lv.roff[l];
-            const unsigned row = v / lv.ru[l], a = v - row * lv.ru[l];
-            float4 gr = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (a < (unsigned)na) {
-                const unsigned b = row / lv.pix[l], p = row - b * lv.pix[l];
-                const unsigned ai = lv.aoff[l] + p * (unsigned)na + a;
-                const int64_t as = assigned[(int64_t)b * A + ai];
-                if (as > 0) {
-                    const float4 an = *reinterpret_cast<const float4 *>(anchors + (int64_t)ai * 4);
-                    const float4 g = *reinterpret_cast<const float4 *>(gts + ((int64_t)b * K + (as - 1)) * 4);
-                    const float px = (an.x + an.z) * 0.5f, py = (an.y + an.w) * 0.5f, pw = an.z - an.x, ph = an.w - an.y;
-                    const float cx = (g.x + g.z) * 0.5f, cy = (g.y + g.w) * 0.5f, gw = g.z - g.x, gh = g.w - g.y;
-                    float tgt[4];
-                    tgt[0] = ((cx - px) / pw - means.v[0]) / stds.v[0];
-                    tgt[1] = ((cy - py) / ph - means.v[1]) / stds.v[1];
-                    tgt[2] = (logf(gw / pw) - means.v[2]) / stds.v[2];
-                    tgt[3] = (logf(gh / ph) - means.v[3]) / stds.v[3];
-                    const float4 r = *reinterpret_cast<const float4 *>(lv.reg[l] + (int64_t)v * 4);
-                    const float rr[4] = {r.x, r.y, r.z, r.w};
-                    float go[4];
+        const RegUnit r = reg_unit(lv, L, u);
+        float go[4] = {0.f, 0.f, 0.f, 0.f};
+        if (r.a < (unsigned)na) {
+            unsigned b;
+            const unsigned ai = reg_anchor(lv, r, na, b);
+            const int64_t as = assigned[(int64_t)b * A + ai];
+            if (as > 0) {
+                float tgt[4], rr[4];
+                delta_target(anchors + (int64_t)ai * 4, gts + ((int64_t)b * K + (as - 1)) * 4, means, stds, tgt);
+                load_unit<4>(lv.reg[r.l], r.v, rr);
 #pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        s_box += box_elem<L1>(rr[k] - tgt[k], beta, go[k]);
-                        go[k] *= bs;
-                    }
-                    gr = make_float4(go[0], go[1], go[2], go[3]);
+                for (int k = 0; k < 4; ++k) {
+                    s_box += box_elem<L1>(rr[k] - tgt[k], beta, go[k]);
+                    go[k] *= bs;
                 }
             }
-            *reinterpret_cast<float4 *>(lv.greg[l] + (int64_t)v * 4) = gr;
         }
+        store_unit<4>(lv.greg[r.l], r.v, go);
     }
     block_store_partial2(s_cls, s_box, partial);
 }
@@ -217,8 +171,7 @@ __global__ __launch_bounds__(256) void retina_scale_kernel(RetinaLevels lv, int 
     for (unsigned u = lo + blockIdx.x * 256u + threadIdx.x; u < hi; u += gridDim.x * 256u) {
         const bool is_cls = u < n_cls;
         const unsigned *off = is_cls ? lv.coff : lv.roff;
-        int l = 0;
-        while (l + 1 < L && u >= off[l + 1]) ++l;
+        const int l = level_of(off, L, u);
         float4 *p = reinterpret_cast<float4 *>(is_cls ? lv.gcls[l] : lv.greg[l]) + (u - off[l]);
         float4 q = *p;
         const float s = is_cls ? gc : gb;
@@ -239,8 +192,7 @@ __global__ __launch_bounds__(256) void retina_keys_kernel(RetinaLevels lv, int L
         if (i < rows) {
             const int b = (int)(i / A);
             const unsigned ai = (unsigned)(i - (int64_t)b * A);
-            int l = 0;
-            while (l + 1 < L && ai >= lv.aoff[l + 1]) ++l;
+            const int l = level_of(lv.aoff, L, ai);
             const unsigned q = ai - lv.aoff[l], p = q / (unsigned)na, a = q - p * (unsigned)na;
             const float *x = lv.cls[l] + ((int64_t)b * lv.pix[l] + p) * lv.cu[l] + (int64_t)a * C;   // cu: channel stride in floats here
             if ((C & 3) == 0 && (lv.cu[l] & 3) == 0) {
@@ -303,19 +255,12 @@ extern "C" int htd_retina_loss(const float *const *cls, const int64_t *cls_strid
     HTD_REQUIRE(anchors && gts && gt_labels && assigned && means4 && stds4 && avg_factor && partial, "retina_loss: null pointer");
     HTD_REQUIRE((int64_t)na * C < (1 << 20), "retina_loss: more than 2^20 classification channels");
     HTD_REQUIRE(K > 0 && gamma >= 0.f && (box_loss == 1 || (box_loss == 0 && beta > 0.f)), "retina_loss: bad parameters");
-    bool vec = (C & 3) == 0;
-    for (int l = 0; l < L && l < RETINA_MAX_LEVELS && vec; ++l) vec = cls_stride && (cls_stride[l] & 3) == 0;
     RetinaLevels lv = {};
-    int64_t A_lv = 0;
-    const int rc = fill_levels(lv, "retina_loss", cls, cls_stride, reg, reg_stride, grad_cls, grad_reg, pix, L, B, na, C, vec ? 4 : 1,
-                               &A_lv);
-    if (rc != HTD_OK) return rc;
-    HTD_REQUIRE(A_lv == A, "retina_loss: A = %d, the levels hold %lld anchors", A, (long long)A_lv);
-    for (int l = 0; l < L; ++l)
-        HTD_REQUIRE(grad_cls[l] && grad_reg[l] && (((vec ? (uintptr_t)grad_cls[l] : 0) | (uintptr_t)grad_reg[l]) & 15) == 0,
-                    "retina_loss: gradient map %d is null or not 16-byte aligned", l);
+    bool vec;
     Vec4f m, sd;
-    for (int k = 0; k < 4; ++k) { m.v[k] = means4[k]; sd.v[k] = stds4[k]; }
+    const int rc = head_loss_levels(lv, "retina_loss", cls, cls_stride, reg, reg_stride, grad_cls, grad_reg, pix, L, B, na, C, A,
+                                    means4, stds4, vec, m, sd);
+    if (rc != HTD_OK) return rc;
     const bool g2 = gamma == 2.f, l1 = box_loss == 1;
 #define HTD_RETINA_LAUNCH(V, G, B1)                                                                                                    \
     hipLaunchKernelGGL((retina_loss_kernel<V, G, B1>), dim3(FOCAL_BLOCKS), dim3(256), 0, (hipStream_t)stream, lv, L, na, C, anchors, \

@@ -59,8 +59,8 @@ __device__ __forceinline__ int ghm_bin(float g, const float *edges, int bins)
     return g >= lo ? i : -1;                // (false only for a NaN)
 }
 
-// -> BCEWithLogits(x, t); g = |sigmoid(x) - t|, sgn * g = d BCE / dx.  The exponential, logarithm and reciprocal of the
-// focal kernels (focal_elem.h): one exp and one log per element.
+// -> BCEWithLogits(x, t); g = |sigmoid(x) - t|, sgn * g = d BCE / dx.  One exp and one log per element, as in focal_elem.h;
+// written out here, because sharing the lines through a function changes the code generated for the focal kernels.
 __device__ __forceinline__ float ghmc_elem(float x, bool t, float &g, float &sgn)
 {
     const float z = t ? -x : x;
@@ -149,8 +149,8 @@ __global__ __launch_bounds__(256) void ghmc_matrix_kernel(const float *__restric
 #pragma unroll
         for (int k = 0; k < VEC; ++k) bin[k] = -1;
         if (u < units) {
-            const int64_t row = units <= 0xffffffffLL ? (int64_t)((unsigned)u / (unsigned)cols) : u / cols;
-            const int c0 = (int)(u - row * cols) * VEC;
+            int c0;
+            const int64_t row = matrix_unit<VEC>(u, units, cols, c0);
             const int64_t lab = labels[row];
             const bool valid = weight[row] > 0.f;
             float go[VEC];
@@ -158,12 +158,7 @@ __global__ __launch_bounds__(256) void ghmc_matrix_kernel(const float *__restric
             for (int k = 0; k < VEC; ++k) go[k] = 0.f;
             if (valid) {
                 float xv[VEC];
-                if (VEC == 4) {
-                    const float4 v = *reinterpret_cast<const float4 *>(x + u * 4);
-                    xv[0] = v.x; xv[1 % VEC] = v.y; xv[2 % VEC] = v.z; xv[3 % VEC] = v.w;
-                } else {
-                    xv[0] = x[u];
-                }
+                load_unit<VEC>(x, u, xv);
 #pragma unroll
                 for (int k = 0; k < VEC; ++k) {
                     float g, sgn;
@@ -177,12 +172,7 @@ __global__ __launch_bounds__(256) void ghmc_matrix_kernel(const float *__restric
                 }
                 nv += VEC;
             }
-            if (LOSS) {
-                if (VEC == 4)
-                    *reinterpret_cast<float4 *>(grad + u * 4) = make_float4(go[0], go[1 % VEC], go[2 % VEC], go[3 % VEC]);
-                else
-                    grad[u] = go[0];
-            }
+            if (LOSS) store_unit<VEC>(grad, u, go);
         }
         if (!LOSS) {
 #pragma unroll
@@ -234,10 +224,11 @@ __global__ __launch_bounds__(64) void ghm_weights_kernel(int L, int n_losses, in
 }
 
 // ---- head form -----------------------------------------------------------------------------------------------------------------
-// The traversal of retina_loss_kernel (focal_loss.hip): one wavefront per pixel row of the classification maps, one float4
-// (the four deltas of an anchor) per thread of the regression maps.  LOSS = false: launch 1; LOSS = true: launch 3, which
-// stores every unit of every gradient map exactly once, zeros and padding channels included.  Valid for GHMC: assigned >= 0
-// (only the sign of a label weight counts, ghm_loss.py:75); for GHMR: assigned > 0, weight 1 per delta.
+// One wavefront per pixel row of the classification maps, one float4 (the four deltas of an anchor) per thread of the
+// regression maps, decoded by retina_levels.h.  Every lane stays in both sweeps: wave_key_add needs the whole wavefront.
+// LOSS = false: launch 1; LOSS = true: launch 3, which stores every unit of every gradient map exactly once, zeros and
+// padding channels included.  Valid for GHMC: assigned >= 0 (only the sign of a label weight counts, ghm_loss.py:75); for
+// GHMR: assigned > 0, weight 1 per delta.
 template <int VEC, bool LOSS>
 __global__ __launch_bounds__(256) void ghm_head_kernel(RetinaLevels lv, int L, int na, int C, const float *__restrict__ anchors,
                                                        const float *__restrict__ gts, const int64_t *__restrict__ gt_labels,
@@ -265,41 +256,26 @@ __global__ __launch_bounds__(256) void ghm_head_kernel(RetinaLevels lv, int L, i
     const unsigned n_rows = lv.rrow[L];
     const float inv_c = 1.f / (float)C;
     for (unsigned rw = wave; rw < n_rows; rw += gridDim.x * 4u) {
-        int l = 0;
-        while (l + 1 < L && rw >= lv.rrow[l + 1]) ++l;
-        const unsigned row = rw - lv.rrow[l];                                       // b * pix + p
-        const unsigned b = row / lv.pix[l], p = row - b * lv.pix[l];
-        const unsigned cu = lv.cu[l];
-        const int64_t *as_row = assigned + (int64_t)b * A + lv.aoff[l] + p * (unsigned)na;
-        const int64_t *lab_row = gt_labels + (int64_t)b * K;
-        const float *x_row = lv.cls[l] + (int64_t)row * cu * VEC;
-        float *g_row = LOSS ? lv.gcls[l] + (int64_t)row * cu * VEC : nullptr;
+        const ClsRow r = cls_row<VEC>(lv, L, rw, na, assigned, A, gt_labels, K);
+        const int l = r.l;
         unsigned nv = 0;
-        for (unsigned j0 = 0; j0 < cu; j0 += 64u) {                                 // uniform over the wavefront
+        for (unsigned j0 = 0; j0 < r.cu; j0 += 64u) {                               // uniform over the wavefront
             const unsigned j = j0 + lane;
             int bin[VEC];
 #pragma unroll
             for (int k = 0; k < VEC; ++k) bin[k] = -1;
-            if (j < cu) {
+            if (j < r.cu) {
                 const unsigned ch = j * VEC;
                 float go[VEC];
 #pragma unroll
                 for (int k = 0; k < VEC; ++k) go[k] = 0.f;
                 if (ch < nc) {
-                    unsigned a = (unsigned)(((float)ch + 0.5f) * inv_c);            // ch / C for ch < 2^20 ...
-                    a -= (a * (unsigned)C > ch) ? 1u : 0u;                          // ... made exact whatever the rounding
-                    a += ((a + 1u) * (unsigned)C <= ch) ? 1u : 0u;
-                    const unsigned c0 = ch - a * (unsigned)C;
-                    const int64_t as = as_row[a];
+                    unsigned c0;
+                    const int64_t as = r.as_row[anchor_of_channel(ch, (unsigned)C, inv_c, c0)];
                     if (as >= 0) {
-                        const int64_t lab = as > 0 ? lab_row[as - 1] : (int64_t)C;
+                        const int64_t lab = as > 0 ? r.lab_row[as - 1] : (int64_t)C;
                         float xv[VEC];
-                        if (VEC == 4) {
-                            const float4 q = *reinterpret_cast<const float4 *>(x_row + (int64_t)j * 4);
-                            xv[0] = q.x; xv[1 % VEC] = q.y; xv[2 % VEC] = q.z; xv[3 % VEC] = q.w;
-                        } else {
-                            xv[0] = x_row[j];
-                        }
+                        load_unit<VEC>(r.x_row, j, xv);
 #pragma unroll
                         for (int k = 0; k < VEC; ++k) {
                             float g, sgn;
@@ -314,12 +290,7 @@ __global__ __launch_bounds__(256) void ghm_head_kernel(RetinaLevels lv, int L, i
                         nv += VEC;
                     }
                 }
-                if (LOSS) {
-                    if (VEC == 4)
-                        *reinterpret_cast<float4 *>(g_row + (int64_t)j * 4) = make_float4(go[0], go[1 % VEC], go[2 % VEC], go[3 % VEC]);
-                    else
-                        g_row[j] = go[0];
-                }
+                if (LOSS) store_unit<VEC>(r.g_row, j, go);
             }
             if (!LOSS) {
 #pragma unroll
@@ -337,29 +308,17 @@ __global__ __launch_bounds__(256) void ghm_head_kernel(RetinaLevels lv, int L, i
         int key[4] = {-1, -1, -1, -1};
         int tot_key = -1;
         if (u < n_all) {
-            int l = 0;
-            while (l + 1 < L && u >= lv.roff[l + 1]) ++l;
-            const unsigned v = u - lv.roff[l];
-            const unsigned row = v / lv.ru[l], a = v - row * lv.ru[l];
-            float4 gr = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (a < (unsigned)na) {
-                const unsigned b = row / lv.pix[l], p = row - b * lv.pix[l];
-                const unsigned ai = lv.aoff[l] + p * (unsigned)na + a;
+            const RegUnit r = reg_unit(lv, L, u);
+            const int l = r.l;
+            float go[4] = {0.f, 0.f, 0.f, 0.f};
+            if (r.a < (unsigned)na) {
+                unsigned b;
+                const unsigned ai = reg_anchor(lv, r, na, b);
                 const int64_t as = assigned[(int64_t)b * A + ai];
                 if (as > 0) {
-                    const float4 an = *reinterpret_cast<const float4 *>(anchors + (int64_t)ai * 4);
-                    const float4 g = *reinterpret_cast<const float4 *>(gts + ((int64_t)b * K + (as - 1)) * 4);
-                    // bbox2delta in the reference's fp32 arithmetic (it casts its inputs to float), as retina_loss_kernel forms it
-                    const float px = (an.x + an.z) * 0.5f, py = (an.y + an.w) * 0.5f, pw = an.z - an.x, ph = an.w - an.y;
-                    const float cx = (g.x + g.z) * 0.5f, cy = (g.y + g.w) * 0.5f, gw = g.z - g.x, gh = g.w - g.y;
-                    float tgt[4];
-                    tgt[0] = ((cx - px) / pw - means.v[0]) / stds.v[0];
-                    tgt[1] = ((cy - py) / ph - means.v[1]) / stds.v[1];
-                    tgt[2] = (logf(gw / pw) - means.v[2]) / stds.v[2];
-                    tgt[3] = (logf(gh / ph) - means.v[3]) / stds.v[3];
-                    const float4 r = *reinterpret_cast<const float4 *>(lv.reg[l] + (int64_t)v * 4);
-                    const float rr[4] = {r.x, r.y, r.z, r.w};
-                    float go[4];
+                    float tgt[4], rr[4];
+                    delta_target(anchors + (int64_t)ai * 4, gts + ((int64_t)b * K + (as - 1)) * 4, means, stds, tgt);
+                    load_unit<4>(lv.reg[l], r.v, rr);
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {
                         float gs;
@@ -370,11 +329,10 @@ __global__ __launch_bounds__(256) void ghm_head_kernel(RetinaLevels lv, int L, i
                         s_box += loss * m;
                         go[k] = gs * m;
                     }
-                    gr = make_float4(go[0], go[1], go[2], go[3]);
                     tot_key = GHM_TOT + RETINA_MAX_LEVELS + l;
                 }
             }
-            if (LOSS) *reinterpret_cast<float4 *>(lv.greg[l] + (int64_t)v * 4) = gr;
+            if (LOSS) store_unit<4>(lv.greg[l], r.v, go);
         }
         if (!LOSS) {
 #pragma unroll
@@ -443,18 +401,12 @@ extern "C" int htd_ghm_head_loss_launches(const float *const *cls, const int64_t
     if (rc != HTD_OK) return rc;
     rc = check_ghm("ghm_head_loss (GHMR)", edges_r, bins_r, momentum_r, acc_sum_r);
     if (rc != HTD_OK) return rc;
-    bool vec = (C & 3) == 0;
-    for (int l = 0; l < L && l < RETINA_MAX_LEVELS && vec; ++l) vec = cls_stride && (cls_stride[l] & 3) == 0;
     RetinaLevels lv = {};
-    int64_t A_lv = 0;
-    rc = fill_levels(lv, "ghm_head_loss", cls, cls_stride, reg, reg_stride, grad_cls, grad_reg, pix, L, B, na, C, vec ? 4 : 1, &A_lv);
-    if (rc != HTD_OK) return rc;
-    HTD_REQUIRE(A_lv == A, "ghm_head_loss: A = %d, the levels hold %lld anchors", A, (long long)A_lv);
-    for (int l = 0; l < L; ++l)
-        HTD_REQUIRE(grad_cls[l] && grad_reg[l] && (((vec ? (uintptr_t)grad_cls[l] : 0) | (uintptr_t)grad_reg[l]) & 15) == 0,
-                    "ghm_head_loss: gradient map %d is null or not 16-byte aligned", l);
+    bool vec;
     Vec4f m, sd;
-    for (int k = 0; k < 4; ++k) { m.v[k] = means4[k]; sd.v[k] = stds4[k]; }
+    rc = head_loss_levels(lv, "ghm_head_loss", cls, cls_stride, reg, reg_stride, grad_cls, grad_reg, pix, L, B, na, C, A, means4,
+                          stds4, vec, m, sd);
+    if (rc != HTD_OK) return rc;
     unsigned *ws = (unsigned *)workspace;
     hipStream_t s = (hipStream_t)stream;
     if ((launches & 1) && hipMemsetAsync(ws, 0, GHM_INT_WORDS * 4, s) != hipSuccess) return htd::check_launch("ghm_head_loss");

@@ -274,7 +274,7 @@ class FCOSHead(AnchorFreeHead):
             type(lb).__name__ in M.FCOS_BOX_KINDS and lb.reduction == 'mean' and \
             type(lt).__name__ == 'CrossEntropyLoss' and lt.use_sigmoid and lt.reduction == 'mean' and lt.class_weight is None and \
             len(cls_scores) <= 8 and \
-            all(t.is_cuda and t.dtype == torch.float32 and M.fcos_channel_stride(t) is not None
+            all(t.is_cuda and t.dtype == torch.float32 and M.nhwc_channel_stride(t) is not None
                 for t in list(cls_scores) + list(bbox_preds) + list(centernesses))
 
     def loss_tensor(self, cls_scores, bbox_preds, centernesses, gt_bboxes, gt_labels, img_metas, gt_bboxes_ignore=None):

@@ -1094,26 +1094,64 @@ class SigmoidFocalLoss(nn.Module):
 
 def nhwc_channel_stride(m):
     """Per-pixel channel stride of a (B, C, h, w) tensor whose memory is [B][h][w][stride] -- a channels_last map or a channel
-    slice of one -- or None for any other layout.  The stride of a size-1 dimension says nothing and is not looked at."""
+    slice of one -- or None for any other layout.  The stride of a size-1 dimension (one channel included) is not looked at."""
     B, C, h, w = m.shape
     sb, sc, sh, sw = m.stride()
     sw = (sb if B > 1 else C) if h * w == 1 else (sh if w == 1 else sw)
-    if sc != 1 or sw < C or (h > 1 and w > 1 and sh != w * sw) or (B > 1 and sb != h * w * sw):
+    if (C > 1 and sc != 1) or sw < C or (h > 1 and w > 1 and sh != w * sw) or (B > 1 and sb != h * w * sw):
         return None
     return sw
 
 
-def _level_tables(maps):
+def _level_tables(maps, what='level tables'):
     """channels_last (B, C, h, w) maps (possibly channel slices of wider maps) -> pointer table, channel strides, pixel counts."""
     ptrs, strides, pix = [], [], []
     for m in maps:
         sw = nhwc_channel_stride(m)
         if sw is None:
-            raise ValueError('retina ops: maps must be channels_last (or channel slices of channels_last maps)')
+            raise ValueError(f'{what}: maps must be channels_last (or channel slices of channels_last maps)')
         ptrs.append(m.data_ptr())
         strides.append(sw)
         pix.append(m.size(2) * m.size(3))
     return _table(ptrs), _i64s(strides), _i64s(pix)
+
+
+def _like_padded(m, stride):
+    """An uninitialised gradient map in the memory layout of m: channels_last, a slice of a `stride`-channel map when m is one."""
+    full = torch.empty(m.size(0), stride, m.size(2), m.size(3), device=m.device, dtype=torch.float32, memory_format=CL)
+    return full if stride == m.size(1) else full[:, :m.size(1)]
+
+
+def _grad_maps(maps, strides, what):
+    """-> gradient maps in the layout of `maps` (a kernel writes their padding as zeros) and their pointer table."""
+    grads = [_like_padded(m, s) for m, s in zip(maps, strides)]
+    table, gstrides, _ = _level_tables(grads, what)
+    assert list(gstrides) == list(strides)
+    return grads, table
+
+
+def _hand_over_once(ctx, what, entry, tables, grads):
+    """The backward of a fused head loss whose forward left finished gradient maps: `entry` (..., incoming gradients as device
+    scalars, stream) scales the saved maps where they lie (no second pass over a few hundred MB; a factor of exactly 1 is
+    skipped on the device) and autograd gets the maps themselves.  So one backward per forward: a second one raises."""
+    if getattr(ctx, 'scaled', False):
+        raise RuntimeError(f'{what}: a second backward through the same forward (retain_graph=True) is not supported: '
+                           'the gradient maps were handed over and scaled in place by the first')
+    ctx.scaled = True
+    capi.call(entry, *tables, *[_P(g.float().contiguous()) for g in grads], _S())
+
+
+def _anchor_head_backward(ctx, what, g_cls, g_box):
+    """-> the gradient maps of retina_loss / ghm_head_loss times the incoming gradients (htd_retina_grad_scale serves both)."""
+    na, C, B, L = ctx.meta
+    grads = ctx.saved_tensors
+    gcls, greg = grads[:L], grads[L:]
+    gct, gcs, pix = _level_tables(gcls, what)
+    grt, grs, _ = _level_tables(greg, what)
+    if all(s % 4 == 0 for s in gcs):
+        _hand_over_once(ctx, what, 'htd_retina_grad_scale', (gct, gcs, grt, grs, pix, L, B, na, C), (g_cls, g_box))
+        return tuple(grads)
+    return tuple(g * g_cls for g in gcls) + tuple(g * g_box for g in greg)
 
 
 def retina_avg_factor(assigned):
@@ -1141,22 +1179,11 @@ class RetinaLossFunction(Function):
         cls, reg = maps[:L], maps[L:]
         B, A = assigned.shape
         K = gts.size(1)
-        ct, cs, pix = _level_tables(cls)
-        rt, rs, _ = _level_tables(reg)
-        dev = assigned.device
-        gcls = [torch.empty(m.shape, device=dev, dtype=torch.float32, memory_format=CL) for m in cls]
-        greg = [torch.empty(m.shape, device=dev, dtype=torch.float32, memory_format=CL) for m in reg]
-        gct, gcs, _ = _level_tables(gcls)
-        grt, grs, _ = _level_tables(greg)
-        if list(gcs) != list(cs) or list(grs) != list(rs):
-            # maps that are slices of wider ones: the gradient maps take the same padded layout, padding written as zeros
-            gcls = [torch.empty(m.size(0), s, m.size(2), m.size(3), device=dev, dtype=torch.float32, memory_format=CL)[:, :m.size(1)]
-                    for m, s in zip(cls, cs)]
-            greg = [torch.empty(m.size(0), s, m.size(2), m.size(3), device=dev, dtype=torch.float32, memory_format=CL)[:, :m.size(1)]
-                    for m, s in zip(reg, rs)]
-            gct, gcs, _ = _level_tables(gcls)
-            grt, grs, _ = _level_tables(greg)
-        partial = torch.empty(capi.lib().htd_focal_loss_partial_rows(), 2, device=dev, dtype=torch.float32)
+        ct, cs, pix = _level_tables(cls, 'retina_loss')
+        rt, rs, _ = _level_tables(reg, 'retina_loss')
+        gcls, gct = _grad_maps(cls, cs, 'retina_loss')
+        greg, grt = _grad_maps(reg, rs, 'retina_loss')
+        partial = torch.empty(capi.lib().htd_focal_loss_partial_rows(), 2, device=assigned.device, dtype=torch.float32)
         capi.call('htd_retina_loss', ct, cs, rt, rs, pix, L, B, int(na), int(C), _P(anchors), _P(gts), _P(gt_labels), _P(assigned),
                   A, K, _f4(means), _f4(stds), float(gamma), float(alpha), float(pos_weight), int(box_loss), float(beta),
                   _P(avg), float(cls_weight), float(box_weight), _P(partial), gct, grt, _S())
@@ -1168,22 +1195,7 @@ class RetinaLossFunction(Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, g_cls, g_box):
-        na, C, B, L = ctx.meta
-        grads = ctx.saved_tensors
-        gcls, greg = grads[:L], grads[L:]
-        gct, gcs, pix = _level_tables(gcls)
-        grt, grs, _ = _level_tables(greg)
-        if all(s % 4 == 0 for s in gcs):
-            # the saved maps are scaled where they are (no second 258 MB pass): one backward per forward
-            if getattr(ctx, 'scaled', False):
-                raise RuntimeError('retina_loss: a second backward through the same forward (retain_graph=True) is not supported: '
-                                   'the gradient maps were handed over and scaled in place by the first')
-            ctx.scaled = True
-            capi.call('htd_retina_grad_scale', gct, gcs, grt, grs, pix, L, B, na, C, _P(g_cls.float().contiguous()),
-                      _P(g_box.float().contiguous()), _S())
-        else:
-            gcls, greg = [g * g_cls for g in gcls], [g * g_box for g in greg]
-        return (None, ) * 16 + tuple(gcls) + tuple(greg)
+        return (None, ) * 16 + _anchor_head_backward(ctx, 'retina_loss', g_cls, g_box)
 
 
 def retina_loss(cls_maps, reg_maps, na, C, anchors, gts, gt_labels, assigned, avg, means, stds, gamma, alpha, pos_weight,
@@ -1202,7 +1214,7 @@ def retina_keys(cls_maps, na, C):
     _need_gpu(cls_maps[0], 'retina_keys')
     for m in cls_maps:
         _f32(m, 'retina_keys')
-    ct, cs, pix = _level_tables(cls_maps)
+    ct, cs, pix = _level_tables(cls_maps, 'retina_keys')
     B = cls_maps[0].size(0)
     A = na * sum(pix)
     keys = torch.empty(B, A, device=cls_maps[0].device, dtype=torch.float32)
@@ -1278,20 +1290,13 @@ class GhmHeadLossFunction(Function):
         cls, reg = maps[:L], maps[L:]
         B, A = assigned.shape
         K = gts.size(1)
-        ct, cs, pix = _level_tables(cls)
-        rt, rs, _ = _level_tables(reg)
-        dev = assigned.device
-        # the gradient maps take the layout of the maps (slices of wider ones: the padded layout, padding written as zeros)
-        gcls = [torch.empty(m.size(0), s, m.size(2), m.size(3), device=dev, dtype=torch.float32, memory_format=CL)[:, :m.size(1)]
-                for m, s in zip(cls, cs)]
-        greg = [torch.empty(m.size(0), s, m.size(2), m.size(3), device=dev, dtype=torch.float32, memory_format=CL)[:, :m.size(1)]
-                for m, s in zip(reg, rs)]
-        gct, gcs, _ = _level_tables(gcls)
-        grt, grs, _ = _level_tables(greg)
-        assert list(gcs) == list(cs) and list(grs) == list(rs)
+        ct, cs, pix = _level_tables(cls, 'ghm_head_loss')
+        rt, rs, _ = _level_tables(reg, 'ghm_head_loss')
+        gcls, gct = _grad_maps(cls, cs, 'ghm_head_loss')
+        greg, grt = _grad_maps(reg, rs, 'ghm_head_loss')
         edges_c, bins_c, mmt_c, acc_c, w_c = ghmc
         edges_r, bins_r, mmt_r, acc_r, w_r, mu = ghmr
-        partial = torch.empty(capi.lib().htd_focal_loss_partial_rows(), 2, device=dev, dtype=torch.float32)
+        partial = torch.empty(capi.lib().htd_focal_loss_partial_rows(), 2, device=assigned.device, dtype=torch.float32)
         capi.call('htd_ghm_head_loss', ct, cs, rt, rs, pix, L, B, int(na), int(C), _P(anchors), _P(gts), _P(gt_labels), _P(assigned),
                   A, K, _f4(means), _f4(stds), _P(edges_c), int(bins_c), float(mmt_c), _P(acc_c) if mmt_c > 0 else None,
                   _P(edges_r), int(bins_r), float(mmt_r), _P(acc_r) if mmt_r > 0 else None, float(mu), float(w_c), float(w_r),
@@ -1304,21 +1309,7 @@ class GhmHeadLossFunction(Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, g_cls, g_box):
-        na, C, B, L = ctx.meta
-        grads = ctx.saved_tensors
-        gcls, greg = grads[:L], grads[L:]
-        gct, gcs, pix = _level_tables(gcls)
-        grt, grs, _ = _level_tables(greg)
-        if all(s % 4 == 0 for s in gcs):
-            if getattr(ctx, 'scaled', False):
-                raise RuntimeError('ghm_head_loss: a second backward through the same forward (retain_graph=True) is not '
-                                   'supported: the gradient maps were handed over and scaled in place by the first')
-            ctx.scaled = True
-            capi.call('htd_retina_grad_scale', gct, gcs, grt, grs, pix, L, B, na, C, _P(g_cls.float().contiguous()),
-                      _P(g_box.float().contiguous()), _S())
-        else:
-            gcls, greg = [g * g_cls for g in gcls], [g * g_box for g in greg]
-        return (None, ) * 11 + tuple(gcls) + tuple(greg)
+        return (None, ) * 11 + _anchor_head_backward(ctx, 'ghm_head_loss', g_cls, g_box)
 
 
 def ghm_head_loss(cls_maps, reg_maps, na, C, anchors, gts, gt_labels, assigned, means, stds, loss_cls, loss_bbox,
@@ -1380,30 +1371,6 @@ def fcos_targets(featmap_sizes, strides, regress_ranges, gts, gt_valid, center_s
     return assigned, bbox_targets, ctr_targets, num_pos, norm
 
 
-def fcos_channel_stride(m):
-    """nhwc_channel_stride of a map; a one-channel map (the centerness) is NHWC whatever stride its channel dimension reports."""
-    if m.size(1) == 1 and m.stride(1) != 1:
-        m = m.as_strided(m.size(), (m.stride(0), 1, m.stride(2), m.stride(3)))
-    return nhwc_channel_stride(m)
-
-
-def _fcos_tables(maps):
-    ptrs, strides = [], []
-    for m in maps:
-        sw = fcos_channel_stride(m)
-        if sw is None:
-            raise ValueError('fcos ops: maps must be channels_last (or channel slices of channels_last maps)')
-        ptrs.append(m.data_ptr())
-        strides.append(sw)
-    return _table(ptrs), _i64s(strides)
-
-
-def _like_padded(m, stride):
-    """An uninitialised gradient map in the memory layout of m: channels_last, a slice of a `stride`-channel map when m is one."""
-    full = torch.empty(m.size(0), stride, m.size(2), m.size(3), device=m.device, dtype=torch.float32, memory_format=CL)
-    return full if stride == m.size(1) else full[:, :m.size(1)]
-
-
 class FcosLossFunction(Function):
     """htd_fcos_loss: the three losses of FCOSHead.loss over every level and image in one launch, which also writes the three
     finished gradient maps (loss weight and normaliser applied); backward hands them over, after htd_fcos_grad_scale applies
@@ -1415,16 +1382,12 @@ class FcosLossFunction(Function):
         L = len(maps) // 3
         cls, reg, ctr = maps[:L], maps[L:2 * L], maps[2 * L:]
         B, K = gt_labels.shape
-        ct, cs = _fcos_tables(cls)
-        rt, rs = _fcos_tables(reg)
-        tt, ts = _fcos_tables(ctr)
-        gcls = [_like_padded(m, s) for m, s in zip(cls, cs)]
-        greg = [_like_padded(m, s) for m, s in zip(reg, rs)]
-        gctr = [_like_padded(m, s) for m, s in zip(ctr, ts)]
-        gct, gcs = _fcos_tables(gcls)
-        grt, grs = _fcos_tables(greg)
-        gtt, gts_ = _fcos_tables(gctr)
-        assert list(gcs) == list(cs) and list(grs) == list(rs) and list(gts_) == list(ts)
+        ct, cs, _ = _level_tables(cls, 'fcos_loss')
+        rt, rs, _ = _level_tables(reg, 'fcos_loss')
+        tt, ts, _ = _level_tables(ctr, 'fcos_loss')
+        gcls, gct = _grad_maps(cls, cs, 'fcos_loss')
+        greg, grt = _grad_maps(reg, rs, 'fcos_loss')
+        gctr, gtt = _grad_maps(ctr, ts, 'fcos_loss')
         rows = capi.lib().htd_fcos_loss_partial_rows()
         partial = torch.empty(rows, 2, device=assigned.device, dtype=torch.float32)
         capi.call('htd_fcos_loss', ct, cs, rt, rs, tt, ts, hw, st, L, B, int(C), _P(gt_labels), K, _P(assigned), _P(bbox_targets),
@@ -1440,16 +1403,12 @@ class FcosLossFunction(Function):
     @once_differentiable
     def backward(ctx, g_cls, g_box, g_ctr):
         hw, st, L, B, C = ctx.meta
-        if getattr(ctx, 'scaled', False):
-            raise RuntimeError('fcos_loss: a second backward through the same forward (retain_graph=True) is not supported: '
-                               'the gradient maps were handed over and scaled in place by the first')
-        ctx.scaled = True
         grads = ctx.saved_tensors
-        gct, gcs = _fcos_tables(grads[:L])
-        grt, grs = _fcos_tables(grads[L:2 * L])
-        gtt, gts_ = _fcos_tables(grads[2 * L:])
-        capi.call('htd_fcos_grad_scale', gct, gcs, grt, grs, gtt, gts_, hw, st, L, B, C, _P(g_cls.float().contiguous()),
-                  _P(g_box.float().contiguous()), _P(g_ctr.float().contiguous()), _S())
+        gct, gcs, _ = _level_tables(grads[:L], 'fcos_loss')
+        grt, grs, _ = _level_tables(grads[L:2 * L], 'fcos_loss')
+        gtt, gts_, _ = _level_tables(grads[2 * L:], 'fcos_loss')
+        _hand_over_once(ctx, 'fcos_loss', 'htd_fcos_grad_scale', (gct, gcs, grt, grs, gtt, gts_, hw, st, L, B, C),
+                        (g_cls, g_box, g_ctr))
         return (None, ) * 15 + tuple(grads)
 
 
@@ -1474,8 +1433,8 @@ def fcos_keys(cls_maps, ctr_maps, strides):
     for m in list(cls_maps) + list(ctr_maps):
         _f32(m, 'fcos_keys')
     hw, st, P = _fcos_levels([m.shape[-2:] for m in cls_maps], strides)
-    ct, cs = _fcos_tables(cls_maps)
-    tt, ts = _fcos_tables(ctr_maps)
+    ct, cs, _ = _level_tables(cls_maps, 'fcos_keys')
+    tt, ts, _ = _level_tables(ctr_maps, 'fcos_keys')
     B = cls_maps[0].size(0)
     keys = torch.empty(B, P, device=cls_maps[0].device, dtype=torch.float32)
     capi.call('htd_fcos_keys', ct, cs, tt, ts, hw, st, len(cls_maps), B, cls_maps[0].size(1), _P(keys), _S())

@@ -245,8 +245,8 @@ def test_fused_loss_dispatch_rule():
     from htd_amd import mmcv_ops as M
     assert M.FCOS_BOX_KINDS == dict(IoULoss=0, GIoULoss=2)
     m = torch.zeros(2, 1, 4, 5)
-    assert M.fcos_channel_stride(m) == 1 and M.fcos_channel_stride(torch.zeros(2, 8, 4, 5)) is None
-    assert M.fcos_channel_stride(torch.zeros(2, 8, 4, 5).contiguous(memory_format=torch.channels_last)[:, :3]) == 8
+    assert M.nhwc_channel_stride(m) == 1 and M.nhwc_channel_stride(torch.zeros(2, 8, 4, 5)) is None
+    assert M.nhwc_channel_stride(torch.zeros(2, 8, 4, 5).contiguous(memory_format=torch.channels_last)[:, :3]) == 8
 
 
 def test_new_abi_symbols_are_declared_and_exported():

@@ -192,10 +192,10 @@ def _loss_raw(case, kind, gamma, alpha, weights, assigned=None):
     view = dict(cls=[m[:, :C] for m in wide['cls']], reg=[m[:, :4] for m in wide['reg']], ctr=[m[:, :1] for m in wide['ctr']])
     grads = {k: [torch.full_like(m, float('nan')) for m in v] for k, v in wide.items()}
     gview = dict(cls=[m[:, :C] for m in grads['cls']], reg=[m[:, :4] for m in grads['reg']], ctr=[m[:, :1] for m in grads['ctr']])
-    assert all(M.fcos_channel_stride(a) == b.size(1) for k in view for a, b in zip(view[k], wide[k]))
+    assert all(M.nhwc_channel_stride(a) == b.size(1) for k in view for a, b in zip(view[k], wide[k]))
     hw, st, P = M._fcos_levels(case['sizes'], case['strides'])
-    tabs = [M._fcos_tables(view[k]) for k in ('cls', 'reg', 'ctr')]
-    gtabs = [M._fcos_tables(gview[k])[0] for k in ('cls', 'reg', 'ctr')]
+    tabs = [M._level_tables(view[k]) for k in ('cls', 'reg', 'ctr')]
+    gtabs = [M._level_tables(gview[k])[0] for k in ('cls', 'reg', 'ctr')]
     assigned = (case['assigned'] if assigned is None else assigned).to(dev).to(torch.int32).contiguous()
     bt, ctr_t, labels = case['bt'].to(dev).contiguous(), case['ctr_t'].to(dev).contiguous(), case['labels'].to(dev).contiguous()
     n = int((assigned > 0).sum())

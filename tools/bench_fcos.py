@@ -65,9 +65,9 @@ def bench_kernel(dev, reps, warmup, batch):
     def targets():
         capi.call('htd_fcos_targets', hw, st, ranges, 5, capi.ptr(gts), capi.ptr(gt_valid), B, K, 0, 1.5, 0, capi.ptr(assigned),
                   capi.ptr(bt), capi.ptr(ct), capi.ptr(ws), capi.ptr(num_pos), capi.ptr(norm), stream)
-    tabs = [M._fcos_tables(m) for m in (cls, reg, ctr)]
+    tabs = [M._level_tables(m, 'bench_fcos') for m in (cls, reg, ctr)]
     grads = [[torch.empty_like(m) for m in ms] for ms in (cls, reg, ctr)]
-    gtabs = [M._fcos_tables(m)[0] for m in grads]
+    gtabs = [M._level_tables(m, 'bench_fcos')[0] for m in grads]
     partial = torch.empty(capi.lib().htd_fcos_loss_partial_rows(), 2, device=dev)
 
     def loss():

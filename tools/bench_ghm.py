@@ -58,11 +58,11 @@ def bench_kernel(dev, reps, warmup, batch):
     num_pos, avg = M.retina_avg_factor(assigned)
     B, A = assigned.shape
     L = len(cls)
-    ct, cs, pix = M._level_tables(cls)
-    rt, rs, _ = M._level_tables(reg)
+    ct, cs, pix = M._level_tables(cls, 'bench_ghm')
+    rt, rs, _ = M._level_tables(reg, 'bench_ghm')
     gcls, greg = [torch.empty_like(c) for c in cls], [torch.empty_like(r) for r in reg]
-    gct, _, _ = M._level_tables(gcls)
-    grt, _, _ = M._level_tables(greg)
+    gct, _, _ = M._level_tables(gcls, 'bench_ghm')
+    grt, _, _ = M._level_tables(greg, 'bench_ghm')
     partial = torch.empty(capi.lib().htd_focal_loss_partial_rows(), 2, device=dev)
     means, stds = (ctypes.c_float * 4)(0, 0, 0, 0), (ctypes.c_float * 4)(1, 1, 1, 1)
     stream = capi.current_stream_ptr()

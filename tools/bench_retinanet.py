@@ -86,11 +86,11 @@ def bench_kernel(dev, reps, warmup, batch):
     assigned, _ = batched_max_iou_assign(head.assigner, flat_anchors, inside, gts, gt_valid)
     num_pos, avg = M.retina_avg_factor(assigned)
     B, A = assigned.shape
-    ct, cs, pix = M._level_tables(cls)
-    rt, rs, _ = M._level_tables(reg)
+    ct, cs, pix = M._level_tables(cls, 'bench_retinanet')
+    rt, rs, _ = M._level_tables(reg, 'bench_retinanet')
     gcls, greg = [torch.empty_like(c) for c in cls], [torch.empty_like(r) for r in reg]
-    gct, _, _ = M._level_tables(gcls)
-    grt, _, _ = M._level_tables(greg)
+    gct, _, _ = M._level_tables(gcls, 'bench_retinanet')
+    grt, _, _ = M._level_tables(greg, 'bench_retinanet')
     partial = torch.empty(capi.lib().htd_focal_loss_partial_rows(), 2, device=dev)
     import ctypes
     means, stds = (ctypes.c_float * 4)(0, 0, 0, 0), (ctypes.c_float * 4)(1, 1, 1, 1)
