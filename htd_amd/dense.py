@@ -172,7 +172,12 @@ def grad_out2(like):
 OVERLAP_WGRAD = bool(int(__import__('os').environ.get('HTD_OVERLAP_WGRAD', '1')))
 _OVERLAP_IN_PROFILE = False
 _SIDE = {}
-_SIDE_CONSUMED = set()          # data_ptr of folded weights whose gradient is consumed by _BNFold.backward (side stream)
+# Folded weights whose gradient is consumed by _BNFold.backward (side stream): data_ptr -> (element count, the storage's
+# identity, weak reference to that storage), the pattern of _AMAX_BY_PTR below.  A folded weight is a temporary of one step, and
+# the allocator hands its address to other tensors afterwards: an entry answers for tensors over the storage it was made for
+# and for nothing else.  A wrong "no" costs one wait, a wrong "yes" lets autograd read a gradient that the side stream has not
+# written yet -- every doubtful case answers no.
+_SIDE_CONSUMED = {}
 
 
 class overlap_wgrad:
@@ -203,21 +208,45 @@ def side_stream(device=None):
 
 
 def mark_side_consumed(t):
-    _SIDE_CONSUMED.add(t.data_ptr())
+    st = t.untyped_storage()
+    _SIDE_CONSUMED[t.data_ptr()] = (t.numel(), st._cdata, _StorageWeakRef(st))
+
+
+def side_consumed(t):
+    """Was `t` -- this tensor or another view of all its elements, not a later tensor at its address -- marked?"""
+    e = _SIDE_CONSUMED.get(t.data_ptr())
+    if e is None:
+        return False
+    if e[2].expired():
+        del _SIDE_CONSUMED[t.data_ptr()]
+        return False
+    return e[0] == t.numel() and t.untyped_storage()._cdata == e[1] and _dense_layout(t)
+
+
+def _drop_dead_side_consumed():
+    for k in [k for k, e in _SIDE_CONSUMED.items() if e[2].expired()]:
+        del _SIDE_CONSUMED[k]
 
 
 # Flipped / transposed weight images produced ahead of time (bricks._BNFoldMany writes them with the folds of a whole
 # stage): offered under the folded weight's address during the forward pass, taken -- and removed -- by the autograd
 # node that will run the data gradient (ResStageFunction.forward), which keeps them with its saved tensors.
+# An image that nobody took (a stage whose forward raised) must not reach whatever weight has that address later: every offer
+# remembers the weight's shape and storage, take_flipped() refuses anything else, new_step() drops what is left.
 _FLIPPED = {}
 
 
 def offer_flipped(weight, wT):
-    _FLIPPED[weight.data_ptr()] = wT
+    st = weight.untyped_storage()
+    _FLIPPED[weight.data_ptr()] = (wT, tuple(weight.shape), st._cdata, _StorageWeakRef(st))
 
 
 def take_flipped(weight):
-    return _FLIPPED.pop(weight.data_ptr(), None)
+    e = _FLIPPED.pop(weight.data_ptr(), None)
+    if e is None or e[3].expired() or e[1] != tuple(weight.shape) or e[0].numel() != weight.numel() or \
+            weight.untyped_storage()._cdata != e[2]:
+        return None
+    return e[0]
 
 
 # Flipped / transposed weight images made during this step, by (address, version, shape, parameter epoch): a weight that several data gradients
@@ -244,6 +273,8 @@ def new_step():
     _STEP_PLANES.clear()
     _AMAX_POOL.clear()
     _AMAX_BY_PTR.clear()
+    _FLIPPED.clear()
+    _drop_dead_side_consumed()
     _drop_temp_sinks()
 
 
@@ -901,7 +932,7 @@ def _wgrad_raw(x, g, weight, stride, padding, dilation, bias=None, overlap=True)
     g.record_stream(side)
     with torch.cuda.stream(side):
         gw, gb, sinks = _wgrad_launch(x, g, weight, stride, padding, dilation, bias, amax)
-    if not sinks and weight.data_ptr() not in _SIDE_CONSUMED:
+    if not sinks and not side_consumed(weight):
         if gw is not None:
             gw.record_stream(main)
         if gb is not None:

@@ -371,16 +371,6 @@ def det(golden):
     return U.load_fixture_weights_(model, float(g['cls_scale'])).to(torch.device(DEV))
 
 
-@pytest.fixture(scope='module', autouse=True)
-def _retire_weight_images():
-    """The prepared weight images of the convolutions are cached under (address, version, shape, mmcv_ops.PARAM_EPOCH) of the
-    parameter: once this module's detector is freed, a later module's parameters can take the same addresses with the same
-    version and shape, so the epoch is moved on when the module ends."""
-    yield
-    from htd_amd import mmcv_ops as M
-    M.PARAM_EPOCH += 1
-
-
 def _reset(det):
     with torch.no_grad():
         det.bbox_head.loss_cls.acc_sum.zero_()

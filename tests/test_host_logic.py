@@ -385,6 +385,74 @@ def test_gradient_sinks_are_scoped_to_their_trainer():
     assert len(dense._GRAD_SINK) == n0
 
 
+def test_side_consumed_and_flipped_entries_answer_for_their_own_storage_only():
+    """dense.mark_side_consumed / side_consumed and offer_flipped / take_flipped are keyed by address and validated against the
+    storage the entry was made for (the part that needs no allocator: views, other shapes, partial views, copies, new_step and
+    reset_grad_sinks; the recycled address itself is tests/test_gpu_wgrad_stream.py)."""
+    from htd_amd import dense
+    CL = torch.channels_last
+    dense.reset_grad_sinks()
+    dense.new_step()
+    t = torch.randn(8, 4, 3, 3).contiguous(memory_format=CL)
+    assert not dense.side_consumed(t)
+    dense.mark_side_consumed(t)
+    assert dense.side_consumed(t) and dense.side_consumed(t.view_as(t)) and dense.side_consumed(t.permute(0, 2, 3, 1).permute(0, 3, 1, 2))
+    assert not dense.side_consumed(t[:4]) and not dense.side_consumed(t.clone())
+    big = torch.zeros(2 * t.numel())
+    dense.mark_side_consumed(big[:t.numel()])
+    assert not dense.side_consumed(big[:2 * t.numel():2])            # same address and element count, other elements
+    dense.new_step()
+    assert dense.side_consumed(t) and len(dense._SIDE_CONSUMED) == 2  # live entries survive a new step ...
+    del big
+    dense.new_step()
+    assert len(dense._SIDE_CONSUMED) == 1                             # ... dead ones do not
+    dense.reset_grad_sinks()
+    assert len(dense._SIDE_CONSUMED) == 0 and not dense.side_consumed(t)
+    wT = torch.empty(t.numel())
+    dense.offer_flipped(t, wT)
+    assert dense.take_flipped(t) is wT and dense.take_flipped(t) is None
+    dense.offer_flipped(t, wT)
+    assert dense.take_flipped(t.permute(0, 2, 3, 1).reshape(8, -1, 1, 1)) is None        # same address, other shape
+    dense.offer_flipped(t, wT)
+    assert dense.take_flipped(t[:4]) is None
+    dense.offer_flipped(t, wT)
+    dense.new_step()
+    assert len(dense._FLIPPED) == 0 and dense.take_flipped(t) is None
+
+
+def test_padded_gt_cache_holds_four_entries_and_their_lists():
+    """core.bbox._PAD_GT_LAST: keyed by address, version and shape of every tensor of the lists and holding the lists, so an
+    address cannot be recycled under a live key; at most four entries (the fifth insert clears), and boxes modified in place
+    (version bump) miss."""
+    import gc
+    import weakref
+    from htd_amd.core import bbox as BX
+    assert BX._PAD_GT_CACHE
+    BX._PAD_GT_LAST.clear()
+    g = torch.Generator().manual_seed(4)
+    lists = [[torch.rand(3, 4, generator=g), torch.rand(2, 4, generator=g)] for _ in range(5)]
+    labels = [torch.tensor([1, 2, 3]), torch.tensor([4, 5])]
+    outs = [BX.pad_gt_batch(l) for l in lists[:4]]
+    assert len(BX._PAD_GT_LAST) == 4
+    assert all(BX.pad_gt_batch(l) is o for l, o in zip(lists[:4], outs))             # served: the same objects
+    assert BX.pad_gt_batch(lists[0], labels) is not outs[0] and len(BX._PAD_GT_LAST) == 1     # other key: the fifth insert clears
+    outs = [BX.pad_gt_batch(l) for l in lists[1:4]]
+    assert len(BX._PAD_GT_LAST) == 4
+    alive = weakref.ref(lists[1][0])
+    lists[1] = None
+    gc.collect()
+    assert alive() is not None                                        # the entry keeps its tensors
+    o4 = BX.pad_gt_batch(lists[4])
+    gc.collect()
+    assert len(BX._PAD_GT_LAST) == 1 and alive() is None
+    assert BX.pad_gt_batch(lists[4]) is o4
+    lists[4][0].mul_(2.0)                                             # in place: same address and shape, new version
+    o5 = BX.pad_gt_batch(lists[4])
+    assert o5 is not o4 and len(BX._PAD_GT_LAST) == 2
+    assert torch.equal(o5[0][0, :3], lists[4][0]) and torch.equal(o5[0][1, :2], lists[4][1]) and not bool(o5[1][1, 2])
+    BX._PAD_GT_LAST.clear()
+
+
 def test_split_heads_backward_equals_slicing():
     """rpn_head._SplitHeads: channel slices of the merged 1x1 head; its one-concatenation backward equals what autograd
     computes for two plain slices (including a head that received no gradient)."""
