@@ -7,7 +7,8 @@ The two baselines HTD is measured against come the same way: faster_rcnn_config 
 faster_rcnn_r50_fpn_1x_coco.py) and cascade_rcnn_config (configs/cascade_rcnn/cascade_rcnn_r50_fpn_1x_coco.py), with
 their `_base_` chains merged, and so do the single-stage baselines retinanet_config (configs/retinanet/
 retinanet_r50_fpn_1x_coco.py), its GHM variant retinanet_ghm_config (configs/ghm/retinanet_ghm_r50_fpn_1x_coco.py) and
-fcos_config (the two configs/fcos/fcos_*_r50_caffe_fpn_gn-head_4x4_1x_coco.py).
+fcos_config (the two configs/fcos/fcos_*_r50_caffe_fpn_gn-head_4x4_1x_coco.py) and atss_config (configs/atss/
+atss_r50_fpn_1x_coco.py and its R101 sibling).
 """
 import copy
 
@@ -251,6 +252,34 @@ def fcos_config(depth=50, variant='gn-head'):
     return cfg
 
 
+def atss_model(depth=50):
+    """configs/atss/atss_r50_fpn_1x_coco.py: P3-P7 with P6 / P7 by convolutions on the output P5, one square anchor of 8 strides
+    per location, a GroupNorm(32) ATSSHead with a centerness-weighted GIoULoss of weight 2 on decoded boxes."""
+    return dict(
+        type='ATSS', pretrained=f'torchvision://resnet{depth}', backbone=htd_model(depth)['backbone'],
+        neck=dict(type='FPN', in_channels=[256, 512, 1024, 2048], out_channels=256, start_level=1, add_extra_convs='on_output',
+                  num_outs=5),
+        bbox_head=dict(type='ATSSHead', num_classes=80, in_channels=256, stacked_convs=4, feat_channels=256,
+                       anchor_generator=dict(type='AnchorGenerator', ratios=[1.0], octave_base_scale=8, scales_per_octave=1,
+                                             strides=[8, 16, 32, 64, 128]),
+                       bbox_coder=dict(type='DeltaXYWHBBoxCoder', target_means=[.0, .0, .0, .0],
+                                       target_stds=[0.1, 0.1, 0.2, 0.2]),
+                       loss_cls=dict(type='FocalLoss', use_sigmoid=True, gamma=2.0, alpha=0.25, loss_weight=1.0),
+                       loss_bbox=dict(type='GIoULoss', loss_weight=2.0),
+                       loss_centerness=dict(type='CrossEntropyLoss', use_sigmoid=True, loss_weight=1.0)))
+
+
+def atss_config(depth=50):
+    """atss_r{depth}_fpn_1x_coco: ATSSAssigner with the nine nearest anchors per level and gt, every anchor a sample, lr 0.01, no
+    gradient clipping, the linear warm-up of schedule_1x: `python -m htd_amd.train` takes it as it is."""
+    cfg = _baseline_config(atss_model(depth),
+                           dict(assigner=dict(type='ATSSAssigner', topk=9), allowed_border=-1, pos_weight=-1, debug=False), depth)
+    cfg.test_cfg = ConfigDict(nms_pre=1000, min_bbox_size=0, score_thr=0.05, nms=dict(type='nms', iou_threshold=0.6),
+                              max_per_img=100)
+    cfg.optimizer.lr = 0.01
+    return cfg
+
+
 IMG_NORM_CFG = dict(mean=[123.675, 116.28, 103.53], std=[58.395, 57.12, 57.375], to_rgb=True)
 
 
@@ -362,11 +391,12 @@ def build_htd_detector(depth=50, dcn=False, cfg=None, bf16=False, resnext=False)
 
 
 def build_baseline_detector(kind='faster_rcnn', depth=50, cfg=None, bf16=False):
-    """kind = 'faster_rcnn' | 'cascade_rcnn' | 'faster_rcnn_gn_ws' | 'fcos' | 'fcos_center' -> the detector of faster_rcnn_config /
-    cascade_rcnn_config / faster_rcnn_gn_ws_config / fcos_config (its two variants) (or of `cfg`), with the `pretrained` URL of the
+    """kind = 'faster_rcnn' | 'cascade_rcnn' | 'faster_rcnn_gn_ws' | 'fcos' | 'fcos_center' | 'atss' -> the detector of
+    faster_rcnn_config / cascade_rcnn_config / faster_rcnn_gn_ws_config / fcos_config (its two variants) / atss_config (or of
+    `cfg`), with the `pretrained` URL of the
     reference's config dropped: weights come from a checkpoint or from init_weights.  bf16 as in build_htd_detector."""
     makers = dict(faster_rcnn=faster_rcnn_config, cascade_rcnn=cascade_rcnn_config, faster_rcnn_gn_ws=faster_rcnn_gn_ws_config,
-                  fcos=fcos_config, fcos_center=lambda d: fcos_config(d, 'center-normbbox-centeronreg-giou'))
+                  fcos=fcos_config, fcos_center=lambda d: fcos_config(d, 'center-normbbox-centeronreg-giou'), atss=atss_config)
     if cfg is None:
         if kind not in makers:
             raise ValueError(f'build_baseline_detector: kind must be one of {sorted(makers)}, got {kind!r}')

@@ -136,6 +136,121 @@ class MaxIoUAssigner:
         return AssignResult(num_gts, assigned, max_overlaps, labels=labels)
 
 
+@BBOX_ASSIGNERS.register_module()
+class ATSSAssigner:
+    """mmdet/core/bbox/assigners/atss_assigner.py:10-178.  Per gt and pyramid level the min(topk, n_level) boxes whose centres
+    lie nearest the gt centre are candidates; a candidate is positive when its IoU reaches the mean + (unbiased) standard
+    deviation of the gt's candidate IoUs and its centre lies more than 0.01 inside the gt; a box positive for several gts
+    goes to the one of highest IoU.
+
+    torch.topk and torch.max leave ties undefined, so the rule is declared here and every form (`assign`,
+    `batched_atss_assign`'s tensor form, htd_atss_targets) follows it: candidates are taken in the order (distance, box
+    index) -- the distance in fp32 where the form computes in fp32 --, a box goes to the gt of (highest IoU, lowest gt
+    index), and a gt with a single candidate has a NaN threshold (the unbiased deviation of one value) and gets no
+    positive, as in the reference."""
+
+    def __init__(self, topk, iou_calculator=dict(type='BboxOverlaps2D'), ignore_iof_thr=-1):
+        self.topk, self.ignore_iof_thr = topk, ignore_iof_thr
+        self.iou_calculator = build_iou_calculator(iou_calculator)
+
+    def assign(self, bboxes, num_level_bboxes, gt_bboxes, gt_bboxes_ignore=None, gt_labels=None):
+        """atss_assigner.py:33-178 step for step, in the dtype of its inputs (the tests run it on CPU tensors in fp64)."""
+        INF = 100000000
+        bboxes = bboxes[:, :4]
+        num_gt, num_bboxes = gt_bboxes.size(0), bboxes.size(0)
+        overlaps = self.iou_calculator(bboxes, gt_bboxes)
+        assigned_gt_inds = overlaps.new_full((num_bboxes, ), 0, dtype=torch.long)
+        if num_gt == 0 or num_bboxes == 0:
+            labels = None if gt_labels is None else overlaps.new_full((num_bboxes, ), -1, dtype=torch.long)
+            return AssignResult(num_gt, assigned_gt_inds, overlaps.new_zeros((num_bboxes, )), labels=labels)
+        gt_points = torch.stack(((gt_bboxes[:, 0] + gt_bboxes[:, 2]) / 2.0, (gt_bboxes[:, 1] + gt_bboxes[:, 3]) / 2.0), dim=1)
+        bboxes_cx, bboxes_cy = (bboxes[:, 0] + bboxes[:, 2]) / 2.0, (bboxes[:, 1] + bboxes[:, 3]) / 2.0
+        bboxes_points = torch.stack((bboxes_cx, bboxes_cy), dim=1)
+        distances = (bboxes_points[:, None, :] - gt_points[None, :, :]).pow(2).sum(-1).sqrt()
+        if (self.ignore_iof_thr > 0 and gt_bboxes_ignore is not None and gt_bboxes_ignore.numel() > 0
+                and bboxes.numel() > 0):
+            ignore_max, _ = self.iou_calculator(bboxes, gt_bboxes_ignore, mode='iof').max(dim=1)
+            ignore_idxs = ignore_max > self.ignore_iof_thr
+            distances[ignore_idxs, :] = INF
+            assigned_gt_inds[ignore_idxs] = -1
+        candidate_idxs, start = [], 0
+        for n_level in num_level_bboxes:
+            selectable_k = min(self.topk, n_level)
+            # the first selectable_k of the order (distance, box index)
+            order = distances[start:start + n_level, :].sort(dim=0, stable=True)[1]
+            candidate_idxs.append(order[:selectable_k] + start)
+            start += n_level
+        candidate_idxs = torch.cat(candidate_idxs, dim=0)                       # (candidates, num_gt)
+        gt_ar = torch.arange(num_gt, device=overlaps.device)
+        candidate_overlaps = overlaps[candidate_idxs, gt_ar]
+        thr = candidate_overlaps.mean(0) + candidate_overlaps.std(0)
+        is_pos = candidate_overlaps >= thr[None, :]
+        cx, cy = bboxes_cx[candidate_idxs], bboxes_cy[candidate_idxs]
+        ltrb = torch.stack([cx - gt_bboxes[:, 0], cy - gt_bboxes[:, 1], gt_bboxes[:, 2] - cx, gt_bboxes[:, 3] - cy], dim=1)
+        is_pos = is_pos & (ltrb.min(dim=1)[0] > 0.01)
+        overlaps_inf = torch.full_like(overlaps, -INF)
+        cols = gt_ar[None, :].expand_as(candidate_idxs)
+        overlaps_inf[candidate_idxs[is_pos], cols[is_pos]] = candidate_overlaps[is_pos]
+        max_overlaps = overlaps_inf.max(dim=1)[0]
+        # (highest IoU, lowest gt index)
+        argmax_overlaps = torch.where(overlaps_inf == max_overlaps[:, None], gt_ar[None, :], gt_ar.new_full((1, ), num_gt)).min(1)[0]
+        hit = max_overlaps != -INF
+        assigned_gt_inds[hit] = argmax_overlaps[hit] + 1
+        labels = None
+        if gt_labels is not None:
+            labels = assigned_gt_inds.new_full((num_bboxes, ), -1)
+            pos = assigned_gt_inds > 0
+            labels[pos] = gt_labels[assigned_gt_inds[pos] - 1]
+        return AssignResult(num_gt, assigned_gt_inds, max_overlaps, labels=labels)
+
+
+def batched_atss_assign(assigner, anchors, level_sizes, gts, gt_valid):
+    """ATSSAssigner.assign for B images at once, every anchor a candidate (no ignore boxes).  anchors (A, 4) shared by all
+    images, level-major; level_sizes: anchors per level (host); gts (B, K, 4) zero-padded; gt_valid (B, K).
+    -> assigned (B, A): 0 background, k + 1 = gt k.  fp32 GPU anchors with at most 8 levels and topk <= 16 take
+    htd_atss_targets; everything else the tensor form, which has no Python loop over gts and reads nothing on the host.
+    The tie rule is ATSSAssigner's."""
+    assert assigner.ignore_iof_thr <= 0
+    if anchors.is_cuda and anchors.dtype == torch.float32 and len(level_sizes) <= 8 and assigner.topk <= 16:
+        from .. import mmcv_ops as M
+        return M.atss_targets(anchors, level_sizes, gts, gt_valid, assigner.topk)[0]
+    return _batched_atss_assign_tensor(assigner, anchors, level_sizes, gts, gt_valid)
+
+
+def _batched_atss_assign_tensor(a, anchors, level_sizes, gts, gt_valid):
+    B, K = gt_valid.shape
+    A = anchors.size(0)
+    assert sum(level_sizes) == A
+    dev = anchors.device
+    g = gts.to(anchors.dtype)
+    area_a = (anchors[:, 2] - anchors[:, 0]) * (anchors[:, 3] - anchors[:, 1])
+    area_g = (g[..., 2] - g[..., 0]) * (g[..., 3] - g[..., 1])
+    wh = (torch.min(anchors[None, None, :, 2:], g[:, :, None, 2:]) - torch.max(anchors[None, None, :, :2], g[:, :, None, :2])).clamp(min=0)
+    overlap = wh[..., 0] * wh[..., 1]
+    union = torch.max(area_a[None, None, :] + area_g[:, :, None] - overlap, const_tensor([1e-6], dev, overlap.dtype))
+    iou = overlap / union                                                   # (B, K, A) == bbox_overlaps(anchors, gt).t()
+    acx, acy = (anchors[:, 0] + anchors[:, 2]) / 2.0, (anchors[:, 1] + anchors[:, 3]) / 2.0
+    gcx, gcy = (g[..., 0] + g[..., 2]) / 2.0, (g[..., 1] + g[..., 3]) / 2.0
+    dist = ((acx[None, None, :] - gcx[:, :, None]).pow(2) + (acy[None, None, :] - gcy[:, :, None]).pow(2)).sqrt()
+    cand, start = [], 0
+    for n in level_sizes:
+        order = dist[:, :, start:start + n].sort(dim=2, stable=True)[1]       # (distance, anchor index)
+        cand.append(order[:, :, :min(a.topk, n)] + start)
+        start += n
+    cand = torch.cat(cand, 2)                                               # (B, K, M)
+    cand_iou = torch.gather(iou, 2, cand)
+    thr = cand_iou.mean(2) + cand_iou.std(2)                                # one candidate: NaN, no positive
+    cx, cy = acx[cand], acy[cand]
+    inside = torch.stack([cx - g[:, :, None, 0], cy - g[:, :, None, 1], g[:, :, None, 2] - cx, g[:, :, None, 3] - cy], -1).min(-1)[0]
+    is_pos = (cand_iou >= thr[:, :, None]) & (inside > 0.01) & gt_valid[:, :, None]
+    # the candidates of one (image, gt) are distinct anchors: a plain scatter
+    score = torch.full_like(iou, -1.0).scatter(2, cand, torch.where(is_pos, cand_iou, cand_iou.new_full((1, ), -1.0)))
+    best = score.max(1)[0]                                                  # (B, A)
+    ks = arange_cached(K, dev).view(1, K, 1)
+    k_of = torch.where(score == best[:, None, :], ks, ks.new_full((1, ), K)).min(1)[0]     # (highest IoU, lowest gt index)
+    return torch.where(best >= 0, k_of + 1, torch.zeros_like(k_of))
+
+
 # ------------------------------------------------------------------ sampler
 def _device_randperm(n, device):
     return torch.randperm(n, device=device)

@@ -1,4 +1,4 @@
-"""mmdet/core/utils/misc.py:7-39."""
+"""mmdet/core/utils/misc.py:7-39 and dist_utils.py (reduce_mean)."""
 from functools import partial
 
 import torch
@@ -14,6 +14,17 @@ def unmap(data, count, inds, fill=0):
     ret = data.new_full((count, ) + tuple(data.shape[1:]), fill)
     ret[inds.type(torch.bool)] = data
     return ret
+
+
+def reduce_mean(tensor):
+    """mmdet/core/utils/dist_utils.py: the mean of `tensor` over the processes of the default group -- an all-reduce of a
+    copy divided by the world size -- and the tensor itself where no process group is initialised.  No host read."""
+    import torch.distributed as dist
+    if not (dist.is_available() and dist.is_initialized()):
+        return tensor
+    tensor = tensor.clone()
+    dist.all_reduce(tensor.div_(dist.get_world_size()), op=dist.ReduceOp.SUM)
+    return tensor
 
 
 _CONSTS = {}

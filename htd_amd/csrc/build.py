@@ -17,7 +17,8 @@ COMMON = ['--offload-arch=' + ARCH, '-O3', '-fPIC', '-std=c++17', '-Wall', '-Wno
 EXTRA = {'nms.hip': ['-ffp-contract=off'], 'box_ops.hip': ['-ffp-contract=off'],
          'image_pipeline.hip': ['-ffp-contract=off'], 'coco_eval.hip': ['-ffp-contract=off'],
          'voc_eval.hip': ['-ffp-contract=off'], 'fcos.hip': ['-ffp-contract=off'],
-         'ghm_loss.hip': ['-ffp-contract=off']}     # its two passes must bin an element alike
+         'ghm_loss.hip': ['-ffp-contract=off'],     # its two passes must bin an element alike
+         'atss.hip': ['-ffp-contract=off']}         # distances and IoUs one rounded operation at a time
 
 
 # Every *.hip / *.cpp of this directory is a translation unit of the library; what each one replaces (include/htd_amd.h cites
@@ -27,7 +28,9 @@ EXTRA = {'nms.hip': ['-ffp-contract=off'], 'box_ops.hip': ['-ffp-contract=off'],
 #   ghm_loss.hip     GHMC / GHMR (mmdet/models/losses/ghm_loss.py:20-172) and AnchorHead.loss with the pair (the level table,
 #                    map decoding and box targets of focal_loss.hip, shared through retina_levels.h)
 #   fcos.hip         FCOSHead's targets, loss and ranking keys (dense_heads/fcos_head.py:159-253,364-372,415-576)
-# The three share focal_elem.h (the element arithmetic) and loss_units.h (level search, VEC-wide units, matrix units).
+#   atss.hip         ATSSAssigner over a batch with the centerness targets and averaging factors, and ATSSHead's loss
+#                    (core/bbox/assigners/atss_assigner.py:33-178, dense_heads/atss_head.py:145-313)
+# The four share focal_elem.h (the element arithmetic) and loss_units.h (level search, VEC-wide units, matrix units).
 def sources():
     return sorted(f for f in os.listdir(HERE) if f.endswith('.hip') or f.endswith('.cpp'))
 

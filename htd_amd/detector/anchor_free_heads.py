@@ -16,7 +16,8 @@ permute, concatenation or gather of the predictions, no nonzero(), no host read.
 
 `get_bboxes` handles the whole batch on the GPU: one key launch (htd_fcos_keys) and one segmented top-k give every (image, level)
 cut to nms_pre, one gather, one multiclass NMS over all images with the centerness as score factor; the decode stays
-distance2bbox image by image, so the result is bit-identical to the per-image loop, which ranks by the same launch form.
+distance2bbox image by image, so the result is bit-identical to the per-image loop, which ranks by the same launch form.  The
+code is BaseDenseHead's (`_ctr_get_bboxes`), which ATSSHead shares.
 """
 import os
 
@@ -321,112 +322,26 @@ class FCOSHead(AnchorFreeHead):
         return dict(loss_cls=loss_cls, loss_bbox=loss_bbox, loss_centerness=loss_centerness)
 
     # ------------------------------------------------------------------ boxes
+    @staticmethod
+    def _decode(points, distances, img_shape):
+        return distance2bbox(points, distances, max_shape=img_shape)
+
     @torch.no_grad()
     def get_bboxes(self, cls_scores, bbox_preds, centernesses, img_metas, cfg=None, rescale=False, with_nms=True):
-        """fcos_head.py:255-401 -> list (per image) of (dets (k, 5), labels (k,)).  GPU fp32 maps with hard NMS take the batched
-        form; everything else the per-image loop."""
-        cfg = self.test_cfg if cfg is None else cfg
-        assert len(cls_scores) == len(bbox_preds) == len(centernesses)
-        nms_pre = cfg.get('nms_pre', -1)
-        Ns = [int(c.shape[2] * c.shape[3]) for c in cls_scores]
-        maps = list(cls_scores) + list(bbox_preds) + list(centernesses)
-        batched = with_nms and cls_scores[0].is_cuda and len(cls_scores) <= 8 and all(t.dtype == torch.float32 for t in maps) and \
-            cfg.nms.get('type', 'nms') == 'nms' and (nms_pre <= 0 or nms_pre <= M.TOPK_KMAX) and \
-            getattr(self, 'batched_get_bboxes', True) and (nms_pre > 0 or max(Ns) <= M.TOPK_KMAX)
-        if batched:
-            return self._get_bboxes_batched(cls_scores, bbox_preds, centernesses, img_metas, cfg, rescale)
+        """fcos_head.py:255-401 -> list (per image) of (dets (k, 5), labels (k,)): BaseDenseHead._ctr_get_bboxes with the points
+        as priors and distance2bbox as decode.  GPU fp32 maps with hard NMS take the batched form; everything else the
+        per-image loop."""
         featmap_sizes = [c.shape[-2:] for c in cls_scores]
-        mlvl_points = self.get_points(featmap_sizes, bbox_preds[0].dtype, bbox_preds[0].device)
-        out = []
-        for b, meta in enumerate(img_metas):
-            out.append(self._get_bboxes_single([c[b].detach() for c in cls_scores], [r[b].detach() for r in bbox_preds],
-                                               [t[b].detach() for t in centernesses], mlvl_points, meta['img_shape'],
-                                               meta['scale_factor'], cfg, rescale, with_nms))
-        return out
+        dev = cls_scores[0].device
 
-    def _level_keys(self, cls_score_list, centerness_list):
-        """per level (n_l,) max_c sigmoid(score) * sigmoid(centerness): htd_fcos_keys on the GPU (the same launch form as the
-        batched path, so the two rank identically), the reference's tensor operations elsewhere."""
-        if cls_score_list[0].is_cuda and cls_score_list[0].dtype == torch.float32 and len(cls_score_list) <= 8:
-            keys = M.fcos_keys([c[None] for c in cls_score_list], [t[None] for t in centerness_list], self.strides)[0]
-            return list(keys.split([int(c.shape[1] * c.shape[2]) for c in cls_score_list]))
-        out = []
-        for c, t in zip(cls_score_list, centerness_list):
-            s = c.permute(1, 2, 0).reshape(-1, self.cls_out_channels).sigmoid()
-            out.append((s * t.permute(1, 2, 0).reshape(-1).sigmoid()[:, None]).max(dim=1)[0])
-        return out
+        def flat_points():
+            return self._cached('_points_cache', 32, (self._shape_key(featmap_sizes), str(dev)),
+                                lambda: torch.cat(self.get_points(featmap_sizes, torch.float32, dev)))
+        return self._ctr_get_bboxes(cls_scores, bbox_preds, centernesses, img_metas, cfg, rescale, with_nms, self.strides,
+                                    lambda: self.get_points(featmap_sizes, bbox_preds[0].dtype, dev), flat_points, self._decode)
 
     def _get_bboxes_single(self, cls_scores, bbox_preds, centernesses, mlvl_points, img_shape, scale_factor, cfg, rescale=False,
                            with_nms=True):
         """fcos_head.py:315-401 for one image."""
-        from ..core.post_processing import multiclass_nms
-        cfg = self.test_cfg if cfg is None else cfg
-        assert len(cls_scores) == len(bbox_preds) == len(mlvl_points)
-        nms_pre = cfg.get('nms_pre', -1)
-        keys = self._level_keys(cls_scores, centernesses) if nms_pre > 0 and any(p.size(0) > nms_pre for p in mlvl_points) else None
-        mlvl_bboxes, mlvl_scores, mlvl_centerness = [], [], []
-        for lvl, (cls_score, bbox_pred, centerness, points) in enumerate(zip(cls_scores, bbox_preds, centernesses, mlvl_points)):
-            assert cls_score.size()[-2:] == bbox_pred.size()[-2:]
-            scores = cls_score.permute(1, 2, 0).reshape(-1, self.cls_out_channels).sigmoid()
-            centerness = centerness.permute(1, 2, 0).reshape(-1).sigmoid()
-            bbox_pred = bbox_pred.permute(1, 2, 0).reshape(-1, 4)
-            if nms_pre > 0 and scores.shape[0] > nms_pre:
-                # the first nms_pre of the stable descending order (equal keys: lower point index first)
-                topk_inds = keys[lvl].sort(descending=True, stable=True)[1][:nms_pre]
-                points, bbox_pred = points[topk_inds, :], bbox_pred[topk_inds, :]
-                scores, centerness = scores[topk_inds, :], centerness[topk_inds]
-            mlvl_bboxes.append(distance2bbox(points, bbox_pred, max_shape=img_shape))
-            mlvl_scores.append(scores)
-            mlvl_centerness.append(centerness)
-        mlvl_bboxes = torch.cat(mlvl_bboxes)
-        if rescale:
-            mlvl_bboxes = mlvl_bboxes / mlvl_bboxes.new_tensor(scale_factor)
-        mlvl_scores = torch.cat(mlvl_scores)
-        mlvl_scores = torch.cat([mlvl_scores, mlvl_scores.new_zeros(mlvl_scores.shape[0], 1)], dim=1)
-        mlvl_centerness = torch.cat(mlvl_centerness)
-        if with_nms:
-            return multiclass_nms(mlvl_bboxes, mlvl_scores, cfg.score_thr, cfg.nms, cfg.max_per_img, score_factors=mlvl_centerness)
-        return mlvl_bboxes, mlvl_scores, mlvl_centerness
-
-    def _get_bboxes_batched(self, cls_scores, bbox_preds, centernesses, img_metas, cfg, rescale):
-        from ..core.post_processing import multiclass_nms_images
-        B, L = cls_scores[0].size(0), len(cls_scores)
-        dev = cls_scores[0].device
-        C = self.cls_out_channels
-        featmap_sizes = [c.shape[-2:] for c in cls_scores]
-        nms_pre = cfg.get('nms_pre', -1)
-        Ns = [int(c.shape[2] * c.shape[3]) for c in cls_scores]
-        ks = [n if nms_pre <= 0 else min(nms_pre, n) for n in Ns]
-        offs = [sum(Ns[:l]) for l in range(L)]
-        total = sum(Ns)
-        cls_scores = [c.detach() for c in cls_scores]
-        centernesses = [t.detach() for t in centernesses]
-        points = self._cached('_points_cache', 32, (self._shape_key(featmap_sizes), str(dev)),
-                              lambda: torch.cat(self.get_points(featmap_sizes, torch.float32, dev)))
-        cut = [l for l in range(L) if ks[l] < Ns[l]]
-        pieces = [torch.arange(offs[l], offs[l] + Ns[l], device=dev)[None].expand(B, Ns[l]) for l in range(L)]
-        if cut:
-            # every (image, level) cut of the call in one key launch and one segmented top-k; a level that is not cut keeps its
-            # points in their own order, as the per-image form does
-            keys = M.fcos_keys(cls_scores, centernesses, self.strides)                # (B, total)
-            top_idx, _ = M.segmented_topk(keys, [(b * total + offs[l], Ns[l], ks[l]) for b in range(B) for l in cut])
-            top_idx, at = top_idx.view(B, -1), 0
-            for l in cut:
-                pieces[l] = top_idx[:, at:at + ks[l]] + offs[l]
-                at += ks[l]
-        gidx = torch.cat(pieces, 1)
-        K = gidx.size(1)
-        logits = torch.cat([c.permute(0, 2, 3, 1).reshape(B, -1, C) for c in cls_scores], 1)
-        dists = torch.cat([r.detach().permute(0, 2, 3, 1).reshape(B, -1, 4) for r in bbox_preds], 1)
-        ctrs = torch.cat([t.permute(0, 2, 3, 1).reshape(B, -1) for t in centernesses], 1)
-        scores = torch.gather(logits, 1, gidx[..., None].expand(B, K, C)).sigmoid()
-        dists = torch.gather(dists, 1, gidx[..., None].expand(B, K, 4))
-        ctrs = torch.gather(ctrs, 1, gidx).sigmoid()
-        boxes = torch.stack([distance2bbox(points[gidx[b]], dists[b], max_shape=img_metas[b]['img_shape']) for b in range(B)])
-        if rescale:
-            boxes = torch.stack([boxes[b] / boxes.new_tensor(img_metas[b]['scale_factor']) for b in range(B)])
-        scores = torch.cat([scores, scores.new_zeros(B, K, 1)], dim=2)
-        img_of = torch.arange(B, device=dev).repeat_interleave(K)
-        dets, labels = multiclass_nms_images(boxes.reshape(B * K, 4), scores.reshape(B * K, C + 1), img_of, B, cfg.score_thr,
-                                             cfg.nms, cfg.max_per_img, score_factors=ctrs.reshape(B * K))
-        return list(zip(dets, labels))
+        return self._ctr_bboxes_single(cls_scores, bbox_preds, centernesses, mlvl_points, self._decode, self.strides, img_shape,
+                                       scale_factor, cfg, rescale, with_nms)

@@ -1,8 +1,9 @@
-"""Anchor-based dense heads of single-stage detectors: AnchorHead and RetinaHead.
+"""Anchor-based dense heads of single-stage detectors: AnchorHead, RetinaHead and ATSSHead.
 
 Reference: dense_heads/anchor_head.py:14-682 (AnchorHead: forward, get_anchors, get_targets, loss, get_bboxes),
-base_dense_head.py:22-59 (forward_train), retina_head.py:8-114 (RetinaHead).  Same registry names, constructor kwargs,
-state_dict keys (cls_convs / reg_convs / retina_cls / retina_reg) and return structures.  AnchorHead is also the base of RPNHead
+base_dense_head.py:22-59 (forward_train), retina_head.py:8-114 (RetinaHead), atss_head.py:15-650 (ATSSHead).  Same registry
+names, constructor kwargs, state_dict keys (cls_convs / reg_convs / retina_cls / retina_reg; atss_cls / atss_reg /
+atss_centerness / scales.N.scale) and return structures.  AnchorHead is also the base of RPNHead
 (detector/rpn_head.py), as in the reference: anchors, per-image targets (gt_labels None: foreground is class 0), the
 reference-order loss are written once, here; forward_train, simple_test and the cache of constants of the pyramid's map shapes
 (`_shape_key` makes their key, `_cached` fetches them) come from BaseDenseHead (detector/base_dense_head.py), which the
@@ -27,7 +28,7 @@ import os
 import torch
 import torch.nn as nn
 
-from ..core import anchor_inside_flags, images_to_levels, multi_apply, unmap
+from ..core import anchor_inside_flags, images_to_levels, multi_apply, reduce_mean, unmap
 from ..core.misc import const_tensor
 from .. import mmcv_ops as M
 from ..registry import HEADS, build_anchor_generator, build_assigner, build_bbox_coder, build_loss, build_sampler
@@ -36,6 +37,8 @@ from .bricks import Conv2d, ConvModule, normal_init
 from .losses import GHM_KERNEL_BINS, GHMC, GHMR
 
 RETINA_FUSED = os.environ.get('HTD_RETINA_FUSED', '1') != '0'       # 0: the tensor-path loss (A/B runs)
+ATSS_FUSED = os.environ.get('HTD_ATSS_FUSED', '1') != '0'           # the same switch for ATSSHead
+ATSS_EPS = 1e-12                                                    # atss_head.py:12
 
 
 def bias_init_with_prob(prior_prob):
@@ -415,3 +418,266 @@ class RetinaHead(AnchorHead):
         for reg_conv in self.reg_convs:
             reg_feat = reg_conv(reg_feat)
         return self.retina_cls(cls_feat), self.retina_reg(reg_feat)
+
+
+@HEADS.register_module()
+class ATSSHead(AnchorHead):
+    """dense_heads/atss_head.py:15-650: the towers of RetinaHead under GroupNorm, a centerness branch on the regression tower,
+    one learnable scale per level, ATSSAssigner in place of MaxIoUAssigner and a centerness-weighted IoU-family box loss on
+    decoded boxes.
+
+    `loss` has two forms, like AnchorHead.loss, and `_fused_loss_ok` is the one rule between them.  `loss_tensor` is the
+    reference's order of operations (get_targets / _get_target_single on the inside-flag subset, loss_single per level, the two
+    averaging factors through reduce_mean) and works on the CPU, in fp64, with several anchors per location and with ignore
+    boxes.  `loss_fused` assigns the whole batch and leaves the centerness targets and the averaging factors on the device
+    (htd_atss_targets), and takes the three losses and the three gradient maps of all levels in one more launch (htd_atss_loss)
+    that reads the maps where they are: no permute, concatenation or gather of the predictions, no nonzero(), no host read.
+
+    `get_bboxes` is BaseDenseHead._ctr_get_bboxes, shared with FCOSHead, with the anchors as priors and the coder's decode."""
+
+    def __init__(self, num_classes, in_channels, stacked_convs=4, conv_cfg=None,
+                 norm_cfg=dict(type='GN', num_groups=32, requires_grad=True),
+                 loss_centerness=dict(type='CrossEntropyLoss', use_sigmoid=True, loss_weight=1.0), **kwargs):
+        self.stacked_convs, self.conv_cfg, self.norm_cfg = stacked_convs, conv_cfg, norm_cfg
+        super().__init__(num_classes, in_channels, **kwargs)
+        self.sampling = False
+        if self.train_cfg:
+            self.assigner = build_assigner(self.train_cfg.assigner)
+            self.sampler = build_sampler(dict(type='PseudoSampler'), context=self)
+        self.loss_centerness = build_loss(loss_centerness)
+
+    def _init_layers(self):
+        from .anchor_free_heads import Scale
+        self.relu = nn.ReLU(inplace=True)
+        self.cls_convs = nn.ModuleList()
+        self.reg_convs = nn.ModuleList()
+        for i in range(self.stacked_convs):
+            chn = self.in_channels if i == 0 else self.feat_channels
+            self.cls_convs.append(ConvModule(chn, self.feat_channels, 3, stride=1, padding=1, conv_cfg=self.conv_cfg,
+                                             norm_cfg=self.norm_cfg))
+            self.reg_convs.append(ConvModule(chn, self.feat_channels, 3, stride=1, padding=1, conv_cfg=self.conv_cfg,
+                                             norm_cfg=self.norm_cfg))
+        self.atss_cls = Conv2d(self.feat_channels, self.num_anchors * self.cls_out_channels, 3, padding=1)
+        self.atss_reg = Conv2d(self.feat_channels, self.num_anchors * 4, 3, padding=1)
+        self.atss_centerness = Conv2d(self.feat_channels, self.num_anchors * 1, 3, padding=1)
+        self.scales = nn.ModuleList([Scale(1.0) for _ in self.anchor_generator.strides])
+
+    def init_weights(self):
+        for m in list(self.cls_convs) + list(self.reg_convs):
+            normal_init(m.conv, std=0.01)
+        normal_init(self.atss_cls, std=0.01, bias=bias_init_with_prob(0.01))
+        normal_init(self.atss_reg, std=0.01)
+        normal_init(self.atss_centerness, std=0.01)
+
+    # ------------------------------------------------------------------ forward
+    def forward(self, feats):
+        return multi_apply(self.forward_single, feats, self.scales)
+
+    def forward_single(self, x, scale):
+        """atss_head.py:116-143 -> cls_score, bbox_pred (scaled, no exp), centerness (on the regression tower)."""
+        if x.dtype != torch.float32:             # a bf16 pyramid: the towers and all box / loss arithmetic stay fp32
+            x = x.float()
+        cls_feat = reg_feat = x
+        for cls_conv in self.cls_convs:
+            cls_feat = cls_conv(cls_feat)
+        for reg_conv in self.reg_convs:
+            reg_feat = reg_conv(reg_feat)
+        return self.atss_cls(cls_feat), scale(self.atss_reg(reg_feat)).float(), self.atss_centerness(reg_feat)
+
+    # ------------------------------------------------------------------ targets
+    def centerness_target(self, anchors, bbox_targets):
+        """atss_head.py:297-313 (positives only: elsewhere there may be NaN)."""
+        gts = self.bbox_coder.decode(anchors, bbox_targets)
+        anchors_cx, anchors_cy = (anchors[:, 2] + anchors[:, 0]) / 2, (anchors[:, 3] + anchors[:, 1]) / 2
+        left_right = torch.stack([anchors_cx - gts[:, 0], gts[:, 2] - anchors_cx], dim=1)
+        top_bottom = torch.stack([anchors_cy - gts[:, 1], gts[:, 3] - anchors_cy], dim=1)
+        return torch.sqrt((left_right.min(dim=-1)[0] / left_right.max(dim=-1)[0]) *
+                          (top_bottom.min(dim=-1)[0] / top_bottom.max(dim=-1)[0]))
+
+    def get_num_level_anchors_inside(self, num_level_anchors, inside_flags):
+        return [int(flags.sum()) for flags in torch.split(inside_flags, num_level_anchors)]
+
+    def _get_target_single(self, flat_anchors, valid_flags, num_level_anchors, gt_bboxes, gt_bboxes_ignore, gt_labels, img_meta,
+                           label_channels=1, unmap_outputs=True):
+        """atss_head.py:535-643 for one image."""
+        inside = anchor_inside_flags(flat_anchors, valid_flags, img_meta['img_shape'][:2], self.train_cfg.allowed_border)
+        if not inside.any():
+            return (None, ) * 7
+        anchors = flat_anchors[inside, :]
+        num_level_anchors_inside = self.get_num_level_anchors_inside(num_level_anchors, inside)
+        assign_result = self.assigner.assign(anchors, num_level_anchors_inside, gt_bboxes, gt_bboxes_ignore, gt_labels)
+        sr = self.sampler.sample(assign_result, anchors, gt_bboxes)
+        n = anchors.shape[0]
+        bbox_targets = torch.zeros_like(anchors)
+        bbox_weights = torch.zeros_like(anchors)
+        labels = anchors.new_full((n, ), self.num_classes, dtype=torch.long)
+        label_weights = anchors.new_zeros(n, dtype=torch.float)
+        pos_inds, neg_inds = sr.pos_inds, sr.neg_inds
+        if len(pos_inds) > 0:
+            bbox_targets[pos_inds, :] = self.bbox_coder.encode(sr.pos_bboxes, sr.pos_gt_bboxes)
+            bbox_weights[pos_inds, :] = 1.0
+            labels[pos_inds] = 0 if gt_labels is None else gt_labels[sr.pos_assigned_gt_inds]
+            label_weights[pos_inds] = 1.0 if self.train_cfg.pos_weight <= 0 else self.train_cfg.pos_weight
+        if len(neg_inds) > 0:
+            label_weights[neg_inds] = 1.0
+        if unmap_outputs:
+            total = flat_anchors.size(0)
+            anchors = unmap(anchors, total, inside)
+            labels = unmap(labels, total, inside, fill=self.num_classes)
+            label_weights = unmap(label_weights, total, inside)
+            bbox_targets = unmap(bbox_targets, total, inside)
+            bbox_weights = unmap(bbox_weights, total, inside)
+        return anchors, labels, label_weights, bbox_targets, bbox_weights, pos_inds, neg_inds
+
+    def get_targets(self, anchor_list, valid_flag_list, gt_bboxes_list, img_metas, gt_bboxes_ignore_list=None,
+                    gt_labels_list=None, label_channels=1, unmap_outputs=True):
+        """atss_head.py:471-533 -> (anchors, labels, label_weights, bbox_targets, bbox_weights per level, num_total_pos,
+        num_total_neg)."""
+        num_imgs = len(img_metas)
+        assert len(anchor_list) == len(valid_flag_list) == num_imgs
+        num_level_anchors = [a.size(0) for a in anchor_list[0]]
+        concat_anchors = [torch.cat(a) for a in anchor_list]
+        concat_valid = [torch.cat(v) for v in valid_flag_list]
+        if gt_bboxes_ignore_list is None:
+            gt_bboxes_ignore_list = [None] * num_imgs
+        if gt_labels_list is None:
+            gt_labels_list = [None] * num_imgs
+        res = [self._get_target_single(concat_anchors[i], concat_valid[i], num_level_anchors, gt_bboxes_list[i],
+                                       gt_bboxes_ignore_list[i], gt_labels_list[i], img_metas[i], label_channels, unmap_outputs)
+               for i in range(num_imgs)]
+        if any(r[1] is None for r in res):
+            return None
+        num_total_pos = sum(max(r[5].numel(), 1) for r in res)
+        num_total_neg = sum(max(r[6].numel(), 1) for r in res)
+        lv = [images_to_levels([r[k] for r in res], num_level_anchors) for k in range(5)]
+        return lv[0], lv[1], lv[2], lv[3], lv[4], num_total_pos, num_total_neg
+
+    # ------------------------------------------------------------------ loss
+    def loss_single(self, anchors, cls_score, bbox_pred, centerness, labels, label_weights, bbox_targets, num_total_samples):
+        """atss_head.py:145-218."""
+        anchors = anchors.reshape(-1, 4)
+        cls_score = cls_score.permute(0, 2, 3, 1).reshape(-1, self.cls_out_channels).contiguous()
+        bbox_pred = bbox_pred.permute(0, 2, 3, 1).reshape(-1, 4)
+        centerness = centerness.permute(0, 2, 3, 1).reshape(-1)
+        bbox_targets = bbox_targets.reshape(-1, 4)
+        labels = labels.reshape(-1)
+        label_weights = label_weights.reshape(-1)
+        loss_cls = self.loss_cls(cls_score, labels, label_weights, avg_factor=num_total_samples)
+        pos_inds = ((labels >= 0) & (labels < self.num_classes)).nonzero().squeeze(1)
+        if len(pos_inds) > 0:
+            pos_bbox_targets, pos_bbox_pred = bbox_targets[pos_inds], bbox_pred[pos_inds]
+            pos_anchors, pos_centerness = anchors[pos_inds], centerness[pos_inds]
+            centerness_targets = self.centerness_target(pos_anchors, pos_bbox_targets)
+            loss_bbox = self.loss_bbox(self.bbox_coder.decode(pos_anchors, pos_bbox_pred),
+                                       self.bbox_coder.decode(pos_anchors, pos_bbox_targets), weight=centerness_targets,
+                                       avg_factor=1.0)
+            loss_centerness = self.loss_centerness(pos_centerness, centerness_targets, avg_factor=num_total_samples)
+        else:
+            loss_bbox = bbox_pred.sum() * 0
+            loss_centerness = centerness.sum() * 0
+            centerness_targets = bbox_targets.new_tensor(0.)
+        return loss_cls, loss_bbox, loss_centerness, centerness_targets.sum()
+
+    def loss(self, cls_scores, bbox_preds, centernesses, gt_bboxes, gt_labels, img_metas, gt_bboxes_ignore=None):
+        if self._fused_loss_ok(cls_scores, bbox_preds, centernesses, gt_labels, gt_bboxes_ignore, img_metas):
+            return self.loss_fused(cls_scores, bbox_preds, centernesses, gt_bboxes, gt_labels, img_metas)
+        return self.loss_tensor(cls_scores, bbox_preds, centernesses, gt_bboxes, gt_labels, img_metas, gt_bboxes_ignore)
+
+    def loss_tensor(self, cls_scores, bbox_preds, centernesses, gt_bboxes, gt_labels, img_metas, gt_bboxes_ignore=None):
+        """atss_head.py:220-295, in the reference's order of operations."""
+        featmap_sizes = [f.size()[-2:] for f in cls_scores]
+        assert len(featmap_sizes) == self.anchor_generator.num_levels
+        device = cls_scores[0].device
+        anchor_list, valid_flag_list = self.get_anchors(featmap_sizes, img_metas, device=device)
+        label_channels = self.cls_out_channels if self.use_sigmoid_cls else 1
+        targets = self.get_targets(anchor_list, valid_flag_list, gt_bboxes, img_metas, gt_bboxes_ignore_list=gt_bboxes_ignore,
+                                   gt_labels_list=gt_labels, label_channels=label_channels)
+        if targets is None:
+            return None
+        anchors, labels, label_weights, bbox_targets, _, num_total_pos, _ = targets
+        num_total_samples = float(reduce_mean(torch.tensor(float(num_total_pos), device=device)))
+        num_total_samples = max(num_total_samples, 1.0)
+        losses_cls, losses_bbox, loss_centerness, bbox_avg_factor = multi_apply(
+            self.loss_single, anchors, cls_scores, bbox_preds, centernesses, labels, label_weights, bbox_targets,
+            num_total_samples=num_total_samples)
+        bbox_avg_factor = float(reduce_mean(sum(bbox_avg_factor)))
+        if bbox_avg_factor < ATSS_EPS:
+            bbox_avg_factor = 1
+        losses_bbox = [x / bbox_avg_factor for x in losses_bbox]
+        return dict(loss_cls=losses_cls, loss_bbox=losses_bbox, loss_centerness=loss_centerness)
+
+    def _atss_consts(self, featmap_sizes, img_metas, dev):
+        """-> (A, 4) level-concatenated anchors and whether every anchor of every image is valid and inside (a host bool, read
+        once per (map sizes, image shapes))."""
+        def make():
+            flat_anchors, inside = self._anchors_inside(featmap_sizes, img_metas, dev)
+            return flat_anchors.float().contiguous(), bool(inside.all())
+        key = (self._shape_key(featmap_sizes), tuple((tuple(m['img_shape'][:2]), tuple(m['pad_shape'][:2])) for m in img_metas),
+               str(dev), self.train_cfg.allowed_border)
+        return self._cached('_atss_cache', 64, key, make)
+
+    def _fused_loss_ok(self, cls_scores, bbox_preds, centernesses, gt_labels, gt_bboxes_ignore, img_metas):
+        """htd_atss_targets / htd_atss_loss cover one anchor per location (several tie in distance), every anchor valid and
+        inside, no ignore boxes, label weight 1 on positives (pos_weight <= 0: the kernel has no other), sigmoid FocalLoss +
+        IoULoss / GIoULoss + sigmoid CrossEntropyLoss without class weight, all with mean reduction, a DeltaXYWHBBoxCoder and fp32 channels_last GPU maps of at most 8 levels."""
+        lc, lb, lt = self.loss_cls, self.loss_bbox, self.loss_centerness
+        a = getattr(self, 'assigner', None)
+        ok = getattr(self, 'fused_loss', ATSS_FUSED) and gt_labels is not None and gt_bboxes_ignore is None and \
+            self.num_anchors == 1 and type(a).__name__ == 'ATSSAssigner' and a.ignore_iof_thr <= 0 and a.topk <= 16 and \
+            type(lc).__name__ == 'FocalLoss' and lc.use_sigmoid and lc.reduction == 'mean' and \
+            self.train_cfg.pos_weight <= 0 and \
+            type(lb).__name__ in M.FCOS_BOX_KINDS and lb.reduction == 'mean' and \
+            type(lt).__name__ == 'CrossEntropyLoss' and lt.use_sigmoid and lt.reduction == 'mean' and lt.class_weight is None and \
+            type(self.bbox_coder).__name__ == 'DeltaXYWHBBoxCoder' and not self.reg_decoded_bbox and len(cls_scores) <= 8 and \
+            all(t.is_cuda and t.dtype == torch.float32 and M.nhwc_channel_stride(t) is not None
+                for t in list(cls_scores) + list(bbox_preds) + list(centernesses))
+        if not ok:
+            return False
+        return self._atss_consts([f.size()[-2:] for f in cls_scores], img_metas, cls_scores[0].device)[1]
+
+    def loss_fused(self, cls_scores, bbox_preds, centernesses, gt_bboxes, gt_labels, img_metas):
+        import torch.distributed as dist
+        from ..core.bbox import pad_gt_batch
+        featmap_sizes = [f.size()[-2:] for f in cls_scores]
+        assert len(featmap_sizes) == self.anchor_generator.num_levels
+        flat_anchors, _ = self._atss_consts(featmap_sizes, img_metas, cls_scores[0].device)
+        gts, gt_valid, labels = pad_gt_batch(gt_bboxes, gt_labels)
+        means, stds = tuple(self.bbox_coder.means), tuple(self.bbox_coder.stds)
+        targets = M.atss_targets(flat_anchors, [int(h * w) for h, w in featmap_sizes], gts, gt_valid, self.assigner.topk, means, stds)
+        assigned, ctr_targets, num_pos, norm = targets
+        if dist.is_available() and dist.is_initialized():
+            # atss_head.py:271-273,288: both factors averaged over the processes, the sample count at least 1
+            norm = reduce_mean(norm)
+            norm = torch.cat([norm[:2].clamp(min=1.0), norm[2:]])
+            targets = (assigned, ctr_targets, num_pos, norm)
+        self._last_targets = targets            # exposed for tests
+        lc, lb = self.loss_cls, self.loss_bbox
+        loss_cls, loss_bbox, loss_centerness = M.atss_loss(
+            cls_scores, bbox_preds, centernesses, self.anchor_generator.strides, flat_anchors, gts, labels, assigned, ctr_targets,
+            norm, means, stds, M.FCOS_BOX_KINDS[type(lb).__name__], lb.eps, lc.gamma, lc.alpha, lc.loss_weight, lb.loss_weight,
+            self.loss_centerness.loss_weight)
+        return dict(loss_cls=loss_cls, loss_bbox=loss_bbox, loss_centerness=loss_centerness)
+
+    # ------------------------------------------------------------------ boxes
+    def _decode(self, anchors, deltas, img_shape):
+        return self.bbox_coder.decode(anchors, deltas, max_shape=img_shape)
+
+    @torch.no_grad()
+    def get_bboxes(self, cls_scores, bbox_preds, centernesses, img_metas, cfg=None, rescale=False, with_nms=True):
+        """atss_head.py:316-469 -> list (per image) of (dets (k, 5), labels (k,)), the centerness as score factor of the NMS.
+        Several anchors per location take the per-image loop with the reference's own tensor operations."""
+        featmap_sizes = [c.shape[-2:] for c in cls_scores]
+        dev = cls_scores[0].device
+
+        def flat_anchors():
+            return self._cached('_bbox_cache', 32, (self._shape_key(featmap_sizes), str(dev)),
+                                lambda: torch.cat(self.anchor_generator.grid_anchors(featmap_sizes, device=dev)))
+        return self._ctr_get_bboxes(cls_scores, bbox_preds, centernesses, img_metas, cfg, rescale, with_nms,
+                                    self.anchor_generator.strides,
+                                    lambda: self.anchor_generator.grid_anchors(featmap_sizes, device=dev), flat_anchors, self._decode)
+
+    def _get_bboxes_single(self, cls_scores, bbox_preds, centernesses, mlvl_anchors, img_shape, scale_factor, cfg, rescale=False,
+                           with_nms=True):
+        """atss_head.py:379-469 for one image."""
+        return self._ctr_bboxes_single(cls_scores, bbox_preds, centernesses, mlvl_anchors, self._decode, self.anchor_generator.strides,
+                                       img_shape, scale_factor, cfg, rescale, with_nms)

@@ -1,7 +1,7 @@
-"""SingleStageDetector, RetinaNet and FCOS.
+"""SingleStageDetector, RetinaNet, FCOS and ATSS.
 
 Reference: detectors/single_stage.py:9-149 (extract_feat :52-57, forward_train :68-96, simple_test :98-124),
-detectors/retinanet.py:5-17, detectors/fcos.py:5-17.  The dense head does the work (detector/anchor_heads.py,
+detectors/retinanet.py:5-17, detectors/fcos.py:5-17, detectors/atss.py:5-17.  The dense head does the work (detector/anchor_heads.py,
 anchor_free_heads.py); results of a batch leave the device in one copy (core.bbox.bbox2result_many).
 """
 from ..core.bbox import bbox2result_many
@@ -60,6 +60,14 @@ class RetinaNet(SingleStageDetector):
 @DETECTORS.register_module()
 class FCOS(SingleStageDetector):
     """detectors/fcos.py:5-17."""
+
+    def __init__(self, backbone, neck, bbox_head, train_cfg=None, test_cfg=None, pretrained=None):
+        super().__init__(backbone, neck, bbox_head, train_cfg, test_cfg, pretrained)
+
+
+@DETECTORS.register_module()
+class ATSS(SingleStageDetector):
+    """detectors/atss.py:5-17."""
 
     def __init__(self, backbone, neck, bbox_head, train_cfg=None, test_cfg=None, pretrained=None):
         super().__init__(backbone, neck, bbox_head, train_cfg, test_cfg, pretrained)

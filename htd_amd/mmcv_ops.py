@@ -1439,3 +1439,91 @@ def fcos_keys(cls_maps, ctr_maps, strides):
     keys = torch.empty(B, P, device=cls_maps[0].device, dtype=torch.float32)
     capi.call('htd_fcos_keys', ct, cs, tt, ts, hw, st, len(cls_maps), B, cls_maps[0].size(1), _P(keys), _S())
     return keys
+
+
+# ====================================================================== ATSS head (dense_heads/atss_head.py)
+def atss_targets(anchors, level_sizes, gts, gt_valid, topk, means=(0., 0., 0., 0.), stds=(1., 1., 1., 1.),
+                 wh_ratio_clip=16 / 1000):
+    """htd_atss_targets: ATSSAssigner.assign, ATSSHead.centerness_target and the averaging factors of ATSSHead.loss for the whole
+    batch, nothing read back.  anchors (A, 4) float32 level-major, one per location; level_sizes: anchors per level (host);
+    gts (B, K, 4) float32 / gt_valid (B, K) bool as pad_gt_batch leaves them.  -> assigned (B, A) int32 (0 background, k + 1 =
+    gt k), ctr_targets (B, A), num_pos (B,) int32, norm (3,) = [sum_b max(num_pos_b, 1), the same, sum ctr_targets]."""
+    from .core.bbox import _d4
+    _need_gpu(anchors, 'atss_targets')
+    anchors = _f32(anchors, 'atss_targets').contiguous()
+    gts = _f32(gts, 'atss_targets').contiguous()
+    gt_valid = gt_valid.to(torch.bool).contiguous()
+    B, K = gt_valid.shape
+    A = anchors.size(0)
+    if sum(int(n) for n in level_sizes) != A:
+        raise ValueError(f'atss_targets: the levels hold {sum(level_sizes)} anchors, the tensor {A}')
+    dev = anchors.device
+    assigned = torch.empty(B, A, dtype=torch.int32, device=dev)
+    ctr_targets = torch.empty(B, A, dtype=torch.float32, device=dev)
+    num_pos = torch.empty(B, dtype=torch.int32, device=dev)
+    norm = torch.empty(3, dtype=torch.float32, device=dev)
+    ws = torch.empty(capi.lib().htd_atss_targets_workspace_bytes(B, A) // 8, dtype=torch.float64, device=dev)
+    capi.call('htd_atss_targets', _P(anchors), _i64s(level_sizes), len(level_sizes), _P(gts), _P(gt_valid), B, K, int(topk),
+              _d4(means), _d4(stds), float(wh_ratio_clip), _P(assigned), _P(ctr_targets), _P(ws), _P(num_pos), _P(norm), _S())
+    return assigned, ctr_targets, num_pos, norm
+
+
+class AtssLossFunction(Function):
+    """htd_atss_loss: the three losses of ATSSHead.loss over every level and image in one launch, which also writes the three
+    finished gradient maps (loss weight and normaliser applied); backward hands them over, after htd_fcos_grad_scale (the
+    layouts are FCOS's) applies incoming gradients other than 1 on the device, in place.  Single use: a second backward through
+    the same forward raises."""
+
+    @staticmethod
+    def forward(ctx, hw, st, sizes, C, anchors, gts, gt_labels, assigned, ctr_targets, norm, means, stds, wh_ratio_clip, box_kind,
+                eps, gamma, alpha, cls_weight, box_weight, ctr_weight, *maps):
+        from .core.bbox import _d4
+        L = len(maps) // 3
+        cls, reg, ctr = maps[:L], maps[L:2 * L], maps[2 * L:]
+        B, K = gt_labels.shape
+        ct, cs, _ = _level_tables(cls, 'atss_loss')
+        rt, rs, _ = _level_tables(reg, 'atss_loss')
+        tt, ts, _ = _level_tables(ctr, 'atss_loss')
+        gcls, gct = _grad_maps(cls, cs, 'atss_loss')
+        greg, grt = _grad_maps(reg, rs, 'atss_loss')
+        gctr, gtt = _grad_maps(ctr, ts, 'atss_loss')
+        rows = capi.lib().htd_atss_loss_partial_rows()
+        partial = torch.empty(rows, 2, device=assigned.device, dtype=torch.float32)
+        capi.call('htd_atss_loss', ct, cs, rt, rs, tt, ts, sizes, L, B, int(C), _P(anchors), _P(gts), _P(gt_labels), K, _P(assigned),
+                  _P(ctr_targets), _P(norm), _d4(means), _d4(stds), float(wh_ratio_clip), int(box_kind), float(eps), float(gamma),
+                  float(alpha), float(cls_weight), float(box_weight), float(ctr_weight), _P(partial), gct, grt, gtt, _S())
+        ctx.meta = (hw, st, L, B, int(C))
+        ctx.save_for_backward(*gcls, *greg, *gctr)
+        sums = partial.view(2, rows // 2, 2).sum(1)             # [[focal, box], [centerness, 0]]
+        box_norm = torch.where(norm[2] < 1e-12, torch.ones_like(norm[2]), norm[2])      # atss_head.py:289-290
+        return sums[0, 0] / norm[0] * cls_weight, sums[0, 1] / box_norm * box_weight, sums[1, 0] / norm[1] * ctr_weight
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_cls, g_box, g_ctr):
+        hw, st, L, B, C = ctx.meta
+        grads = ctx.saved_tensors
+        gct, gcs, _ = _level_tables(grads[:L], 'atss_loss')
+        grt, grs, _ = _level_tables(grads[L:2 * L], 'atss_loss')
+        gtt, gts_, _ = _level_tables(grads[2 * L:], 'atss_loss')
+        _hand_over_once(ctx, 'atss_loss', 'htd_fcos_grad_scale', (gct, gcs, grt, grs, gtt, gts_, hw, st, L, B, C),
+                        (g_cls, g_box, g_ctr))
+        return (None, ) * 20 + tuple(grads)
+
+
+def atss_loss(cls_maps, reg_maps, ctr_maps, strides, anchors, gts, gt_labels, assigned, ctr_targets, norm, means, stds, box_kind,
+              eps=1e-6, gamma=2.0, alpha=0.25, cls_weight=1.0, box_weight=1.0, ctr_weight=1.0, wh_ratio_clip=16 / 1000):
+    """-> (loss_cls, loss_bbox, loss_centerness) of an ATSS head with one anchor per location from its per-level (B, C, h, w) /
+    (B, 4, h, w) / (B, 1, h, w) maps, the (A, 4) anchors, the padded gts and the outputs of atss_targets.  box_kind:
+    FCOS_BOX_KINDS[type of the box loss]."""
+    _need_gpu(assigned, 'atss_loss')
+    for m in list(cls_maps) + list(reg_maps) + list(ctr_maps):
+        _f32(m, 'atss_loss')
+    hw, st, A = _fcos_levels([m.shape[-2:] for m in cls_maps], strides)
+    if assigned.shape != (cls_maps[0].size(0), A) or assigned.dtype != torch.int32 or anchors.shape != (A, 4):
+        raise ValueError(f'atss_loss: assigned must be int32 of shape {(cls_maps[0].size(0), A)}, anchors float32 {(A, 4)}')
+    sizes = _i64s([int(m.shape[-2] * m.shape[-1]) for m in cls_maps])
+    return AtssLossFunction.apply(hw, st, sizes, cls_maps[0].size(1), _f32(anchors, 'atss_loss').contiguous(),
+                                  _f32(gts, 'atss_loss').contiguous(), gt_labels.contiguous(), assigned.contiguous(),
+                                  ctr_targets.contiguous(), norm, means, stds, wh_ratio_clip, box_kind, eps, gamma, alpha,
+                                  cls_weight, box_weight, ctr_weight, *cls_maps, *reg_maps, *ctr_maps)

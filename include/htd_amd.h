@@ -766,6 +766,48 @@ int htd_fcos_grad_scale(float *const *grad_cls, const int64_t *cls_stride, float
 int htd_fcos_keys(const float *const *cls, const int64_t *cls_stride, const float *const *ctr, const int64_t *ctr_stride,
                   const int64_t *hw, const int64_t *strides, int L, int B, int C, float *keys, void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * ATSS head (core/bbox/assigners/atss_assigner.py, dense_heads/atss_head.py).  anchors [A][4] are the level-concatenated
+ * anchors of the pyramid, ONE per location, shared by all images; level_sizes [L] HOST = anchors per level (L <= 8).  gts
+ * [B][K][4] and gt_valid [B][K] are padded as pad_gt_batch leaves them.  means4 / stds4 HOST (doubles; rounded to fp32 where
+ * the reference's fp32 tensors hold them) and wh_ratio_clip are the DeltaXYWHBBoxCoder's.  Maps are HOST tables of L device pointers to channels_last maps [B][pixels][channel stride] read in
+ * place, as for the FCOS head: classification (C channels), regression (4 deltas) and centerness (1).
+ * The ranking keys of ATSSHead._get_bboxes_single (atss_head.py:433-440) are htd_fcos_keys, and incoming gradients other than 1
+ * are applied by htd_fcos_grad_scale: the layouts are the same.
+ * ---------------------------------------------------------------------------------- */
+/* ATSSAssigner.assign (atss_assigner.py:33-178) of the whole batch with every anchor valid and no ignore boxes, the centerness
+ * targets of ATSSHead.centerness_target (atss_head.py:297-313) and the averaging factors of ATSSHead.loss (:271-273,287-290),
+ * with nothing read back.  IoUs (eps 1e-6) and centre distances are the reference's fp32 values; per (gt, level) the
+ * min(topk, n_level) anchors first in the order (distance, anchor index) of the whole level are candidates (topk <= 16); the
+ * threshold is mean + unbiased standard deviation of the gt's candidate IoUs in two fixed-order fp32 passes (one candidate: NaN,
+ * no positive); a candidate with IoU >= threshold whose centre has min(l, t, r, b) > 0.01 inside the gt is positive; an anchor
+ * positive for several gts goes to (highest IoU, lowest gt index).
+ *   assigned [B][A]      0 = background, k + 1 = gt k
+ *   ctr_targets [B][A]   centerness of delta2bbox(anchor, bbox2delta(anchor, gt)) in the reference's fp32 order (logarithm
+ *                        and exponential: the fp32 rounding of the fp64 function) on positives, 0 elsewhere
+ *   num_pos [B], norm [3] = {sum_b max(num_pos_b, 1), the same, sum of ctr_targets} in a fixed summation order
+ * workspace: htd_atss_targets_workspace_bytes(B, A) bytes, 8-byte aligned.  Every output element is written. */
+int64_t htd_atss_targets_workspace_bytes(int B, int64_t A);
+int htd_atss_targets(const float *anchors, const int64_t *level_sizes, int L, const float *gts, const uint8_t *gt_valid,
+                     int B, int K, int topk, const double *means4, const double *stds4, double wh_ratio_clip, int *assigned,
+                     float *ctr_targets, void *workspace, int *num_pos, float *norm, void *stream);
+/* ATSSHead.loss / loss_single (atss_head.py:145-295) over all levels in one launch: the sigmoid focal loss of every anchor with
+ * the label gt_labels[b][assigned - 1] (background: none) and label weight 1; per positive the box loss of delta2bbox(anchor,
+ * bbox_pred) against delta2bbox(anchor, bbox2delta(anchor, gt)) -- box_kind 0 = IoULoss, 2 = GIoULoss, as htd_fcos_loss --
+ * weighted by ctr_targets; and BCE-with-logits of the centerness against ctr_targets.
+ * partial [htd_atss_loss_partial_rows()][2]: rows 0 .. n/2 - 1 = per-block {sum focal, sum weighted box loss}, rows n/2 .. =
+ * {sum centerness BCE, 0}, unscaled (add in row order: reproducible).  The gradient maps (layout of their inputs) receive
+ * d(cls_weight * focal / norm[0]), d(box_weight * box / (norm[2] < 1e-12 ? 1 : norm[2])) -- the reference's bbox_avg_factor
+ * rule, decided on the device -- and d(ctr_weight * bce / norm[1]); every element is written exactly once, zeros (padding
+ * channels, non-positive anchors) included.  Without positives the box and centerness sums and gradients are exactly 0. */
+int htd_atss_loss_partial_rows(void);
+int htd_atss_loss(const float *const *cls, const int64_t *cls_stride, const float *const *reg, const int64_t *reg_stride,
+                  const float *const *ctr, const int64_t *ctr_stride, const int64_t *level_sizes, int L, int B, int C,
+                  const float *anchors, const float *gts, const int64_t *gt_labels, int K, const int *assigned,
+                  const float *ctr_targets, const float *norm, const double *means4, const double *stds4, double wh_ratio_clip,
+                  int box_kind, double eps, float gamma, float alpha, float cls_weight, float box_weight, float ctr_weight,
+                  float *partial, float *const *grad_cls, float *const *grad_reg, float *const *grad_ctr, void *stream);
+
 /* nn.MaxPool2d(kernel, stride, padding) of the ResNet stem (backbones/resnet.py:509,629) on NHWC maps
  * x [B][H][W][C] -> y [B][Ho][Wo][C], C % 4 == 0, padding = -inf, floor mode.  idx (may be NULL for inference; int32
  * [B][Ho][Wo][C]) records the input pixel hi*W+wi of the first maximum of each window; bwd sends the gradient there
