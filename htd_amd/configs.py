@@ -7,8 +7,9 @@ The two baselines HTD is measured against come the same way: faster_rcnn_config 
 faster_rcnn_r50_fpn_1x_coco.py) and cascade_rcnn_config (configs/cascade_rcnn/cascade_rcnn_r50_fpn_1x_coco.py), with
 their `_base_` chains merged, and so do the single-stage baselines retinanet_config (configs/retinanet/
 retinanet_r50_fpn_1x_coco.py), its GHM variant retinanet_ghm_config (configs/ghm/retinanet_ghm_r50_fpn_1x_coco.py) and
-fcos_config (the two configs/fcos/fcos_*_r50_caffe_fpn_gn-head_4x4_1x_coco.py) and atss_config (configs/atss/
-atss_r50_fpn_1x_coco.py and its R101 sibling).
+fcos_config (the two configs/fcos/fcos_*_r50_caffe_fpn_gn-head_4x4_1x_coco.py), atss_config (configs/atss/
+atss_r50_fpn_1x_coco.py and its R101 sibling) and gfl_config (configs/gfl/gfl_r50_fpn_1x_coco.py and the mstrain 2x schedule
+of gfl_r101_fpn_mstrain_2x_coco.py).
 """
 import copy
 
@@ -280,6 +281,41 @@ def atss_config(depth=50):
     return cfg
 
 
+def gfl_model(depth=50):
+    """configs/gfl/gfl_r50_fpn_1x_coco.py: ATSS's backbone, neck and one-anchor pyramid under a GFLHead -- QualityFocalLoss on the
+    joint class / quality score, 17 bins per side (reg_max 16) under DistributionFocalLoss of weight 0.25, GIoULoss of weight 2
+    on the integral-decoded boxes."""
+    return dict(
+        type='GFL', pretrained=f'torchvision://resnet{depth}', backbone=htd_model(depth)['backbone'],
+        neck=dict(type='FPN', in_channels=[256, 512, 1024, 2048], out_channels=256, start_level=1, add_extra_convs='on_output',
+                  num_outs=5),
+        bbox_head=dict(type='GFLHead', num_classes=80, in_channels=256, stacked_convs=4, feat_channels=256,
+                       anchor_generator=dict(type='AnchorGenerator', ratios=[1.0], octave_base_scale=8, scales_per_octave=1,
+                                             strides=[8, 16, 32, 64, 128]),
+                       loss_cls=dict(type='QualityFocalLoss', use_sigmoid=True, beta=2.0, loss_weight=1.0),
+                       loss_dfl=dict(type='DistributionFocalLoss', loss_weight=0.25), reg_max=16,
+                       loss_bbox=dict(type='GIoULoss', loss_weight=2.0)))
+
+
+def gfl_config(depth=50, mstrain=False):
+    """gfl_r{depth}_fpn_1x_coco, or with mstrain gfl_r{depth}_fpn_mstrain_2x_coco: ATSS's training and test settings and lr 0.01;
+    the multi-scale schedule trains 24 epochs with steps at 16 / 22 on a short side drawn from [480, 800] (Resize in `range`
+    mode): `python -m htd_amd.train` takes either as it is."""
+    cfg = _baseline_config(gfl_model(depth),
+                           dict(assigner=dict(type='ATSSAssigner', topk=9), allowed_border=-1, pos_weight=-1, debug=False), depth)
+    cfg.test_cfg = ConfigDict(nms_pre=1000, min_bbox_size=0, score_thr=0.05, nms=dict(type='nms', iou_threshold=0.6),
+                              max_per_img=100)
+    cfg.optimizer.lr = 0.01
+    if mstrain:
+        cfg.lr_config.step = [16, 22]
+        cfg.total_epochs = 24
+        resize = cfg.data.train.pipeline[2]
+        assert resize['type'] == 'Resize'
+        cfg.data.train.pipeline[2] = ConfigDict(type='Resize', img_scale=[(1333, 480), (1333, 800)], multiscale_mode='range',
+                                                keep_ratio=True)
+    return cfg
+
+
 IMG_NORM_CFG = dict(mean=[123.675, 116.28, 103.53], std=[58.395, 57.12, 57.375], to_rgb=True)
 
 
@@ -391,12 +427,13 @@ def build_htd_detector(depth=50, dcn=False, cfg=None, bf16=False, resnext=False)
 
 
 def build_baseline_detector(kind='faster_rcnn', depth=50, cfg=None, bf16=False):
-    """kind = 'faster_rcnn' | 'cascade_rcnn' | 'faster_rcnn_gn_ws' | 'fcos' | 'fcos_center' | 'atss' -> the detector of
-    faster_rcnn_config / cascade_rcnn_config / faster_rcnn_gn_ws_config / fcos_config (its two variants) / atss_config (or of
-    `cfg`), with the `pretrained` URL of the
+    """kind = 'faster_rcnn' | 'cascade_rcnn' | 'faster_rcnn_gn_ws' | 'fcos' | 'fcos_center' | 'atss' | 'gfl' -> the detector of
+    faster_rcnn_config / cascade_rcnn_config / faster_rcnn_gn_ws_config / fcos_config (its two variants) / atss_config /
+    gfl_config (or of `cfg`), with the `pretrained` URL of the
     reference's config dropped: weights come from a checkpoint or from init_weights.  bf16 as in build_htd_detector."""
     makers = dict(faster_rcnn=faster_rcnn_config, cascade_rcnn=cascade_rcnn_config, faster_rcnn_gn_ws=faster_rcnn_gn_ws_config,
-                  fcos=fcos_config, fcos_center=lambda d: fcos_config(d, 'center-normbbox-centeronreg-giou'), atss=atss_config)
+                  fcos=fcos_config, fcos_center=lambda d: fcos_config(d, 'center-normbbox-centeronreg-giou'), atss=atss_config,
+                  gfl=gfl_config)
     if cfg is None:
         if kind not in makers:
             raise ValueError(f'build_baseline_detector: kind must be one of {sorted(makers)}, got {kind!r}')

@@ -355,6 +355,15 @@ def distance2bbox(points, distance, max_shape=None):
     return torch.stack([x1, y1, x2, y2], -1)
 
 
+def bbox2distance(points, bbox, max_dis=None, eps=0.1):
+    """mmdet/core/bbox/transforms.py:143-164: points (n, 2) [x, y] and boxes (n, 4) -> distances (n, 4) [left, top, right,
+    bottom], clamped to [0, max_dis - eps] when max_dis is given (eps keeps a target below max_dis, never at it)."""
+    d = [points[:, 0] - bbox[:, 0], points[:, 1] - bbox[:, 1], bbox[:, 2] - points[:, 0], bbox[:, 3] - points[:, 1]]
+    if max_dis is not None:
+        d = [v.clamp(min=0, max=max_dis - eps) for v in d]
+    return torch.stack(d, -1)
+
+
 def bbox2delta(proposals, gt, means=(0., 0., 0., 0.), stds=(1., 1., 1., 1.)):
     assert proposals.size() == gt.size()
     proposals, gt = proposals.float(), gt.float()

@@ -13,20 +13,15 @@
 // No float atomics: the one atomic is a 64-bit integer maximum, which does not depend on the order it is taken in; every sum
 // has a fixed order; every element of every output is stored exactly once with plain vector stores.
 #include "common.h"
+#include "anchor_levels.h"
 #include "focal_elem.h"
 #include "iou_family.h"
 #include "loss_units.h"
 
 namespace {
 
-constexpr int ATSS_BLOCKS = 2048;           // 256 CUs x 8 blocks: the cap of a memory-bound grid; the rest is grid-stride
-constexpr int ATSS_MAX_LEVELS = 8;
 constexpr int ATSS_MAX_TOPK = 16;
 constexpr double ATSS_EPS = 1e-12;          // atss_head.py:12
-
-struct AtssLevels {
-    unsigned aoff[ATSS_MAX_LEVELS + 1];     // first anchor of the level; aoff[L] = A (one anchor per location)
-};
 
 struct AtssCoder {                          // DeltaXYWHBBoxCoder: means, stds, |log(wh_ratio_clip)|
     float mean[4], std[4], max_ratio;          // as the reference's fp32 tensors hold them
@@ -42,18 +37,6 @@ struct AtssMaps {
     unsigned ts[ATSS_MAX_LEVELS];           // channel stride of the centerness map in floats (>= 1)
     unsigned rrow[ATSS_MAX_LEVELS + 1];     // prefix sums of B * pix: the pixel rows of all levels
 };
-
-__device__ __forceinline__ float4 load4(const float *p, int64_t i) { return *reinterpret_cast<const float4 *>(p + i * 4); }
-
-// bbox_overlaps(anchor, gt) (iou2d_calculator.py:43-124) in its fp32 order, eps = 1e-6
-__device__ __forceinline__ float iou_ref(float4 a, float4 g)
-{
-    const float area1 = (a.z - a.x) * (a.w - a.y), area2 = (g.z - g.x) * (g.w - g.y);
-    const float w = fmaxf(fminf(a.z, g.z) - fmaxf(a.x, g.x), 0.f), h = fmaxf(fminf(a.w, g.w) - fmaxf(a.y, g.y), 0.f);
-    const float overlap = w * h;
-    const float uni = fmaxf(area1 + area2 - overlap, 1e-6f);
-    return overlap / uni;
-}
 
 __device__ __forceinline__ float log_rounded(float x) { return (float)log((double)x); }
 __device__ __forceinline__ float exp_rounded(float x) { return (float)exp((double)x); }
@@ -340,22 +323,6 @@ __global__ __launch_bounds__(256) void atss_loss_kernel(AtssMaps mp, AtssLevels 
     block_store_partial2(s_cls, (float)s_box, partial);
     __syncthreads();                        // the reduction's LDS is read before the second pair overwrites it
     block_store_partial2((float)s_ctr, 0.f, partial + 2 * ATSS_BLOCKS);
-}
-
-int fill_levels(AtssLevels &lv, const char *what, const int64_t *level_sizes, int L, int64_t *A_out)
-{
-    HTD_REQUIRE(L > 0 && L <= ATSS_MAX_LEVELS, "%s: 1 to %d levels, got %d", what, ATSS_MAX_LEVELS, L);
-    HTD_REQUIRE(level_sizes, "%s: null level table", what);
-    int64_t off = 0;
-    for (int l = 0; l < L; ++l) {
-        HTD_REQUIRE(level_sizes[l] > 0, "%s: level %d has no anchor", what, l);
-        lv.aoff[l] = (unsigned)off;
-        off += level_sizes[l];
-        HTD_REQUIRE(off < ((int64_t)1 << 31), "%s: more than 2^31 anchors", what);
-    }
-    for (int l = L; l <= ATSS_MAX_LEVELS; ++l) lv.aoff[l] = (unsigned)off;
-    *A_out = off;
-    return HTD_OK;
 }
 
 int fill_coder(AtssCoder &cd, const char *what, const double *means4, const double *stds4, double wh_ratio_clip)

@@ -18,7 +18,8 @@ EXTRA = {'nms.hip': ['-ffp-contract=off'], 'box_ops.hip': ['-ffp-contract=off'],
          'image_pipeline.hip': ['-ffp-contract=off'], 'coco_eval.hip': ['-ffp-contract=off'],
          'voc_eval.hip': ['-ffp-contract=off'], 'fcos.hip': ['-ffp-contract=off'],
          'ghm_loss.hip': ['-ffp-contract=off'],     # its two passes must bin an element alike
-         'atss.hip': ['-ffp-contract=off']}         # distances and IoUs one rounded operation at a time
+         'atss.hip': ['-ffp-contract=off'],         # distances and IoUs one rounded operation at a time
+         'gfl.hip': ['-ffp-contract=off']}          # centres, targets and IoU scores in the reference's fp32 order
 
 
 # Every *.hip / *.cpp of this directory is a translation unit of the library; what each one replaces (include/htd_amd.h cites
@@ -30,7 +31,9 @@ EXTRA = {'nms.hip': ['-ffp-contract=off'], 'box_ops.hip': ['-ffp-contract=off'],
 #   fcos.hip         FCOSHead's targets, loss and ranking keys (dense_heads/fcos_head.py:159-253,364-372,415-576)
 #   atss.hip         ATSSAssigner over a batch with the centerness targets and averaging factors, and ATSSHead's loss
 #                    (core/bbox/assigners/atss_assigner.py:33-178, dense_heads/atss_head.py:145-313)
-# The four share focal_elem.h (the element arithmetic) and loss_units.h (level search, VEC-wide units, matrix units).
+#   gfl.hip          GFLHead's quality pass, loss (QFL, weighted IoU / GIoU, DFL) and inference decode
+#                    (dense_heads/gfl_head.py:209-369,420-428, losses/gfocal_loss.py:8-74); level table of atss.hip (anchor_levels.h)
+# The five share focal_elem.h (the element arithmetic) and loss_units.h (level search, VEC-wide units, matrix units).
 def sources():
     return sorted(f for f in os.listdir(HERE) if f.endswith('.hip') or f.endswith('.cpp'))
 

@@ -1,9 +1,9 @@
-"""Anchor-based dense heads of single-stage detectors: AnchorHead, RetinaHead and ATSSHead.
+"""Anchor-based dense heads of single-stage detectors: AnchorHead, RetinaHead, ATSSHead and GFLHead (with its Integral layer).
 
 Reference: dense_heads/anchor_head.py:14-682 (AnchorHead: forward, get_anchors, get_targets, loss, get_bboxes),
-base_dense_head.py:22-59 (forward_train), retina_head.py:8-114 (RetinaHead), atss_head.py:15-650 (ATSSHead).  Same registry
-names, constructor kwargs, state_dict keys (cls_convs / reg_convs / retina_cls / retina_reg; atss_cls / atss_reg /
-atss_centerness / scales.N.scale) and return structures.  AnchorHead is also the base of RPNHead
+base_dense_head.py:22-59 (forward_train), retina_head.py:8-114 (RetinaHead), atss_head.py:15-650 (ATSSHead), gfl_head.py:15-632
+(Integral, GFLHead).  Same registry names, constructor kwargs, state_dict keys (cls_convs / reg_convs / retina_cls / retina_reg;
+atss_cls / atss_reg / atss_centerness / scales.N.scale; gfl_cls / gfl_reg / integral.project) and return structures.  AnchorHead is also the base of RPNHead
 (detector/rpn_head.py), as in the reference: anchors, per-image targets (gt_labels None: foreground is class 0), the
 reference-order loss are written once, here; forward_train, simple_test and the cache of constants of the pyramid's map shapes
 (`_shape_key` makes their key, `_cached` fetches them) come from BaseDenseHead (detector/base_dense_head.py), which the
@@ -39,6 +39,7 @@ from .losses import GHM_KERNEL_BINS, GHMC, GHMR
 RETINA_FUSED = os.environ.get('HTD_RETINA_FUSED', '1') != '0'       # 0: the tensor-path loss (A/B runs)
 ATSS_FUSED = os.environ.get('HTD_ATSS_FUSED', '1') != '0'           # the same switch for ATSSHead
 ATSS_EPS = 1e-12                                                    # atss_head.py:12
+GFL_FUSED = os.environ.get('HTD_GFL_FUSED', '1') != '0'             # the same switch for GFLHead
 
 
 def bias_init_with_prob(prior_prob):
@@ -497,9 +498,13 @@ class ATSSHead(AnchorHead):
     def get_num_level_anchors_inside(self, num_level_anchors, inside_flags):
         return [int(flags.sum()) for flags in torch.split(inside_flags, num_level_anchors)]
 
+    def _pos_bbox_targets(self, sr):
+        """The regression targets of the positives of a sampling result: the coder's deltas (GFLHead: the gt boxes)."""
+        return self.bbox_coder.encode(sr.pos_bboxes, sr.pos_gt_bboxes)
+
     def _get_target_single(self, flat_anchors, valid_flags, num_level_anchors, gt_bboxes, gt_bboxes_ignore, gt_labels, img_meta,
                            label_channels=1, unmap_outputs=True):
-        """atss_head.py:535-643 for one image."""
+        """atss_head.py:535-643 for one image (gfl_head.py:521-625 with GFLHead's _pos_bbox_targets)."""
         inside = anchor_inside_flags(flat_anchors, valid_flags, img_meta['img_shape'][:2], self.train_cfg.allowed_border)
         if not inside.any():
             return (None, ) * 7
@@ -514,7 +519,7 @@ class ATSSHead(AnchorHead):
         label_weights = anchors.new_zeros(n, dtype=torch.float)
         pos_inds, neg_inds = sr.pos_inds, sr.neg_inds
         if len(pos_inds) > 0:
-            bbox_targets[pos_inds, :] = self.bbox_coder.encode(sr.pos_bboxes, sr.pos_gt_bboxes)
+            bbox_targets[pos_inds, :] = self._pos_bbox_targets(sr)
             bbox_weights[pos_inds, :] = 1.0
             labels[pos_inds] = 0 if gt_labels is None else gt_labels[sr.pos_assigned_gt_inds]
             label_weights[pos_inds] = 1.0 if self.train_cfg.pos_weight <= 0 else self.train_cfg.pos_weight
@@ -681,3 +686,312 @@ class ATSSHead(AnchorHead):
         """atss_head.py:379-469 for one image."""
         return self._ctr_bboxes_single(cls_scores, bbox_preds, centernesses, mlvl_anchors, self._decode, self.anchor_generator.strides,
                                        img_shape, scale_factor, cfg, rescale, with_nms)
+
+
+class Integral(nn.Module):
+    """gfl_head.py:15-48: the expectation sum_i P(y_i) y_i of the discrete distribution over {0, 1, ..., reg_max} that a softmax
+    of each side's reg_max + 1 logits gives: (N, 4 * (reg_max + 1)) -> (N, 4).  `project` is part of the state dict."""
+
+    def __init__(self, reg_max=16):
+        super().__init__()
+        self.reg_max = reg_max
+        self.register_buffer('project', torch.linspace(0, self.reg_max, self.reg_max + 1))
+
+    def forward(self, x):
+        x = torch.softmax(x.reshape(-1, self.reg_max + 1), dim=1)
+        return torch.nn.functional.linear(x, self.project.type_as(x)).reshape(-1, 4)
+
+
+@HEADS.register_module()
+class GFLHead(AnchorHead):
+    """dense_heads/gfl_head.py:51-632: ATSSHead's towers, assigner and one-anchor pyramid with a joint class / quality score
+    under QualityFocalLoss in place of the centerness branch, and a discrete distribution of reg_max + 1 bins per side under
+    DistributionFocalLoss, plus an IoU-family loss on its integral, in place of the four deltas.  The targets are the gt boxes.
+
+    `loss` has two forms, like ATSSHead.loss, and `_fused_loss_ok` is the one rule between them.  `loss_tensor` is the reference's
+    order of operations and works on the CPU, in fp64 and with ignore boxes.  `loss_fused` assigns the batch with
+    htd_atss_targets, takes the weights, the IoU scores and their sum in one pass (htd_gfl_quality) and the three losses with
+    both gradient maps of all levels in one more launch (htd_gfl_loss): no permute, concatenation, gather or nonzero() of the
+    predictions, no host read.
+
+    Two pieces of reference behaviour are kept in both forms.  The averaging factor of the box and DFL losses (the sum of the
+    positives' weights, gfl_head.py:364-367) is not clamped: a batch without a positive gives loss_bbox = loss_dfl = 0 / 0 = NaN
+    and a NaN regression gradient beside a finite loss_cls.  And the DFL targets are clamped to [0, reg_max - 0.1]
+    (bbox2distance's max_dis and eps) before `label.long()` splits them into bins."""
+
+    def __init__(self, num_classes, in_channels, stacked_convs=4, conv_cfg=None,
+                 norm_cfg=dict(type='GN', num_groups=32, requires_grad=True),
+                 loss_dfl=dict(type='DistributionFocalLoss', loss_weight=0.25), reg_max=16, **kwargs):
+        self.stacked_convs, self.conv_cfg, self.norm_cfg, self.reg_max = stacked_convs, conv_cfg, norm_cfg, reg_max
+        super().__init__(num_classes, in_channels, **kwargs)
+        self.sampling = False
+        if self.train_cfg:
+            self.assigner = build_assigner(self.train_cfg.assigner)
+            self.sampler = build_sampler(dict(type='PseudoSampler'), context=self)
+        self.integral = Integral(self.reg_max)
+        self.loss_dfl = build_loss(loss_dfl)
+
+    def _init_layers(self):
+        from .anchor_free_heads import Scale
+        self.relu = nn.ReLU(inplace=True)
+        self.cls_convs = nn.ModuleList()
+        self.reg_convs = nn.ModuleList()
+        for i in range(self.stacked_convs):
+            chn = self.in_channels if i == 0 else self.feat_channels
+            self.cls_convs.append(ConvModule(chn, self.feat_channels, 3, stride=1, padding=1, conv_cfg=self.conv_cfg,
+                                             norm_cfg=self.norm_cfg))
+            self.reg_convs.append(ConvModule(chn, self.feat_channels, 3, stride=1, padding=1, conv_cfg=self.conv_cfg,
+                                             norm_cfg=self.norm_cfg))
+        assert self.num_anchors == 1, 'anchor free version'
+        self.gfl_cls = Conv2d(self.feat_channels, self.cls_out_channels, 3, padding=1)
+        self.gfl_reg = Conv2d(self.feat_channels, 4 * (self.reg_max + 1), 3, padding=1)
+        self.scales = nn.ModuleList([Scale(1.0) for _ in self.anchor_generator.strides])
+
+    def init_weights(self):
+        for m in list(self.cls_convs) + list(self.reg_convs):
+            normal_init(m.conv, std=0.01)
+        normal_init(self.gfl_cls, std=0.01, bias=bias_init_with_prob(0.01))
+        normal_init(self.gfl_reg, std=0.01)
+
+    # ------------------------------------------------------------------ forward
+    def forward(self, feats):
+        return multi_apply(self.forward_single, feats, self.scales)
+
+    def forward_single(self, x, scale):
+        """gfl_head.py:170-194 -> cls_score (class / quality logits), bbox_pred (scaled distribution logits)."""
+        if x.dtype != torch.float32:             # a bf16 pyramid: the towers and all box / loss arithmetic stay fp32
+            x = x.float()
+        cls_feat = reg_feat = x
+        for cls_conv in self.cls_convs:
+            cls_feat = cls_conv(cls_feat)
+        for reg_conv in self.reg_convs:
+            reg_feat = reg_conv(reg_feat)
+        return self.gfl_cls(cls_feat), scale(self.gfl_reg(reg_feat)).float()
+
+    def anchor_center(self, anchors):
+        """gfl_head.py:196-207: (N, 4) anchors -> (N, 2) centres."""
+        return torch.stack([(anchors[:, 2] + anchors[:, 0]) / 2, (anchors[:, 3] + anchors[:, 1]) / 2], dim=-1)
+
+    # ------------------------------------------------------------------ targets (ATSSHead's, with the gt boxes as targets)
+    def _pos_bbox_targets(self, sr):
+        return sr.pos_gt_bboxes
+
+    get_num_level_anchors_inside = ATSSHead.get_num_level_anchors_inside
+    _get_target_single = ATSSHead._get_target_single
+    get_targets = ATSSHead.get_targets
+    _atss_consts = ATSSHead._atss_consts
+
+    # ------------------------------------------------------------------ loss
+    def loss_single(self, anchors, cls_score, bbox_pred, labels, label_weights, bbox_targets, stride, num_total_samples):
+        """gfl_head.py:209-295."""
+        from ..core.bbox import bbox2distance, bbox_overlaps, distance2bbox
+        assert stride[0] == stride[1], 'h stride is not equal to w stride!'
+        anchors = anchors.reshape(-1, 4)
+        cls_score = cls_score.permute(0, 2, 3, 1).reshape(-1, self.cls_out_channels)
+        bbox_pred = bbox_pred.permute(0, 2, 3, 1).reshape(-1, 4 * (self.reg_max + 1))
+        bbox_targets = bbox_targets.reshape(-1, 4)
+        labels = labels.reshape(-1)
+        label_weights = label_weights.reshape(-1)
+        pos_inds = ((labels >= 0) & (labels < self.num_classes)).nonzero().squeeze(1)
+        # in the dtype of the logits (the reference takes label_weights' fp32, the same wherever it runs): an fp64 run keeps its
+        # fp64 IoU scores, as the fixture's fp64 run of the reference does with its label weights cast
+        score = cls_score.new_zeros(labels.shape)
+        if len(pos_inds) > 0:
+            pos_bbox_targets, pos_bbox_pred = bbox_targets[pos_inds], bbox_pred[pos_inds]
+            pos_anchor_centers = self.anchor_center(anchors[pos_inds]) / stride[0]
+            weight_targets = cls_score.detach().sigmoid().max(dim=1)[0][pos_inds]
+            pos_decode_bbox_pred = distance2bbox(pos_anchor_centers, self.integral(pos_bbox_pred))
+            pos_decode_bbox_targets = pos_bbox_targets / stride[0]
+            score[pos_inds] = bbox_overlaps(pos_decode_bbox_pred.detach(), pos_decode_bbox_targets, is_aligned=True).to(score.dtype)
+            pred_corners = pos_bbox_pred.reshape(-1, self.reg_max + 1)
+            target_corners = bbox2distance(pos_anchor_centers, pos_decode_bbox_targets, self.reg_max).reshape(-1)
+            loss_bbox = self.loss_bbox(pos_decode_bbox_pred, pos_decode_bbox_targets, weight=weight_targets, avg_factor=1.0)
+            loss_dfl = self.loss_dfl(pred_corners, target_corners, weight=weight_targets[:, None].expand(-1, 4).reshape(-1),
+                                     avg_factor=4.0)
+        else:
+            loss_bbox = bbox_pred.sum() * 0
+            loss_dfl = bbox_pred.sum() * 0
+            weight_targets = bbox_pred.new_tensor(0.)
+        loss_cls = self.loss_cls(cls_score, (labels, score), weight=label_weights, avg_factor=num_total_samples)
+        return loss_cls, loss_bbox, loss_dfl, weight_targets.sum()
+
+    def loss(self, cls_scores, bbox_preds, gt_bboxes, gt_labels, img_metas, gt_bboxes_ignore=None):
+        if self._fused_loss_ok(cls_scores, bbox_preds, gt_labels, gt_bboxes_ignore, img_metas):
+            return self.loss_fused(cls_scores, bbox_preds, gt_bboxes, gt_labels, img_metas)
+        return self.loss_tensor(cls_scores, bbox_preds, gt_bboxes, gt_labels, img_metas, gt_bboxes_ignore)
+
+    def loss_tensor(self, cls_scores, bbox_preds, gt_bboxes, gt_labels, img_metas, gt_bboxes_ignore=None):
+        """gfl_head.py:297-369, in the reference's order of operations; the averaging factor is not clamped."""
+        featmap_sizes = [f.size()[-2:] for f in cls_scores]
+        assert len(featmap_sizes) == self.anchor_generator.num_levels
+        device = cls_scores[0].device
+        anchor_list, valid_flag_list = self.get_anchors(featmap_sizes, img_metas, device=device)
+        label_channels = self.cls_out_channels if self.use_sigmoid_cls else 1
+        targets = self.get_targets(anchor_list, valid_flag_list, gt_bboxes, img_metas, gt_bboxes_ignore_list=gt_bboxes_ignore,
+                                   gt_labels_list=gt_labels, label_channels=label_channels)
+        if targets is None:
+            return None
+        anchors, labels, label_weights, bbox_targets, _, num_total_pos, _ = targets
+        num_total_samples = float(reduce_mean(torch.tensor(float(num_total_pos), device=device)))
+        num_total_samples = max(num_total_samples, 1.0)
+        losses_cls, losses_bbox, losses_dfl, avg_factor = multi_apply(
+            self.loss_single, anchors, cls_scores, bbox_preds, labels, label_weights, bbox_targets, self.anchor_generator.strides,
+            num_total_samples=num_total_samples)
+        avg_factor = float(reduce_mean(sum(avg_factor)))
+        losses_bbox = [x / avg_factor for x in losses_bbox]
+        losses_dfl = [x / avg_factor for x in losses_dfl]
+        return dict(loss_cls=losses_cls, loss_bbox=losses_bbox, loss_dfl=losses_dfl)
+
+    def _fused_loss_ok(self, cls_scores, bbox_preds, gt_labels, gt_bboxes_ignore, img_metas):
+        """htd_atss_targets / htd_gfl_quality / htd_gfl_loss cover one anchor per location, every anchor valid and inside, no
+        ignore boxes, label weight 1 on positives (pos_weight <= 0), ATSSAssigner with topk <= 16, QualityFocalLoss +
+        DistributionFocalLoss + IoULoss / GIoULoss all with mean reduction, reg_max <= 31 and fp32 channels_last GPU maps of at
+        most 8 levels."""
+        lc, lb, ld = self.loss_cls, self.loss_bbox, self.loss_dfl
+        a = getattr(self, 'assigner', None)
+        ok = getattr(self, 'fused_loss', GFL_FUSED) and gt_labels is not None and gt_bboxes_ignore is None and \
+            self.num_anchors == 1 and type(a).__name__ == 'ATSSAssigner' and a.ignore_iof_thr <= 0 and a.topk <= 16 and \
+            type(lc).__name__ == 'QualityFocalLoss' and lc.use_sigmoid and lc.reduction == 'mean' and \
+            self.train_cfg.pos_weight <= 0 and \
+            type(lb).__name__ in M.FCOS_BOX_KINDS and lb.reduction == 'mean' and \
+            type(ld).__name__ == 'DistributionFocalLoss' and ld.reduction == 'mean' and \
+            1 <= self.reg_max <= 31 and len(cls_scores) <= 8 and \
+            all(t.is_cuda and t.dtype == torch.float32 and M.nhwc_channel_stride(t) is not None
+                for t in list(cls_scores) + list(bbox_preds))
+        if not ok:
+            return False
+        return self._atss_consts([f.size()[-2:] for f in cls_scores], img_metas, cls_scores[0].device)[1]
+
+    def loss_fused(self, cls_scores, bbox_preds, gt_bboxes, gt_labels, img_metas):
+        import torch.distributed as dist
+        from ..core.bbox import pad_gt_batch
+        featmap_sizes = [f.size()[-2:] for f in cls_scores]
+        assert len(featmap_sizes) == self.anchor_generator.num_levels
+        flat_anchors, _ = self._atss_consts(featmap_sizes, img_metas, cls_scores[0].device)
+        gts, gt_valid, labels = pad_gt_batch(gt_bboxes, gt_labels)
+        strides = self.anchor_generator.strides
+        assigned, _, num_pos, norm = M.atss_targets(flat_anchors, [int(h * w) for h, w in featmap_sizes], gts, gt_valid,
+                                                    self.assigner.topk)
+        weight, score, wsum = M.gfl_quality([c.detach() for c in cls_scores], [r.detach() for r in bbox_preds], strides,
+                                            self.reg_max, flat_anchors, gts, assigned)
+        if dist.is_available() and dist.is_initialized():
+            # gfl_head.py:347-350,364-365: both factors averaged over the processes, the sample count at least 1
+            norm = reduce_mean(norm)
+            norm = torch.cat([norm[:2].clamp(min=1.0), norm[2:]])
+            wsum = reduce_mean(wsum)
+        self._last_targets = (assigned, num_pos, norm)          # exposed for tests
+        self._last_quality = (weight, score, wsum)
+        lc, lb = self.loss_cls, self.loss_bbox
+        loss_cls, loss_bbox, loss_dfl = M.gfl_loss(
+            cls_scores, bbox_preds, strides, self.reg_max, flat_anchors, gts, labels, assigned, weight, score, norm, wsum,
+            M.FCOS_BOX_KINDS[type(lb).__name__], lb.eps, lc.beta, lc.loss_weight, lb.loss_weight, self.loss_dfl.loss_weight)
+        return dict(loss_cls=loss_cls, loss_bbox=loss_bbox, loss_dfl=loss_dfl)
+
+    # ------------------------------------------------------------------ boxes
+    def _device_decode_ok(self, cls_scores, bbox_preds):
+        """htd_gfl_decode takes fp32 channels_last GPU maps (of a batch, or of one image of one) of at most 8 levels; anything
+        else, NCHW-contiguous maps included, takes the tensor operations."""
+        return cls_scores[0].is_cuda and len(cls_scores) <= 8 and 1 <= self.reg_max <= 31 and \
+            all(t.dtype == torch.float32 and M.nhwc_channel_stride(t if t.dim() == 4 else t[None]) is not None
+                for t in list(cls_scores) + list(bbox_preds))
+
+    @torch.no_grad()
+    def get_bboxes(self, cls_scores, bbox_preds, img_metas, cfg=None, rescale=False, with_nms=True):
+        """gfl_head.py:371-455 over a batch -> list (per image) of (dets (k, 5), labels (k,)).  GPU fp32 maps with hard NMS take
+        the batched form; everything else the per-image loop."""
+        cfg = self.test_cfg if cfg is None else cfg
+        assert len(cls_scores) == len(bbox_preds)
+        featmap_sizes = [c.shape[-2:] for c in cls_scores]
+        dev = cls_scores[0].device
+        nms_pre = cfg.get('nms_pre', -1)
+        Ns = [int(h * w) for h, w in featmap_sizes]
+        batched = with_nms and self._device_decode_ok(cls_scores, bbox_preds) and cfg.nms.get('type', 'nms') == 'nms' and \
+            (nms_pre <= 0 or nms_pre <= M.TOPK_KMAX) and getattr(self, 'batched_get_bboxes', True) and \
+            (nms_pre > 0 or max(Ns) <= M.TOPK_KMAX)
+        if batched:
+            return self._get_bboxes_batched(cls_scores, bbox_preds, img_metas, cfg, rescale)
+        mlvl_anchors = self.anchor_generator.grid_anchors(featmap_sizes, device=dev)
+        return [self._get_bboxes_single([c[b].detach() for c in cls_scores], [r[b].detach() for r in bbox_preds], mlvl_anchors,
+                                        meta['img_shape'], meta['scale_factor'], cfg, rescale, with_nms)
+                for b, meta in enumerate(img_metas)]
+
+    def _level_keys_dists(self, cls_scores, bbox_preds):
+        """per level (n_l,) max_c sigmoid(score) and (n_l, 4) integral * stride of one image: htd_gfl_decode on the GPU (the
+        launch form of the batched path, so the two rank and decode identically), the reference's tensor operations elsewhere."""
+        strides = self.anchor_generator.strides
+        if self._device_decode_ok(cls_scores, bbox_preds):
+            keys, dists = M.gfl_decode([c[None] for c in cls_scores], [r[None] for r in bbox_preds], strides, self.reg_max)
+            Ns = [int(c.shape[1] * c.shape[2]) for c in cls_scores]
+            return list(keys[0].split(Ns)), list(dists[0].split(Ns))
+        keys = [c.permute(1, 2, 0).reshape(-1, self.cls_out_channels).sigmoid().max(dim=1)[0] for c in cls_scores]
+        dists = [self.integral(r.permute(1, 2, 0)) * s[0] for r, s in zip(bbox_preds, strides)]
+        return keys, dists
+
+    def _get_bboxes_single(self, cls_scores, bbox_preds, mlvl_anchors, img_shape, scale_factor, cfg, rescale=False, with_nms=True):
+        """gfl_head.py:371-455 for one image."""
+        from ..core.bbox import distance2bbox
+        from ..core.post_processing import multiclass_nms
+        cfg = self.test_cfg if cfg is None else cfg
+        assert len(cls_scores) == len(bbox_preds) == len(mlvl_anchors)
+        nms_pre = cfg.get('nms_pre', -1)
+        keys, dists = self._level_keys_dists(cls_scores, bbox_preds)
+        mlvl_bboxes, mlvl_scores = [], []
+        for lvl, (cls_score, anchors) in enumerate(zip(cls_scores, mlvl_anchors)):
+            assert cls_score.size()[-2:] == bbox_preds[lvl].size()[-2:]
+            scores = cls_score.permute(1, 2, 0).reshape(-1, self.cls_out_channels).sigmoid()
+            bbox_pred = dists[lvl]
+            if nms_pre > 0 and scores.shape[0] > nms_pre:
+                # the first nms_pre of the stable descending order (equal keys: lower location index first)
+                topk_inds = keys[lvl].sort(descending=True, stable=True)[1][:nms_pre]
+                anchors, bbox_pred, scores = anchors[topk_inds, :], bbox_pred[topk_inds, :], scores[topk_inds, :]
+            mlvl_bboxes.append(distance2bbox(self.anchor_center(anchors), bbox_pred, max_shape=img_shape))
+            mlvl_scores.append(scores)
+        mlvl_bboxes = torch.cat(mlvl_bboxes)
+        if rescale:
+            mlvl_bboxes = mlvl_bboxes / mlvl_bboxes.new_tensor(scale_factor)
+        mlvl_scores = torch.cat(mlvl_scores)
+        mlvl_scores = torch.cat([mlvl_scores, mlvl_scores.new_zeros(mlvl_scores.shape[0], 1)], dim=1)
+        if with_nms:
+            return multiclass_nms(mlvl_bboxes, mlvl_scores, cfg.score_thr, cfg.nms, cfg.max_per_img)
+        return mlvl_bboxes, mlvl_scores
+
+    def _get_bboxes_batched(self, cls_scores, bbox_preds, img_metas, cfg, rescale):
+        """The whole batch on the GPU: one decode launch (htd_gfl_decode) and one segmented top-k give every (image, level) cut
+        to nms_pre, one gather, one multiclass NMS over all images without score factors; distance2bbox stays the tensor
+        operation, image by image, so the result is bit-identical to the per-image loop."""
+        from ..core.bbox import distance2bbox
+        from ..core.post_processing import multiclass_nms_images
+        B, L = cls_scores[0].size(0), len(cls_scores)
+        dev = cls_scores[0].device
+        C = self.cls_out_channels
+        featmap_sizes = [c.shape[-2:] for c in cls_scores]
+        nms_pre = cfg.get('nms_pre', -1)
+        Ns = [int(h * w) for h, w in featmap_sizes]
+        ks = [n if nms_pre <= 0 else min(nms_pre, n) for n in Ns]
+        offs = [sum(Ns[:l]) for l in range(L)]
+        total = sum(Ns)
+        cls_scores = [c.detach() for c in cls_scores]
+        centres = self._cached('_centre_cache', 32, (self._shape_key(featmap_sizes), str(dev)),
+                               lambda: self.anchor_center(torch.cat(self.anchor_generator.grid_anchors(featmap_sizes, device=dev))))
+        keys, dists = M.gfl_decode(cls_scores, [r.detach() for r in bbox_preds], self.anchor_generator.strides, self.reg_max)
+        cut = [l for l in range(L) if ks[l] < Ns[l]]
+        pieces = [torch.arange(offs[l], offs[l] + Ns[l], device=dev)[None].expand(B, Ns[l]) for l in range(L)]
+        if cut:
+            top_idx, _ = M.segmented_topk(keys, [(b * total + offs[l], Ns[l], ks[l]) for b in range(B) for l in cut])
+            top_idx, at = top_idx.view(B, -1), 0
+            for l in cut:
+                pieces[l] = top_idx[:, at:at + ks[l]] + offs[l]
+                at += ks[l]
+        gidx = torch.cat(pieces, 1)
+        K = gidx.size(1)
+        logits = torch.cat([c.permute(0, 2, 3, 1).reshape(B, -1, C) for c in cls_scores], 1)
+        scores = torch.gather(logits, 1, gidx[..., None].expand(B, K, C)).sigmoid()
+        dists = torch.gather(dists, 1, gidx[..., None].expand(B, K, 4))
+        boxes = torch.stack([distance2bbox(centres[gidx[b]], dists[b], max_shape=img_metas[b]['img_shape']) for b in range(B)])
+        if rescale:
+            boxes = torch.stack([boxes[b] / boxes.new_tensor(img_metas[b]['scale_factor']) for b in range(B)])
+        scores = torch.cat([scores, scores.new_zeros(B, K, 1)], dim=2)
+        img_of = torch.arange(B, device=dev).repeat_interleave(K)
+        dets, labels = multiclass_nms_images(boxes.reshape(B * K, 4), scores.reshape(B * K, C + 1), img_of, B, cfg.score_thr,
+                                             cfg.nms, cfg.max_per_img)
+        return list(zip(dets, labels))

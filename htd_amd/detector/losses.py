@@ -1,7 +1,7 @@
 """Losses of the HTD path: CrossEntropyLoss (softmax / sigmoid), SmoothL1Loss, L1Loss, the IoU family on decoded boxes
-(IoULoss, BoundedIoULoss, GIoULoss, DIoULoss, CIoULoss), FocalLoss, GHMC, GHMR, accuracy.
+(IoULoss, BoundedIoULoss, GIoULoss, DIoULoss, CIoULoss), FocalLoss, QualityFocalLoss, DistributionFocalLoss, GHMC, GHMR, accuracy.
 Reference: mmdet/models/losses/{cross_entropy_loss.py:9-202, smooth_l1_loss.py:8-136, iou_loss.py:11-418,
-utils.py:26-52, focal_loss.py:10-157, ghm_loss.py:8-172, accuracy.py:4-48}.  Same constructor kwargs and forward signature
+utils.py:26-52, focal_loss.py:10-157, gfocal_loss.py:8-185, ghm_loss.py:8-172, accuracy.py:4-48}.  Same constructor kwargs and forward signature
 (weight, avg_factor, reduction_override; the GHM pair has the reference's own, ghm_loss.py:50, :127)."""
 import math
 
@@ -282,6 +282,62 @@ class FocalLoss(nn.Module):
         reduction = reduction_override if reduction_override else self.reduction
         return self.loss_weight * sigmoid_focal_loss(pred, target, weight, gamma=self.gamma, alpha=self.alpha,
                                                      reduction=reduction, avg_factor=avg_factor)
+
+
+# ---------------------------------------------------------------- generalized focal losses (gfocal_loss.py:8-185)
+def quality_focal_loss(pred, target, weight=None, beta=2.0, reduction='mean', avg_factor=None):
+    """gfocal_loss.py:8-49 under weighted_loss: pred (N, C) joint class / quality logits, target = (label (N,) with C =
+    background, score (N,) the quality of a positive's own class).  Every (row, class) is supervised by 0 under the modulating
+    factor sigmoid^beta; a positive's own class by its score under |score - sigmoid|^beta.  Neither factor is detached.
+    -> per-row sums, then weight (N,), reduction and avg_factor as weight_reduce_loss has them."""
+    assert len(target) == 2, 'target for QFL must be a tuple of two elements: category label and quality label'
+    label, score = target
+    pred_sigmoid = pred.sigmoid()
+    loss = F.binary_cross_entropy_with_logits(pred, pred_sigmoid.new_zeros(pred.shape), reduction='none') * pred_sigmoid.pow(beta)
+    pos = ((label >= 0) & (label < pred.size(1))).nonzero().squeeze(1)
+    pos_label = label[pos].long()
+    scale_factor = score[pos] - pred_sigmoid[pos, pos_label]
+    loss[pos, pos_label] = F.binary_cross_entropy_with_logits(pred[pos, pos_label], score[pos], reduction='none') * \
+        scale_factor.abs().pow(beta)
+    return weight_reduce_loss(loss.sum(dim=1, keepdim=False), weight, reduction, avg_factor)
+
+
+def distribution_focal_loss(pred, label, weight=None, reduction='mean', avg_factor=None):
+    """gfocal_loss.py:52-74 under weighted_loss: pred (N, n + 1) logits of the bins 0 .. n, label (N,) target distances in
+    [0, n): the cross-entropies of the two neighbouring bins weighted by the distance to the other."""
+    dis_left = label.long()
+    dis_right = dis_left + 1
+    weight_left = dis_right.float() - label
+    weight_right = label - dis_left.float()
+    loss = F.cross_entropy(pred, dis_left, reduction='none') * weight_left + \
+        F.cross_entropy(pred, dis_right, reduction='none') * weight_right
+    return weight_reduce_loss(loss, weight, reduction, avg_factor)
+
+
+@LOSSES.register_module()
+class QualityFocalLoss(nn.Module):
+    def __init__(self, use_sigmoid=True, beta=2.0, reduction='mean', loss_weight=1.0):
+        super().__init__()
+        assert use_sigmoid is True, 'Only sigmoid in QFL supported now.'
+        self.use_sigmoid, self.beta, self.reduction, self.loss_weight = use_sigmoid, beta, reduction, loss_weight
+
+    def forward(self, pred, target, weight=None, avg_factor=None, reduction_override=None):
+        assert reduction_override in (None, 'none', 'mean', 'sum')
+        reduction = reduction_override if reduction_override else self.reduction
+        return self.loss_weight * quality_focal_loss(pred, target, weight, beta=self.beta, reduction=reduction,
+                                                     avg_factor=avg_factor)
+
+
+@LOSSES.register_module()
+class DistributionFocalLoss(nn.Module):
+    def __init__(self, reduction='mean', loss_weight=1.0):
+        super().__init__()
+        self.reduction, self.loss_weight = reduction, loss_weight
+
+    def forward(self, pred, target, weight=None, avg_factor=None, reduction_override=None):
+        assert reduction_override in (None, 'none', 'mean', 'sum')
+        reduction = reduction_override if reduction_override else self.reduction
+        return self.loss_weight * distribution_focal_loss(pred, target, weight, reduction=reduction, avg_factor=avg_factor)
 
 
 # ---------------------------------------------------------------- gradient harmonising losses (ghm_loss.py:8-172)

@@ -1,7 +1,7 @@
-"""SingleStageDetector, RetinaNet, FCOS and ATSS.
+"""SingleStageDetector, RetinaNet, FCOS, ATSS and GFL.
 
 Reference: detectors/single_stage.py:9-149 (extract_feat :52-57, forward_train :68-96, simple_test :98-124),
-detectors/retinanet.py:5-17, detectors/fcos.py:5-17, detectors/atss.py:5-17.  The dense head does the work (detector/anchor_heads.py,
+detectors/retinanet.py:5-17, detectors/fcos.py:5-17, detectors/atss.py:5-17, detectors/gfl.py:5-16.  The dense head does the work (detector/anchor_heads.py,
 anchor_free_heads.py); results of a batch leave the device in one copy (core.bbox.bbox2result_many).
 """
 from ..core.bbox import bbox2result_many
@@ -68,6 +68,14 @@ class FCOS(SingleStageDetector):
 @DETECTORS.register_module()
 class ATSS(SingleStageDetector):
     """detectors/atss.py:5-17."""
+
+    def __init__(self, backbone, neck, bbox_head, train_cfg=None, test_cfg=None, pretrained=None):
+        super().__init__(backbone, neck, bbox_head, train_cfg, test_cfg, pretrained)
+
+
+@DETECTORS.register_module()
+class GFL(SingleStageDetector):
+    """detectors/gfl.py:5-16."""
 
     def __init__(self, backbone, neck, bbox_head, train_cfg=None, test_cfg=None, pretrained=None):
         super().__init__(backbone, neck, bbox_head, train_cfg, test_cfg, pretrained)

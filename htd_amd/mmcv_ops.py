@@ -1527,3 +1527,114 @@ def atss_loss(cls_maps, reg_maps, ctr_maps, strides, anchors, gts, gt_labels, as
                                   _f32(gts, 'atss_loss').contiguous(), gt_labels.contiguous(), assigned.contiguous(),
                                   ctr_targets.contiguous(), norm, means, stds, wh_ratio_clip, box_kind, eps, gamma, alpha,
                                   cls_weight, box_weight, ctr_weight, *cls_maps, *reg_maps, *ctr_maps)
+
+
+# ====================================================================== GFL head (dense_heads/gfl_head.py)
+def _gfl_tables(cls_maps, reg_maps, strides, reg_max, what):
+    """-> (classification table, strides, regression table, strides, level sizes, pyramid strides, A) of a GFL head's maps, all
+    HOST tables; the maps checked for dtype and channel counts."""
+    _need_gpu(cls_maps[0], what)
+    if len(cls_maps) != len(reg_maps):
+        raise ValueError(f'{what}: {len(cls_maps)} classification maps for {len(reg_maps)} regression maps')
+    for c, r in zip(cls_maps, reg_maps):
+        _f32(c, what)
+        _f32(r, what)
+        if r.size(1) != 4 * (int(reg_max) + 1) or r.shape[-2:] != c.shape[-2:] or r.size(0) != c.size(0):
+            raise ValueError(f'{what}: a regression map of shape {tuple(r.shape)} beside a classification map {tuple(c.shape)} '
+                             f'with reg_max = {reg_max}')
+    _, st, A = _fcos_levels([m.shape[-2:] for m in cls_maps], strides)
+    ct, cs, _ = _level_tables(cls_maps, what)
+    rt, rs, _ = _level_tables(reg_maps, what)
+    sizes = _i64s([int(m.shape[-2] * m.shape[-1]) for m in cls_maps])
+    return ct, cs, rt, rs, sizes, st, A
+
+
+def gfl_quality(cls_maps, reg_maps, strides, reg_max, anchors, gts, assigned):
+    """htd_gfl_quality: per positive of `assigned` (B, A) (atss_targets) the weight max_c sigmoid(cls) and the IoU score of its
+    integral-decoded box with its gt, 0 elsewhere, and the sum of all weights: what the averaging factor of GFLHead.loss and the
+    QFL targets are.  -> weight (B, A), score (B, A), wsum (1,); nothing read back."""
+    ct, cs, rt, rs, sizes, st, A = _gfl_tables(cls_maps, reg_maps, strides, reg_max, 'gfl_quality')
+    B, L = cls_maps[0].size(0), len(cls_maps)
+    if assigned.shape != (B, A) or assigned.dtype != torch.int32 or anchors.shape != (A, 4) or gts.dim() != 3 or gts.size(0) != B:
+        raise ValueError(f'gfl_quality: assigned must be int32 of shape {(B, A)}, anchors float32 {(A, 4)}, gts (B, K, 4)')
+    anchors, gts = _f32(anchors, 'gfl_quality').contiguous(), _f32(gts, 'gfl_quality').contiguous()
+    dev = assigned.device
+    weight = torch.empty(B, A, dtype=torch.float32, device=dev)
+    score = torch.empty(B, A, dtype=torch.float32, device=dev)
+    wsum = torch.empty(1, dtype=torch.float32, device=dev)
+    ws = torch.empty(max(capi.lib().htd_gfl_quality_workspace_bytes(B, A) // 8, 1), dtype=torch.float64, device=dev)
+    capi.call('htd_gfl_quality', ct, cs, rt, rs, sizes, st, L, B, cls_maps[0].size(1), int(reg_max), _P(anchors), _P(gts), gts.size(1),
+              _P(assigned.contiguous()), _P(weight), _P(score), _P(wsum), _P(ws), _S())
+    return weight, score, wsum
+
+
+class GflLossFunction(Function):
+    """htd_gfl_loss: the three losses of GFLHead.loss over every level and image in one launch, which also writes both finished
+    gradient maps (loss weights and normalisers applied); backward hands them over, after htd_gfl_grad_scale applies incoming
+    gradients other than 1 on the device, in place.  Single use: a second backward through the same forward raises."""
+
+    @staticmethod
+    def forward(ctx, st, sizes, C, reg_max, anchors, gts, gt_labels, assigned, weight, score, norm, wsum, box_kind, eps, beta,
+                cls_weight, box_weight, dfl_weight, *maps):
+        L = len(maps) // 2
+        cls, reg = maps[:L], maps[L:]
+        B, K = gt_labels.shape
+        ct, cs, _ = _level_tables(cls, 'gfl_loss')
+        rt, rs, _ = _level_tables(reg, 'gfl_loss')
+        gcls, gct = _grad_maps(cls, cs, 'gfl_loss')
+        greg, grt = _grad_maps(reg, rs, 'gfl_loss')
+        rows = capi.lib().htd_gfl_loss_partial_rows()
+        partial = torch.empty(rows, 2, device=assigned.device, dtype=torch.float32)
+        capi.call('htd_gfl_loss', ct, cs, rt, rs, sizes, st, L, B, int(C), int(reg_max), _P(anchors), _P(gts), _P(gt_labels), K,
+                  _P(assigned), _P(weight), _P(score), _P(norm), _P(wsum), int(box_kind), float(eps), float(beta),
+                  float(cls_weight), float(box_weight), float(dfl_weight), _P(partial), gct, grt, _S())
+        ctx.meta = (st, sizes, L, B, int(C), int(reg_max), K, int(box_kind), float(eps), float(box_weight), float(dfl_weight))
+        ctx.save_for_backward(anchors, gts, assigned, weight, wsum, *reg, *gcls, *greg)
+        sums = partial.view(2, rows // 2, 2).sum(1)             # [[qfl, box], [dfl, 0]]
+        # gfl_head.py:364-367: the averaging factor is not clamped (no positive: 0 / 0)
+        return sums[0, 0] / norm[0] * cls_weight, sums[0, 1] / wsum[0] * box_weight, sums[1, 0] / (4 * wsum[0]) * dfl_weight
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_cls, g_box, g_dfl):
+        st, sizes, L, B, C, reg_max, K, box_kind, eps, box_weight, dfl_weight = ctx.meta
+        anchors, gts, assigned, weight, wsum = ctx.saved_tensors[:5]
+        reg, gcls, greg = (ctx.saved_tensors[5 + i * L:5 + (i + 1) * L] for i in range(3))
+        gct, gcs, _ = _level_tables(gcls, 'gfl_loss')
+        rt, rs, _ = _level_tables(reg, 'gfl_loss')
+        grt, grs, _ = _level_tables(greg, 'gfl_loss')
+        assert list(grs) == list(rs)
+        _hand_over_once(ctx, 'gfl_loss', 'htd_gfl_grad_scale',
+                        (gct, gcs, rt, grt, rs, sizes, st, L, B, C, reg_max, _P(anchors), _P(gts), K, _P(assigned), _P(weight),
+                         _P(wsum), box_kind, eps, box_weight, dfl_weight), (g_cls, g_box, g_dfl))
+        return (None, ) * 18 + tuple(gcls) + tuple(greg)
+
+
+def gfl_loss(cls_maps, reg_maps, strides, reg_max, anchors, gts, gt_labels, assigned, weight, score, norm, wsum, box_kind,
+             eps=1e-6, beta=2.0, cls_weight=1.0, box_weight=1.0, dfl_weight=1.0):
+    """-> (loss_cls, loss_bbox, loss_dfl) of a GFL head from its per-level (B, C, h, w) / (B, 4 * (reg_max + 1), h, w) maps, the
+    (A, 4) anchors, the padded gts, `assigned` and `norm` of atss_targets and the outputs of gfl_quality.  box_kind:
+    FCOS_BOX_KINDS[type of the box loss]."""
+    *_, sizes, st, A = _gfl_tables(cls_maps, reg_maps, strides, reg_max, 'gfl_loss')
+    B = cls_maps[0].size(0)
+    if assigned.shape != (B, A) or assigned.dtype != torch.int32 or anchors.shape != (A, 4) or weight.shape != (B, A) or \
+            score.shape != (B, A) or gt_labels.dtype != torch.int64:
+        raise ValueError(f'gfl_loss: assigned must be int32 of shape {(B, A)}, anchors float32 {(A, 4)}, weight / score float32 '
+                         f'{(B, A)}, gt_labels int64')
+    return GflLossFunction.apply(st, sizes, cls_maps[0].size(1), reg_max, _f32(anchors, 'gfl_loss').contiguous(),
+                                 _f32(gts, 'gfl_loss').contiguous(), gt_labels.contiguous(), assigned.contiguous(),
+                                 _f32(weight, 'gfl_loss').contiguous(), _f32(score, 'gfl_loss').contiguous(),
+                                 _f32(norm, 'gfl_loss'), _f32(wsum, 'gfl_loss'), box_kind, eps, beta, cls_weight, box_weight,
+                                 dfl_weight, *cls_maps, *reg_maps)
+
+
+def gfl_decode(cls_maps, reg_maps, strides, reg_max):
+    """htd_gfl_decode, one launch: keys (B, A) = max_c sigmoid(cls) and dist (B, A, 4) = integral(reg) * stride of every anchor of
+    every level (level-major)."""
+    ct, cs, rt, rs, sizes, st, A = _gfl_tables(cls_maps, reg_maps, strides, reg_max, 'gfl_decode')
+    B = cls_maps[0].size(0)
+    keys = torch.empty(B, A, device=cls_maps[0].device, dtype=torch.float32)
+    dist = torch.empty(B, A, 4, device=cls_maps[0].device, dtype=torch.float32)
+    capi.call('htd_gfl_decode', ct, cs, rt, rs, sizes, st, len(cls_maps), B, cls_maps[0].size(1), int(reg_max), _P(keys), _P(dist),
+              _S())
+    return keys, dist

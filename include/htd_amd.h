@@ -808,6 +808,53 @@ int htd_atss_loss(const float *const *cls, const int64_t *cls_stride, const floa
                   int box_kind, double eps, float gamma, float alpha, float cls_weight, float box_weight, float ctr_weight,
                   float *partial, float *const *grad_cls, float *const *grad_reg, float *const *grad_ctr, void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * GFL head (dense_heads/gfl_head.py, losses/gfocal_loss.py).  The assignment is htd_atss_targets: its `assigned` and norm[0] are
+ * what these take.  anchors, level_sizes, gts and the map tables are as for the ATSS head; strides [L] HOST are the pyramid's;
+ * the classification map has C channels, the regression map 4 * (reg_max + 1) logits, side-major (reg_max 1 to 31).
+ * ---------------------------------------------------------------------------------- */
+/* What the averaging factor of GFLHead.loss depends on (gfl_head.py:254-265,364-365), one pass over the anchors.  Per positive:
+ *   weight [B][A]   max_c sigmoid(cls), the fp32 rounding of the fp64 sigmoid of the largest logit
+ *   score [B][A]    bbox_overlaps(distance2bbox(centre / stride, integral(reg)), gt / stride, is_aligned) with eps 1e-6 in the
+ *                   reference's fp32 order (the integral itself: fp64 softmax, rounded to fp32)
+ * both 0 on non-positives, every element written; wsum [1] = the sum of all weights in a fixed order (bitwise reproducible).
+ * workspace: htd_gfl_quality_workspace_bytes(B, A) bytes, 8-byte aligned. */
+int64_t htd_gfl_quality_workspace_bytes(int B, int64_t A);
+int htd_gfl_quality(const float *const *cls, const int64_t *cls_stride, const float *const *reg, const int64_t *reg_stride,
+                    const int64_t *level_sizes, const int64_t *strides, int L, int B, int C, int reg_max, const float *anchors,
+                    const float *gts, int K, const int *assigned, float *weight, float *score, float *wsum, void *workspace,
+                    void *stream);
+/* GFLHead.loss / loss_single (gfl_head.py:209-369) over all levels in one launch.  QFL (gfocal_loss.py:8-49, any beta; a fast
+ * form for beta == 2) of every (anchor, class): negatives supervised by 0, a positive's own class gt_labels[b][assigned - 1] by
+ * `score` under |score - sigmoid|^beta, neither factor detached.  Per positive the box loss (box_kind 0 = IoULoss, 2 =
+ * GIoULoss, as htd_fcos_loss) of the integral-decoded box against gt / stride times `weight`, and the DFL (:52-74) of the four
+ * sides, targets bbox2distance(centre / stride, gt / stride) clamped to [0, reg_max - 0.1], times `weight`.
+ * partial [htd_gfl_loss_partial_rows()][2]: rows 0 .. n/2 - 1 = per-block {sum QFL, sum weighted box loss}, rows n/2 .. =
+ * {sum weighted DFL, 0}, unscaled (add in row order: reproducible).  The gradient maps (layout of their inputs) receive
+ * d(cls_weight * qfl / norm[0]) and d(box_weight * box / wsum + dfl_weight * dfl / (4 * wsum)), the box part through the
+ * integral and the softmax; every element is written exactly once, padding channels (zeros) included.  wsum is NOT clamped
+ * (the reference's avg_factor): without positives the box and DFL sums are 0 over 0 and every regression gradient is NaN, as
+ * the reference's `bbox_pred.sum() * 0` branch gives; the classification part stays finite. */
+int htd_gfl_loss_partial_rows(void);
+int htd_gfl_loss(const float *const *cls, const int64_t *cls_stride, const float *const *reg, const int64_t *reg_stride,
+                 const int64_t *level_sizes, const int64_t *strides, int L, int B, int C, int reg_max, const float *anchors,
+                 const float *gts, const int64_t *gt_labels, int K, const int *assigned, const float *weight, const float *score,
+                 const float *norm, const float *wsum, int box_kind, double eps, float beta, float cls_weight, float box_weight,
+                 float dfl_weight, float *partial, float *const *grad_cls, float *const *grad_reg, void *stream);
+/* The gradient maps of htd_gfl_loss under the incoming gradients *g_cls / *g_box / *g_dfl (device scalars), in place: the
+ * classification map is multiplied; a positive's regression row, where box and DFL gradients are summed, is written again from
+ * the logits `reg` with its two parts scaled separately.  Factors of exactly 1 leave their maps untouched, decided on the device. */
+int htd_gfl_grad_scale(float *const *grad_cls, const int64_t *cls_stride, const float *const *reg, float *const *grad_reg,
+                       const int64_t *reg_stride, const int64_t *level_sizes, const int64_t *strides, int L, int B, int C,
+                       int reg_max, const float *anchors, const float *gts, int K, const int *assigned, const float *weight,
+                       const float *wsum, int box_kind, double eps, float box_weight, float dfl_weight, const float *g_cls,
+                       const float *g_box, const float *g_dfl, void *stream);
+/* GFLHead._get_bboxes_single (gfl_head.py:420-428) for every anchor of every level in one launch: keys [B][A] = max_c
+ * sigmoid(cls), dist [B][A][4] = integral(reg) * stride, fp32. */
+int htd_gfl_decode(const float *const *cls, const int64_t *cls_stride, const float *const *reg, const int64_t *reg_stride,
+                   const int64_t *level_sizes, const int64_t *strides, int L, int B, int C, int reg_max, float *keys, float *dist,
+                   void *stream);
+
 /* nn.MaxPool2d(kernel, stride, padding) of the ResNet stem (backbones/resnet.py:509,629) on NHWC maps
  * x [B][H][W][C] -> y [B][Ho][Wo][C], C % 4 == 0, padding = -inf, floor mode.  idx (may be NULL for inference; int32
  * [B][Ho][Wo][C]) records the input pixel hi*W+wi of the first maximum of each window; bwd sends the gradient there
