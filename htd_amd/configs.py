@@ -8,8 +8,9 @@ faster_rcnn_r50_fpn_1x_coco.py) and cascade_rcnn_config (configs/cascade_rcnn/ca
 their `_base_` chains merged, and so do the single-stage baselines retinanet_config (configs/retinanet/
 retinanet_r50_fpn_1x_coco.py), its GHM variant retinanet_ghm_config (configs/ghm/retinanet_ghm_r50_fpn_1x_coco.py) and
 fcos_config (the two configs/fcos/fcos_*_r50_caffe_fpn_gn-head_4x4_1x_coco.py), atss_config (configs/atss/
-atss_r50_fpn_1x_coco.py and its R101 sibling) and gfl_config (configs/gfl/gfl_r50_fpn_1x_coco.py and the mstrain 2x schedule
-of gfl_r101_fpn_mstrain_2x_coco.py).
+atss_r50_fpn_1x_coco.py and its R101 sibling), gfl_config (configs/gfl/gfl_r50_fpn_1x_coco.py and the mstrain 2x schedule
+of gfl_r101_fpn_mstrain_2x_coco.py) and vfnet_config (configs/vfnet/vfnet_r50_fpn_1x_coco.py and the mstrain 2x schedule of
+vfnet_r101_fpn_mstrain_2x_coco.py).
 """
 import copy
 
@@ -316,6 +317,43 @@ def gfl_config(depth=50, mstrain=False):
     return cfg
 
 
+def vfnet_model(depth=50):
+    """configs/vfnet/vfnet_r50_fpn_1x_coco.py: ATSS's backbone, FCOS's neck (P6 / P7 by convolutions on the ReLU of the output
+    P5), a VFNetHead of three tower convolutions -- VarifocalLoss on the IoU-aware score, GIoULoss of weight 1.5 on the initial
+    and of weight 2 on the refined box, ATSS targets."""
+    return dict(
+        type='VFNet', pretrained=f'torchvision://resnet{depth}', backbone=htd_model(depth)['backbone'],
+        neck=dict(type='FPN', in_channels=[256, 512, 1024, 2048], out_channels=256, start_level=1, add_extra_convs=True,
+                  extra_convs_on_inputs=False, num_outs=5, relu_before_extra_convs=True),
+        bbox_head=dict(type='VFNetHead', num_classes=80, in_channels=256, stacked_convs=3, feat_channels=256,
+                       strides=[8, 16, 32, 64, 128], center_sampling=False, dcn_on_last_conv=False, use_atss=True, use_vfl=True,
+                       loss_cls=dict(type='VarifocalLoss', use_sigmoid=True, alpha=0.75, gamma=2.0, iou_weighted=True,
+                                     loss_weight=1.0),
+                       loss_bbox=dict(type='GIoULoss', loss_weight=1.5), loss_bbox_refine=dict(type='GIoULoss', loss_weight=2.0)))
+
+
+def vfnet_config(depth=50, mstrain=False):
+    """vfnet_r{depth}_fpn_1x_coco, or with mstrain vfnet_r{depth}_fpn_mstrain_2x_coco: ATSS's training and test settings, lr 0.01
+    with doubled, undecayed biases (paramwise_cfg) and a linear warm-up from a tenth of the rate; the multi-scale schedule trains
+    24 epochs with steps at 16 / 22 on a short side drawn from [480, 960] (Resize in `range` mode).
+    (`python -m htd_amd.train` refuses paramwise_cfg: apis.check_supported.)"""
+    cfg = _baseline_config(vfnet_model(depth),
+                           dict(assigner=dict(type='ATSSAssigner', topk=9), allowed_border=-1, pos_weight=-1, debug=False), depth)
+    cfg.test_cfg = ConfigDict(nms_pre=1000, min_bbox_size=0, score_thr=0.05, nms=dict(type='nms', iou_threshold=0.6),
+                              max_per_img=100)
+    cfg.optimizer = ConfigDict(type='SGD', lr=0.01, momentum=0.9, weight_decay=0.0001,
+                               paramwise_cfg=dict(bias_lr_mult=2., bias_decay_mult=0.))
+    cfg.lr_config = ConfigDict(policy='step', warmup='linear', warmup_iters=500, warmup_ratio=0.1, step=[8, 11])
+    if mstrain:
+        cfg.lr_config.step = [16, 22]
+        cfg.total_epochs = 24
+        resize = cfg.data.train.pipeline[2]
+        assert resize['type'] == 'Resize'
+        cfg.data.train.pipeline[2] = ConfigDict(type='Resize', img_scale=[(1333, 480), (1333, 960)], multiscale_mode='range',
+                                                keep_ratio=True)
+    return cfg
+
+
 IMG_NORM_CFG = dict(mean=[123.675, 116.28, 103.53], std=[58.395, 57.12, 57.375], to_rgb=True)
 
 
@@ -427,13 +465,13 @@ def build_htd_detector(depth=50, dcn=False, cfg=None, bf16=False, resnext=False)
 
 
 def build_baseline_detector(kind='faster_rcnn', depth=50, cfg=None, bf16=False):
-    """kind = 'faster_rcnn' | 'cascade_rcnn' | 'faster_rcnn_gn_ws' | 'fcos' | 'fcos_center' | 'atss' | 'gfl' -> the detector of
-    faster_rcnn_config / cascade_rcnn_config / faster_rcnn_gn_ws_config / fcos_config (its two variants) / atss_config /
-    gfl_config (or of `cfg`), with the `pretrained` URL of the
+    """kind = 'faster_rcnn' | 'cascade_rcnn' | 'faster_rcnn_gn_ws' | 'fcos' | 'fcos_center' | 'atss' | 'gfl' | 'vfnet' -> the
+    detector of faster_rcnn_config / cascade_rcnn_config / faster_rcnn_gn_ws_config / fcos_config (its two variants) /
+    atss_config / gfl_config / vfnet_config (or of `cfg`), with the `pretrained` URL of the
     reference's config dropped: weights come from a checkpoint or from init_weights.  bf16 as in build_htd_detector."""
     makers = dict(faster_rcnn=faster_rcnn_config, cascade_rcnn=cascade_rcnn_config, faster_rcnn_gn_ws=faster_rcnn_gn_ws_config,
                   fcos=fcos_config, fcos_center=lambda d: fcos_config(d, 'center-normbbox-centeronreg-giou'), atss=atss_config,
-                  gfl=gfl_config)
+                  gfl=gfl_config, vfnet=vfnet_config)
     if cfg is None:
         if kind not in makers:
             raise ValueError(f'build_baseline_detector: kind must be one of {sorted(makers)}, got {kind!r}')

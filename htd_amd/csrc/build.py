@@ -19,7 +19,8 @@ EXTRA = {'nms.hip': ['-ffp-contract=off'], 'box_ops.hip': ['-ffp-contract=off'],
          'voc_eval.hip': ['-ffp-contract=off'], 'fcos.hip': ['-ffp-contract=off'],
          'ghm_loss.hip': ['-ffp-contract=off'],     # its two passes must bin an element alike
          'atss.hip': ['-ffp-contract=off'],         # distances and IoUs one rounded operation at a time
-         'gfl.hip': ['-ffp-contract=off']}          # centres, targets and IoU scores in the reference's fp32 order
+         'gfl.hip': ['-ffp-contract=off'],          # centres, targets and IoU scores in the reference's fp32 order
+         'vfnet.hip': ['-ffp-contract=off']}        # star offsets, target distances and both IoUs in that order too
 
 
 # Every *.hip / *.cpp of this directory is a translation unit of the library; what each one replaces (include/htd_amd.h cites
@@ -33,7 +34,9 @@ EXTRA = {'nms.hip': ['-ffp-contract=off'], 'box_ops.hip': ['-ffp-contract=off'],
 #                    (core/bbox/assigners/atss_assigner.py:33-178, dense_heads/atss_head.py:145-313)
 #   gfl.hip          GFLHead's quality pass, loss (QFL, weighted IoU / GIoU, DFL) and inference decode
 #                    (dense_heads/gfl_head.py:209-369,420-428, losses/gfocal_loss.py:8-74); level table of atss.hip (anchor_levels.h)
-# The five share focal_elem.h (the element arithmetic) and loss_units.h (level search, VEC-wide units, matrix units).
+#   vfnet.hip        VFNetHead's star offsets with their backward, quality pass and loss (varifocal loss, two IoU-weighted
+#                    IoU / GIoU losses) (dense_heads/vfnet_head.py:246-314,317-463, losses/varifocal_loss.py:8-53)
+# The six share focal_elem.h (the element arithmetic) and loss_units.h (level search, VEC-wide units, matrix units).
 def sources():
     return sorted(f for f in os.listdir(HERE) if f.endswith('.hip') or f.endswith('.cpp'))
 

@@ -340,6 +340,39 @@ class DistributionFocalLoss(nn.Module):
         return self.loss_weight * distribution_focal_loss(pred, target, weight, reduction=reduction, avg_factor=avg_factor)
 
 
+# ---------------------------------------------------------------- varifocal loss (varifocal_loss.py:8-131)
+def varifocal_loss(pred, target, weight=None, alpha=0.75, gamma=2.0, iou_weighted=True, reduction='mean', avg_factor=None):
+    """varifocal_loss.py:8-53: pred (N, C) logits, target (N, C) the IoU-aware classification score (the IoU at a positive's
+    own class, 0 elsewhere).  An element with a positive target is weighted by the target (or by 1 without iou_weighted), every
+    other one by alpha * |sigmoid - target|^gamma; then weight, reduction and avg_factor as weight_reduce_loss has them."""
+    assert pred.size() == target.size()
+    pred_sigmoid = pred.sigmoid()
+    target = target.type_as(pred)
+    positive = (target > 0.0).float()
+    focal_weight = (target * positive if iou_weighted else positive) + \
+        alpha * (pred_sigmoid - target).abs().pow(gamma) * (target <= 0.0).float()
+    loss = F.binary_cross_entropy_with_logits(pred, target, reduction='none') * focal_weight
+    return weight_reduce_loss(loss, weight, reduction, avg_factor)
+
+
+@LOSSES.register_module()
+class VarifocalLoss(nn.Module):
+    def __init__(self, use_sigmoid=True, alpha=0.75, gamma=2.0, iou_weighted=True, reduction='mean', loss_weight=1.0):
+        super().__init__()
+        assert use_sigmoid is True, 'Only sigmoid varifocal loss supported now.'
+        assert alpha >= 0.0
+        self.use_sigmoid, self.alpha, self.gamma, self.iou_weighted = use_sigmoid, alpha, gamma, iou_weighted
+        self.reduction, self.loss_weight = reduction, loss_weight
+
+    def forward(self, pred, target, weight=None, avg_factor=None, reduction_override=None):
+        assert reduction_override in (None, 'none', 'mean', 'sum')
+        reduction = reduction_override if reduction_override else self.reduction
+        if not self.use_sigmoid:
+            raise NotImplementedError
+        return self.loss_weight * varifocal_loss(pred, target, weight, alpha=self.alpha, gamma=self.gamma,
+                                                 iou_weighted=self.iou_weighted, reduction=reduction, avg_factor=avg_factor)
+
+
 # ---------------------------------------------------------------- gradient harmonising losses (ghm_loss.py:8-172)
 GHM_KERNEL_BINS = 64            # bins the kernels of csrc/ghm_loss.hip take
 

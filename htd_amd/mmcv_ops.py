@@ -1638,3 +1638,156 @@ def gfl_decode(cls_maps, reg_maps, strides, reg_max):
     capi.call('htd_gfl_decode', ct, cs, rt, rs, sizes, st, len(cls_maps), B, cls_maps[0].size(1), int(reg_max), _P(keys), _P(dist),
               _S())
     return keys, dist
+
+
+# ====================================================================== VFNet head (dense_heads/vfnet_head.py)
+class VfnetStarFunction(Function):
+    """htd_vfnet_star_fwd / _bwd: the scaled regression logits x (B, 4, H, W) of one level -> bbox_pred = exp(x) * denom and the
+    18-channel star offsets of it (vfnet_head.py:246-261,275-314) in one launch; backward folds the offsets' gradient into the
+    four sides in one more.  Either incoming gradient may be absent."""
+
+    @staticmethod
+    def forward(ctx, x, denom, stride, gradient_mul):
+        B, _, H, W = x.shape
+        xs = nhwc_channel_stride(x)
+        if xs is None:
+            x = x.contiguous(memory_format=CL)
+            xs = nhwc_channel_stride(x)
+        pred = _like_padded(x, xs)
+        off = torch.empty(B, 18, H, W, device=x.device, dtype=torch.float32, memory_format=CL)
+        capi.call('htd_vfnet_star_fwd', _P(x), xs, B, H, W, float(denom), float(stride), float(gradient_mul), _P(pred), xs, _P(off),
+                  18, _S())
+        ctx.meta = (B, H, W, xs, float(stride), float(gradient_mul))
+        ctx.save_for_backward(pred)
+        ctx.set_materialize_grads(False)
+        return pred, off
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_pred, g_off):
+        B, H, W, xs, stride, gm = ctx.meta
+        pred, = ctx.saved_tensors
+        if g_pred is None and g_off is None:
+            return None, None, None, None
+
+        def layout(g):
+            if g is None:
+                return None, 0
+            g = g.float()
+            if nhwc_channel_stride(g) is None:
+                g = g.contiguous(memory_format=CL)
+            return g, nhwc_channel_stride(g)
+        g_pred, gps = layout(g_pred)
+        g_off, gos = layout(g_off)
+        gx = _like_padded(pred, xs)
+        capi.call('htd_vfnet_star_bwd', _P(pred), xs, _P(g_pred), gps, _P(g_off), gos, B, H, W, stride, gm, _P(gx), xs, _S())
+        return gx, None, None, None
+
+
+def vfnet_star(x, denom, stride, gradient_mul):
+    """-> (bbox_pred (B, 4, H, W), dcn_offset (B, 18, H, W)) of the scaled regression logits x of one level (fp32, GPU)."""
+    _need_gpu(x, 'vfnet_star')
+    _f32(x, 'vfnet_star')
+    if x.dim() != 4 or x.size(1) != 4:
+        raise ValueError(f'vfnet_star: x must be (B, 4, H, W), got {tuple(x.shape)}')
+    return VfnetStarFunction.apply(x, denom, stride, gradient_mul)
+
+
+def _vfnet_tables(cls_maps, reg_maps, ref_maps, what):
+    """-> (classification table, strides, initial table, strides, refined table, strides, level sizes, A), all HOST tables; the
+    maps checked for dtype and shapes.  cls_maps may be None (the quality pass reads no logits)."""
+    _need_gpu(reg_maps[0], what)
+    if len(ref_maps) != len(reg_maps) or (cls_maps is not None and len(cls_maps) != len(reg_maps)):
+        raise ValueError(f'{what}: the three lists of maps must have one entry per level')
+    for l, (r, f) in enumerate(zip(reg_maps, ref_maps)):
+        _f32(r, what)
+        _f32(f, what)
+        c = cls_maps[l] if cls_maps is not None else r
+        _f32(c, what)
+        if r.size(1) != 4 or f.shape != r.shape or c.shape[-2:] != r.shape[-2:] or c.size(0) != r.size(0):
+            raise ValueError(f'{what}: regression maps of shapes {tuple(r.shape)} / {tuple(f.shape)} beside a classification map '
+                             f'{tuple(c.shape)}')
+    ct, cs = (None, None) if cls_maps is None else _level_tables(cls_maps, what)[:2]
+    rt, rs, pix = _level_tables(reg_maps, what)
+    ft, fs, _ = _level_tables(ref_maps, what)
+    return ct, cs, rt, rs, ft, fs, pix, sum(pix)
+
+
+def vfnet_quality(reg_maps, ref_maps, anchors, gts, assigned):
+    """htd_vfnet_quality: per positive of `assigned` (B, A) (atss_targets) the IoU of its initial and of its refined box with its
+    gt, clamped to at least 1e-6, 0 elsewhere: the box weights, the varifocal targets and, with the number of positives, the three
+    averaging factors of VFNetHead.loss.  -> iou_ini (B, A), iou_rf (B, A), sums (3,) = [positives, sum iou_ini, sum iou_rf];
+    nothing read back."""
+    _, _, rt, rs, ft, fs, sizes, A = _vfnet_tables(None, reg_maps, ref_maps, 'vfnet_quality')
+    B, L = reg_maps[0].size(0), len(reg_maps)
+    if assigned.shape != (B, A) or assigned.dtype != torch.int32 or anchors.shape != (A, 4) or gts.dim() != 3 or gts.size(0) != B:
+        raise ValueError(f'vfnet_quality: assigned must be int32 of shape {(B, A)}, anchors float32 {(A, 4)}, gts (B, K, 4)')
+    anchors, gts = _f32(anchors, 'vfnet_quality').contiguous(), _f32(gts, 'vfnet_quality').contiguous()
+    dev = assigned.device
+    iou_ini = torch.empty(B, A, dtype=torch.float32, device=dev)
+    iou_rf = torch.empty(B, A, dtype=torch.float32, device=dev)
+    sums = torch.empty(3, dtype=torch.float32, device=dev)
+    ws = torch.empty(max(capi.lib().htd_vfnet_quality_workspace_bytes(B, A) // 8, 1), dtype=torch.float64, device=dev)
+    capi.call('htd_vfnet_quality', rt, rs, ft, fs, sizes, L, B, _P(anchors), _P(gts), gts.size(1), _P(assigned.contiguous()),
+              _P(iou_ini), _P(iou_rf), _P(sums), _P(ws), _S())
+    return iou_ini, iou_rf, sums
+
+
+class VfnetLossFunction(Function):
+    """htd_vfnet_loss: the three losses of VFNetHead.loss over every level and image in one launch, which also writes the three
+    finished gradient maps (loss weights and normalisers applied); backward hands them over, after htd_vfnet_grad_scale applies
+    incoming gradients other than 1 on the device, in place.  Single use: a second backward through the same forward raises."""
+
+    @staticmethod
+    def forward(ctx, sizes, C, anchors, gts, gt_labels, assigned, iou_ini, iou_rf, sums, box_kind, eps_ini, ref_kind, eps_rf,
+                alpha, gamma, iou_weighted, cls_weight, box_weight, ref_weight, *maps):
+        L = len(maps) // 3
+        cls, reg, ref = maps[:L], maps[L:2 * L], maps[2 * L:]
+        B, K = gt_labels.shape
+        ct, cs, _ = _level_tables(cls, 'vfnet_loss')
+        rt, rs, _ = _level_tables(reg, 'vfnet_loss')
+        ft, fs, _ = _level_tables(ref, 'vfnet_loss')
+        gcls, gct = _grad_maps(cls, cs, 'vfnet_loss')
+        greg, grt = _grad_maps(reg, rs, 'vfnet_loss')
+        gref, gft = _grad_maps(ref, fs, 'vfnet_loss')
+        rows = capi.lib().htd_vfnet_loss_partial_rows()
+        partial = torch.empty(rows, 2, device=assigned.device, dtype=torch.float32)
+        capi.call('htd_vfnet_loss', ct, cs, rt, rs, ft, fs, sizes, L, B, int(C), _P(anchors), _P(gts), _P(gt_labels), K, _P(assigned),
+                  _P(iou_ini), _P(iou_rf), _P(sums), int(box_kind), float(eps_ini), int(ref_kind), float(eps_rf), float(alpha),
+                  float(gamma), int(bool(iou_weighted)), float(cls_weight), float(box_weight), float(ref_weight), _P(partial), gct,
+                  grt, gft, _S())
+        ctx.meta = (sizes, L, B, int(C))
+        ctx.save_for_backward(*gcls, *greg, *gref)
+        tot = partial.view(2, rows // 2, 2).sum(1)              # [[vfl, initial box], [refined box, 0]]
+        norm = sums.clamp(min=1.0)                              # vfnet_head.py:396,414,430: each factor at least 1
+        return tot[0, 0] / norm[0] * cls_weight, tot[0, 1] / norm[1] * box_weight, tot[1, 0] / norm[2] * ref_weight
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_cls, g_box, g_ref):
+        sizes, L, B, C = ctx.meta
+        grads = ctx.saved_tensors
+        gct, gcs, _ = _level_tables(grads[:L], 'vfnet_loss')
+        grt, grs, _ = _level_tables(grads[L:2 * L], 'vfnet_loss')
+        gft, gfs, _ = _level_tables(grads[2 * L:], 'vfnet_loss')
+        _hand_over_once(ctx, 'vfnet_loss', 'htd_vfnet_grad_scale', (gct, gcs, grt, grs, gft, gfs, sizes, L, B, C),
+                        (g_cls, g_box, g_ref))
+        return (None, ) * 19 + tuple(grads)
+
+
+def vfnet_loss(cls_maps, reg_maps, ref_maps, anchors, gts, gt_labels, assigned, iou_ini, iou_rf, sums, box_kind, ref_kind,
+               eps_ini=1e-6, eps_rf=1e-6, alpha=0.75, gamma=2.0, iou_weighted=True, cls_weight=1.0, box_weight=1.0, ref_weight=1.0):
+    """-> (loss_cls, loss_bbox, loss_bbox_rf) of a VFNet head from its per-level (B, C, h, w) / (B, 4, h, w) / (B, 4, h, w) maps,
+    the (A, 4) anchors, the padded gts, `assigned` of atss_targets and the outputs of vfnet_quality.  box_kind / ref_kind:
+    FCOS_BOX_KINDS[type of the box loss]."""
+    *_, sizes, A = _vfnet_tables(cls_maps, reg_maps, ref_maps, 'vfnet_loss')
+    B = cls_maps[0].size(0)
+    if assigned.shape != (B, A) or assigned.dtype != torch.int32 or anchors.shape != (A, 4) or iou_ini.shape != (B, A) or \
+            iou_rf.shape != (B, A) or gt_labels.dtype != torch.int64 or sums.shape != (3, ):
+        raise ValueError(f'vfnet_loss: assigned must be int32 of shape {(B, A)}, anchors float32 {(A, 4)}, iou_ini / iou_rf float32 '
+                         f'{(B, A)}, gt_labels int64, sums float32 (3,)')
+    return VfnetLossFunction.apply(sizes, cls_maps[0].size(1), _f32(anchors, 'vfnet_loss').contiguous(),
+                                   _f32(gts, 'vfnet_loss').contiguous(), gt_labels.contiguous(), assigned.contiguous(),
+                                   _f32(iou_ini, 'vfnet_loss').contiguous(), _f32(iou_rf, 'vfnet_loss').contiguous(),
+                                   _f32(sums, 'vfnet_loss').contiguous(), box_kind, eps_ini, ref_kind, eps_rf, alpha, gamma,
+                                   iou_weighted, cls_weight, box_weight, ref_weight, *cls_maps, *reg_maps, *ref_maps)

@@ -855,6 +855,59 @@ int htd_gfl_decode(const float *const *cls, const int64_t *cls_stride, const flo
                    const int64_t *level_sizes, const int64_t *strides, int L, int B, int C, int reg_max, float *keys, float *dist,
                    void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * VFNet head (dense_heads/vfnet_head.py, losses/varifocal_loss.py).  The assignment is htd_atss_targets: its `assigned` is what
+ * these take (NOT its norm[0], which counts an image without positives as one).  anchors, level_sizes, gts and the map tables are
+ * as for the ATSS head; the classification map has C channels, the two regression maps (initial, refined) four distances
+ * (l, t, r, b) in image units.
+ * ---------------------------------------------------------------------------------- */
+/* forward_single :246-261 with star_dcn_offset :275-314 for one level.  x [B][H][W][x_stride >= 4]: the scaled regression
+ * logits.  bbox_pred = exp(x) * denom (reg_denom or the stride; the exponential correctly rounded); dcn_offset [B][H][W]
+ * [offset_stride >= 18] = the star offsets of ((1 - gradient_mul) * bbox_pred + gradient_mul * bbox_pred) / stride in that fp32
+ * order, signs and channels as :300-311, minus dcn_base_offset (the six untouched channels: 0 - base).  Padding channels of
+ * both outputs are written as zeros. */
+int htd_vfnet_star_fwd(const float *x, int64_t x_stride, int B, int H, int W, double denom, double stride, double gradient_mul,
+                       float *bbox_pred, int64_t pred_stride, float *dcn_offset, int64_t offset_stride, void *stream);
+/* Its backward: g_x = (g_pred + (gradient_mul / stride) * fold(g_offset)) * bbox_pred with fold l = -(g1 + g7 + g13),
+ * t = -(g0 + g2 + g4), r = g5 + g11 + g17, b = g12 + g14 + g16.  g_pred and g_offset may each be NULL (no such gradient). */
+int htd_vfnet_star_bwd(const float *bbox_pred, int64_t pred_stride, const float *g_pred, int64_t g_pred_stride,
+                       const float *g_offset, int64_t g_offset_stride, int B, int H, int W, double stride, double gradient_mul,
+                       float *g_x, int64_t x_stride, void *stream);
+/* What the averaging factors of VFNetHead.loss depend on (:384-430), one pass over the anchors.  Per positive (assigned > 0): the
+ * point is the anchor's centre, the target distances bbox2distance(point, gt), both sides decoded through distance2bbox, and
+ *   iou_ini [B][A] / iou_rf [B][A]   bbox_overlaps(decoded initial / refined box, decoded target, is_aligned).clamp(min=1e-6)
+ * in the reference's fp32 order, 0 on background, every element written; sums [3] = {number of positives, sum iou_ini, sum
+ * iou_rf} in a fixed order (bitwise reproducible), not clamped.
+ * workspace: htd_vfnet_quality_workspace_bytes(B, A) bytes, 8-byte aligned. */
+int64_t htd_vfnet_quality_workspace_bytes(int B, int64_t A);
+int htd_vfnet_quality(const float *const *reg, const int64_t *reg_stride, const float *const *ref, const int64_t *ref_stride,
+                      const int64_t *level_sizes, int L, int B, const float *anchors, const float *gts, int K,
+                      const int *assigned, float *iou_ini, float *iou_rf, float *sums, void *workspace, void *stream);
+/* VFNetHead.loss (:317-463) over all levels in one launch.  Varifocal loss (varifocal_loss.py:8-53, any gamma; a fast form for
+ * gamma == 2) of every (anchor, class): target iou_rf at a positive's own class gt_labels[b][assigned - 1] (weight iou_rf, or 1
+ * without iou_weighted), 0 elsewhere (weight alpha * sigmoid^gamma).  Per positive the box loss (box_kind / ref_kind 0 = IoULoss,
+ * 2 = GIoULoss, as htd_fcos_loss, with the losses' own eps) of the initial box times iou_ini and of the refined box times iou_rf,
+ * targets and weights detached.  sums [3] as htd_vfnet_quality leaves them (or their mean over processes); each is clamped to
+ * at least 1 here.
+ * partial [htd_vfnet_loss_partial_rows()][2]: rows 0 .. n/2 - 1 = per-block {sum VFL, sum weighted initial box loss}, rows
+ * n/2 .. = {sum weighted refined box loss, 0}, unscaled (add in row order: reproducible).  The gradient maps (layout of their
+ * inputs) receive d(cls_weight * vfl / max(sums[0], 1)), d(box_weight * box / max(sums[1], 1)) and d(ref_weight * refined /
+ * max(sums[2], 1)); every element is written exactly once, padding channels (zeros) included.  Without positives both box
+ * losses and their gradients are exactly 0. */
+int htd_vfnet_loss_partial_rows(void);
+int htd_vfnet_loss(const float *const *cls, const int64_t *cls_stride, const float *const *reg, const int64_t *reg_stride,
+                   const float *const *ref, const int64_t *ref_stride, const int64_t *level_sizes, int L, int B, int C,
+                   const float *anchors, const float *gts, const int64_t *gt_labels, int K, const int *assigned,
+                   const float *iou_ini, const float *iou_rf, const float *sums, int box_kind, double eps_ini, int ref_kind,
+                   double eps_rf, float alpha, float gamma, int iou_weighted, float cls_weight, float box_weight, float ref_weight,
+                   float *partial, float *const *grad_cls, float *const *grad_reg, float *const *grad_ref, void *stream);
+/* The gradient maps of htd_vfnet_loss times the incoming gradients *g_cls / *g_box / *g_ref (device scalars), in place.  Factors
+ * of exactly 1 leave their maps untouched, decided on the device.  (htd_fcos_grad_scale does not fit: its third map has one
+ * channel.) */
+int htd_vfnet_grad_scale(float *const *grad_cls, const int64_t *cls_stride, float *const *grad_reg, const int64_t *reg_stride,
+                         float *const *grad_ref, const int64_t *ref_stride, const int64_t *level_sizes, int L, int B, int C,
+                         const float *g_cls, const float *g_box, const float *g_ref, void *stream);
+
 /* nn.MaxPool2d(kernel, stride, padding) of the ResNet stem (backbones/resnet.py:509,629) on NHWC maps
  * x [B][H][W][C] -> y [B][Ho][Wo][C], C % 4 == 0, padding = -inf, floor mode.  idx (may be NULL for inference; int32
  * [B][Ho][Wo][C]) records the input pixel hi*W+wi of the first maximum of each window; bwd sends the gradient there
