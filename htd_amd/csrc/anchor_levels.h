@@ -1,12 +1,12 @@
-// What atss.hip and gfl.hip share: the level table of a pyramid with one anchor per location, the float4 load of a box and the
-// reference's fp32 IoU.  One implementation each; the kernels keep their own loops.
+// What atss.hip, gfl.hip and vfnet.hip share beyond point_maps.h: the level table of a pyramid with one anchor per location, the
+// float4 load of a box and the reference's fp32 IoU.  One implementation each; the kernels keep their own loops.
 #pragma once
 #include "common.h"
+#include "point_maps.h"
 
 namespace {
 
-constexpr int ATSS_BLOCKS = 2048;           // 256 CUs x 8 blocks: the cap of a memory-bound grid; the rest is grid-stride
-constexpr int ATSS_MAX_LEVELS = 8;
+constexpr int ATSS_MAX_LEVELS = POINT_MAX_LEVELS;
 
 struct AtssLevels {
     unsigned aoff[ATSS_MAX_LEVELS + 1];     // first anchor of the level; aoff[L] = A (one anchor per location)

@@ -5,18 +5,16 @@
 // are the reference's fp32 values one rounded operation at a time (dx * dx + dy * dy is two products and a sum), divisions and
 // square roots are correctly rounded (-fhip-fp32-correctly-rounded-divide-sqrt), and the logarithm and exponential of the delta
 // coding are the fp32 roundings of the fp64 functions.  The box loss is the fp64 iou_family_loss of the RoI heads, the
-// classification loss the focal_elem of the anchor heads, the map addressing that of loss_units.h: one implementation each.
+// classification loss the sweep of point_maps.h with the focal_elem of the anchor heads: one implementation each.
 //
 // The ranking keys of get_bboxes are htd_fcos_keys and the scaling of the gradient maps by incoming gradients is
-// htd_fcos_grad_scale (fcos.hip): the layouts are the same.
+// htd_fcos_grad_scale (fcos.hip): the map table is the same.
 //
 // No float atomics: the one atomic is a 64-bit integer maximum, which does not depend on the order it is taken in; every sum
 // has a fixed order; every element of every output is stored exactly once with plain vector stores.
 #include "common.h"
 #include "anchor_levels.h"
-#include "focal_elem.h"
 #include "iou_family.h"
-#include "loss_units.h"
 
 namespace {
 
@@ -28,15 +26,7 @@ struct AtssCoder {                          // DeltaXYWHBBoxCoder: means, stds, 
     double mean_d[4], std_d[4], max_ratio_d;    // as its fp64 run does
 };
 
-struct AtssMaps {
-    const float *cls[ATSS_MAX_LEVELS], *reg[ATSS_MAX_LEVELS], *ctr[ATSS_MAX_LEVELS];
-    float *gcls[ATSS_MAX_LEVELS], *greg[ATSS_MAX_LEVELS], *gctr[ATSS_MAX_LEVELS];
-    unsigned pix[ATSS_MAX_LEVELS];
-    unsigned cu[ATSS_MAX_LEVELS];           // units per pixel of the classification map (channel stride / VEC)
-    unsigned rs[ATSS_MAX_LEVELS];           // channel stride of the regression map in floats (>= 4)
-    unsigned ts[ATSS_MAX_LEVELS];           // channel stride of the centerness map in floats (>= 1)
-    unsigned rrow[ATSS_MAX_LEVELS + 1];     // prefix sums of B * pix: the pixel rows of all levels
-};
+enum { CLS = 0, REG = 1, CTR = 2 };       // slots of PointMaps: (B, C, h, w), (B, 4, h, w), (B, 1, h, w)
 
 __device__ __forceinline__ float log_rounded(float x) { return (float)log((double)x); }
 __device__ __forceinline__ float exp_rounded(float x) { return (float)exp((double)x); }
@@ -224,71 +214,33 @@ __global__ __launch_bounds__(64) void atss_targets_finish_kernel(const int *__re
 }
 
 // ---- loss --------------------------------------------------------------------------------------------------------------------
-// Classification maps: a lane group per pixel row [cu units], one anchor per pixel, every anchor with label weight 1.  Then one
-// thread per anchor for the four deltas and the centerness logit.  partial [ATSS_BLOCKS][2] = {sum focal, sum ctr_target * box
-// loss}, partial + 2 * ATSS_BLOCKS: [ATSS_BLOCKS][2] = {sum centerness BCE, 0}, unscaled.
+// Classification maps: the sweep of point_maps.h with plain focal elements, one anchor per pixel, every anchor with label weight
+// 1.  Then one thread per anchor for the four deltas and the centerness logit.  partial [POINT_BLOCKS][2] = {sum focal, sum
+// ctr_target * box loss}, partial + 2 * POINT_BLOCKS: [POINT_BLOCKS][2] = {sum centerness BCE, 0}, unscaled.
 template <int VEC, bool G2>
-__global__ __launch_bounds__(256) void atss_loss_kernel(AtssMaps mp, AtssLevels lv, int L, int C, const float *__restrict__ anchors,
+__global__ __launch_bounds__(256) void atss_loss_kernel(PointMaps mp, AtssLevels lv, int L, int C, const float *__restrict__ anchors,
                                                         const float *__restrict__ gts, const int64_t *__restrict__ gt_labels, int K,
                                                         const int *__restrict__ assigned, const float *__restrict__ ctr_targets,
                                                         const float *__restrict__ norm, AtssCoder cd, int box_kind, double eps,
                                                         float gamma, float alpha, float cls_weight, float box_weight,
                                                         float ctr_weight, int group_shift, float *__restrict__ partial)
 {
-    const unsigned A = lv.aoff[L];
-    const float cs = cls_weight / norm[0];
     const unsigned n_rows = mp.rrow[L];
-    float s_cls = 0.f;
-    const unsigned lane = threadIdx.x & 63u;
-    const unsigned gl = 1u << group_shift, sub = lane & (gl - 1u), rpw = 64u >> group_shift;
-    const unsigned wave = blockIdx.x * 4u + (threadIdx.x >> 6);
-    for (unsigned rw0 = wave * rpw; rw0 < n_rows; rw0 += gridDim.x * 4u * rpw) {
-        const unsigned rw = rw0 + (lane >> group_shift);
-        if (rw >= n_rows) continue;
-        const int l = level_of(mp.rrow, L, rw);
-        const unsigned row = rw - mp.rrow[l];                                       // b * pix + p
-        const unsigned b = row / mp.pix[l], p = row - b * mp.pix[l];
-        const unsigned cu = mp.cu[l];
-        const int as = assigned[(int64_t)b * A + lv.aoff[l] + p];
-        const int64_t lab = as > 0 ? gt_labels[(int64_t)b * K + (as - 1)] : (int64_t)C;
-        const float *x_row = mp.cls[l] + (int64_t)row * cu * VEC;
-        float *g_row = mp.gcls[l] + (int64_t)row * cu * VEC;
-        for (unsigned j = sub; j < cu; j += gl) {
-            const unsigned c0 = j * VEC;
-            float go[VEC];
-#pragma unroll
-            for (int k = 0; k < VEC; ++k) go[k] = 0.f;
-            if (c0 < (unsigned)C) {                                                 // (VEC = 4: C % 4 == 0, whole units)
-                float xv[VEC];
-                load_unit<VEC>(x_row, j, xv);
-#pragma unroll
-                for (int k = 0; k < VEC; ++k) {
-                    float g;
-                    s_cls += focal_elem<G2>(xv[k], lab == (int64_t)(c0 + k), gamma, alpha, g);
-                    go[k] = g * cs;
-                }
-            }
-            store_unit<VEC>(g_row, j, go);
-        }
-    }
+    const float s_cls = cls_sweep<VEC>(mp, lv.aoff, L, C, assigned, gt_labels, K, nullptr, cls_weight / norm[0], group_shift,
+                                       [=](float x, bool own, float, float &g) { return focal_elem<G2>(x, own, gamma, alpha, g); });
     // the anchors: prediction and target decoded against the anchor (delta2bbox of the deltas, and of bbox2delta of the gt), the
     // box loss weighted by the centerness target over norm[2] (1 where that is below EPS), the centerness BCE-with-logits over
     // norm[1]; both in fp64 on the few positives
     const double nb = (double)norm[2] < ATSS_EPS ? 1. : (double)norm[2];
     double s_box = 0., s_ctr = 0.;
     for (unsigned rw = blockIdx.x * 256u + threadIdx.x; rw < n_rows; rw += gridDim.x * 256u) {
-        const int l = level_of(mp.rrow, L, rw);
-        const unsigned row = rw - mp.rrow[l];
-        const unsigned b = row / mp.pix[l], p = row - b * mp.pix[l];
-        const unsigned rs = mp.rs[l], ts = mp.ts[l];
-        const unsigned ai = lv.aoff[l] + p;
-        const int64_t o = (int64_t)b * A + ai;
+        const PointRow r = point_row(mp, lv.aoff, L, rw);
         float gr[4] = {0.f, 0.f, 0.f, 0.f}, gc = 0.f;
-        const int as = assigned[o];
+        const int as = assigned[r.o];
         if (as > 0) {
-            const float4 a = load4(anchors, ai), g = load4(gts, (int64_t)b * K + (as - 1));
-            const float *d = mp.reg[l] + (int64_t)row * rs;
-            const double w = (double)ctr_targets[o];
+            const float4 a = load4(anchors, r.i), g = load4(gts, (int64_t)r.b * K + (as - 1));
+            const float *d = slot_row(mp, REG, r);
+            const double w = (double)ctr_targets[r.o];
             const double px = ((double)a.x + a.z) * 0.5, py = ((double)a.y + a.w) * 0.5, pw = (double)a.z - a.x, ph = (double)a.w - a.y;
             const double *m = cd.mean_d, *s = cd.std_d;
             // the target in fp32, as the reference's fp64 run has it too (bbox2delta works in fp32); the prediction in fp64
@@ -309,20 +261,18 @@ __global__ __launch_bounds__(256) void atss_loss_kernel(AtssMaps mp, AtssLevels 
             gr[1] = (float)((G.y1 + G.y2) * ph * s[1] * bs);
             gr[2] = in_w ? (float)((G.x2 - G.x1) * 0.5 * qw * s[2] * bs) : 0.f;
             gr[3] = in_h ? (float)((G.y2 - G.y1) * 0.5 * qh * s[3] * bs) : 0.f;
-            const double z = (double)mp.ctr[l][(int64_t)row * ts];
-            const double ez = exp(-fabs(z));
-            s_ctr += fmax(z, 0.) - z * w + log1p(ez);
-            const double sig = z >= 0. ? 1. / (1. + ez) : ez / (1. + ez);
+            const double z = (double)slot_row(mp, CTR, r)[0];
+            double l1p, sig;
+            sigmoid_log1p(z, l1p, sig);
+            s_ctr += fmax(z, 0.) - z * w + l1p;
             gc = (float)((sig - w) * (double)ctr_weight / (double)norm[1]);
         }
-        float *g_reg = mp.greg[l] + (int64_t)row * rs;
-        for (unsigned k = 0; k < rs; ++k) g_reg[k] = k < 4u ? gr[k] : 0.f;
-        float *g_ctr = mp.gctr[l] + (int64_t)row * ts;
-        for (unsigned k = 0; k < ts; ++k) g_ctr[k] = k == 0u ? gc : 0.f;
+        store_padded(slot_grad_row(mp, REG, r), mp.cs[REG][r.l], gr, 4u);
+        store_padded(slot_grad_row(mp, CTR, r), mp.cs[CTR][r.l], &gc, 1u);
     }
     block_store_partial2(s_cls, (float)s_box, partial);
     __syncthreads();                        // the reduction's LDS is read before the second pair overwrites it
-    block_store_partial2((float)s_ctr, 0.f, partial + 2 * ATSS_BLOCKS);
+    block_store_partial2((float)s_ctr, 0.f, partial + 2 * POINT_BLOCKS);
 }
 
 int fill_coder(AtssCoder &cd, const char *what, const double *means4, const double *stds4, double wh_ratio_clip)
@@ -341,44 +291,11 @@ int fill_coder(AtssCoder &cd, const char *what, const double *means4, const doub
     return HTD_OK;
 }
 
-// vec: units of the classification map (4: float4 units, 1: floats)
-int fill_maps(AtssMaps &mp, const char *what, const AtssLevels &lv, const float *const *cls, const int64_t *cls_stride,
-              const float *const *reg, const int64_t *reg_stride, const float *const *ctr, const int64_t *ctr_stride,
-              float *const *gcls, float *const *greg, float *const *gctr, int L, int B, int C, int vec)
-{
-    HTD_REQUIRE(B > 0 && C > 0, "%s: bad sizes", what);
-    HTD_REQUIRE(cls && cls_stride && reg && reg_stride && ctr && ctr_stride && gcls && greg && gctr, "%s: null table", what);
-    int64_t rrow = 0, elems = 0;
-    for (int l = 0; l < L; ++l) {
-        const int64_t pix = (int64_t)lv.aoff[l + 1] - lv.aoff[l];
-        HTD_REQUIRE(cls_stride[l] >= C && cls_stride[l] % vec == 0, "%s: bad classification stride of level %d", what, l);
-        HTD_REQUIRE(cls[l] && gcls[l] && (vec != 4 || (((uintptr_t)cls[l] | (uintptr_t)gcls[l]) & 15) == 0),
-                    "%s: classification map of level %d is null or not 16-byte aligned", what, l);
-        HTD_REQUIRE(reg_stride[l] >= 4 && reg[l] && greg[l], "%s: bad regression map of level %d", what, l);
-        HTD_REQUIRE(ctr_stride[l] >= 1 && ctr[l] && gctr[l], "%s: bad centerness map of level %d", what, l);
-        mp.cls[l] = cls[l]; mp.gcls[l] = gcls[l];
-        mp.reg[l] = reg[l]; mp.greg[l] = greg[l];
-        mp.ctr[l] = ctr[l]; mp.gctr[l] = gctr[l];
-        mp.pix[l] = (unsigned)pix;
-        mp.cu[l] = (unsigned)(cls_stride[l] / vec);
-        mp.rs[l] = (unsigned)reg_stride[l];
-        mp.ts[l] = (unsigned)ctr_stride[l];
-        mp.rrow[l] = (unsigned)rrow;
-        rrow += (int64_t)B * pix;
-        elems += (int64_t)B * pix * (cls_stride[l] + reg_stride[l] + ctr_stride[l]);
-    }
-    for (int l = L; l <= ATSS_MAX_LEVELS; ++l) mp.rrow[l] = (unsigned)rrow;
-    HTD_REQUIRE(rrow < ((int64_t)1 << 31) && elems < ((int64_t)1 << 40), "%s: more than 2^31 pixel rows", what);
-    return HTD_OK;
-}
-
 }  // namespace
-
-static int64_t atss_blocks(int64_t A) { return (A + 255) / 256; }
 
 extern "C" int64_t htd_atss_targets_workspace_bytes(int B, int64_t A)
 {
-    return (int64_t)B * A * 8 + (int64_t)B * atss_blocks(A) * 16;      // the words, then one double and one int (padded) per block
+    return (int64_t)B * A * 8 + (int64_t)B * blocks_of(A) * 16;      // the words, then one double and one int (padded) per block
 }
 
 extern "C" int htd_atss_targets(const float *anchors, const int64_t *level_sizes, int L, const float *gts, const uint8_t *gt_valid,
@@ -398,7 +315,7 @@ extern "C" int htd_atss_targets(const float *anchors, const int64_t *level_sizes
     rc = fill_coder(cd, "atss_targets", means4, stds4, wh_ratio_clip);
     if (rc != HTD_OK) return rc;
     HTD_REQUIRE((int64_t)B * A < ((int64_t)1 << 31), "atss_targets: more than 2^31 anchors in the batch");
-    const int nblk = (int)atss_blocks(A);
+    const int nblk = (int)blocks_of(A);
     unsigned long long *best = (unsigned long long *)workspace;
     double *part_c = (double *)(best + (int64_t)B * A);
     int *part_n = (int *)(part_c + (int64_t)B * nblk);
@@ -415,7 +332,7 @@ extern "C" int htd_atss_targets(const float *anchors, const int64_t *level_sizes
     return htd::check_launch("atss_targets");
 }
 
-extern "C" int htd_atss_loss_partial_rows(void) { return 2 * ATSS_BLOCKS; }
+extern "C" int htd_atss_loss_partial_rows(void) { return 2 * POINT_BLOCKS; }
 
 extern "C" int htd_atss_loss(const float *const *cls, const int64_t *cls_stride, const float *const *reg, const int64_t *reg_stride,
                              const float *const *ctr, const int64_t *ctr_stride, const int64_t *level_sizes, int L, int B, int C,
@@ -435,25 +352,13 @@ extern "C" int htd_atss_loss(const float *const *cls, const int64_t *cls_stride,
     AtssCoder cd = {};
     rc = fill_coder(cd, "atss_loss", means4, stds4, wh_ratio_clip);
     if (rc != HTD_OK) return rc;
-    bool vec = (C & 3) == 0;
-    for (int l = 0; l < L && vec; ++l) vec = cls_stride && (cls_stride[l] & 3) == 0;
-    AtssMaps mp = {};
-    rc = fill_maps(mp, "atss_loss", lv, cls, cls_stride, reg, reg_stride, ctr, ctr_stride, grad_cls, grad_reg, grad_ctr, L, B, C,
-                   vec ? 4 : 1);
+    const SweepForm f = sweep_form(C, cls_stride, L);
+    const PointSlot slots[POINT_SLOTS] = {{cls, grad_cls, cls_stride, C, true, true}, {reg, grad_reg, reg_stride, 4, true, true},
+                                          {ctr, grad_ctr, ctr_stride, 1, true, true}};
+    PointMaps mp = {};
+    rc = fill_point_maps(mp, "atss_loss", lv.aoff, L, B, slots, f.vec);
     if (rc != HTD_OK) return rc;
-    HTD_REQUIRE((int64_t)B * A < ((int64_t)1 << 31), "atss_loss: more than 2^31 anchors in the batch");
-    // lanes per pixel row of the classification sweep: the smallest power of two that holds the widest row, from 4 to 64
-    unsigned widest = 1;
-    for (int l = 0; l < L; ++l) widest = mp.cu[l] > widest ? mp.cu[l] : widest;
-    int group_shift = 2;
-    while (group_shift < 6 && (1u << group_shift) < widest) ++group_shift;
-    const bool g2 = gamma == 2.f;
-#define HTD_ATSS_LAUNCH(V, G)                                                                                                       \
-    hipLaunchKernelGGL((atss_loss_kernel<V, G>), dim3(ATSS_BLOCKS), dim3(256), 0, (hipStream_t)stream, mp, lv, L, C, anchors, gts,  \
-                       gt_labels, K, assigned, ctr_targets, norm, cd, box_kind, eps, gamma, alpha, cls_weight, box_weight,          \
-                       ctr_weight, group_shift, partial)
-    if (vec) { if (g2) HTD_ATSS_LAUNCH(4, true); else HTD_ATSS_LAUNCH(4, false); }
-    else { if (g2) HTD_ATSS_LAUNCH(1, true); else HTD_ATSS_LAUNCH(1, false); }
-#undef HTD_ATSS_LAUNCH
+    HTD_POINT_LAUNCH(atss_loss_kernel, f.vec, gamma == 2.f, stream, mp, lv, L, C, anchors, gts, gt_labels, K, assigned, ctr_targets,
+                     norm, cd, box_kind, eps, gamma, alpha, cls_weight, box_weight, ctr_weight, f.group_shift, partial);
     return htd::check_launch("atss_loss");
 }

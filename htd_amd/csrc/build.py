@@ -33,10 +33,14 @@ EXTRA = {'nms.hip': ['-ffp-contract=off'], 'box_ops.hip': ['-ffp-contract=off'],
 #   atss.hip         ATSSAssigner over a batch with the centerness targets and averaging factors, and ATSSHead's loss
 #                    (core/bbox/assigners/atss_assigner.py:33-178, dense_heads/atss_head.py:145-313)
 #   gfl.hip          GFLHead's quality pass, loss (QFL, weighted IoU / GIoU, DFL) and inference decode
-#                    (dense_heads/gfl_head.py:209-369,420-428, losses/gfocal_loss.py:8-74); level table of atss.hip (anchor_levels.h)
+#                    (dense_heads/gfl_head.py:209-369,420-428, losses/gfocal_loss.py:8-74)
 #   vfnet.hip        VFNetHead's star offsets with their backward, quality pass and loss (varifocal loss, two IoU-weighted
 #                    IoU / GIoU losses) (dense_heads/vfnet_head.py:246-314,317-463, losses/varifocal_loss.py:8-53)
-# The six share focal_elem.h (the element arithmetic) and loss_units.h (level search, VEC-wide units, matrix units).
+# The six share focal_elem.h (the element arithmetic) and loss_units.h (level search, VEC-wide units, matrix units).  The last
+# four, the heads with one prediction per location, share point_maps.h (their map table and its checker, the loss grid and the
+# float4 / lane-group decision, the decoding of a pixel row, the classification sweep of their loss kernels), point_scale.h
+# (the kernel behind htd_fcos_grad_scale and htd_vfnet_grad_scale) and, but for FCOS, anchor_levels.h (the level table of
+# htd_atss_targets' anchors, the box load, the reference's fp32 IoU): each of the four files holds only what its head alone does.
 def sources():
     return sorted(f for f in os.listdir(HERE) if f.endswith('.hip') or f.endswith('.cpp'))
 

@@ -10,14 +10,13 @@
 // All three kernels are small and launch- or memory-bound: plain grids, fixed-order partial sums, no float atomics, every element
 // of every output stored exactly once (padding channels and non-positive points as zeros).
 #include "common.h"
-#include "focal_elem.h"
 #include "iou_family.h"
-#include "loss_units.h"
+#include "point_maps.h"
+#include "point_scale.h"
 
 namespace {
 
-constexpr int FCOS_BLOCKS = 2048;           // 256 CUs x 8 blocks: the cap of a memory-bound grid; the rest is grid-stride
-constexpr int FCOS_MAX_LEVELS = 8;
+constexpr int FCOS_MAX_LEVELS = POINT_MAX_LEVELS;
 constexpr int GT_CHUNK = 256;               // gts staged through LDS per pass of the assignment
 constexpr float FCOS_INF = 1e8f;            // fcos_head.py:11
 
@@ -29,15 +28,7 @@ struct FcosPoints {                          // the pyramid as the point generat
     float sr[FCOS_MAX_LEVELS];              // stride * center_sample_radius, rounded to fp32 as the reference's tensor holds it
 };
 
-struct FcosMaps {
-    const float *cls[FCOS_MAX_LEVELS], *reg[FCOS_MAX_LEVELS], *ctr[FCOS_MAX_LEVELS];
-    float *gcls[FCOS_MAX_LEVELS], *greg[FCOS_MAX_LEVELS], *gctr[FCOS_MAX_LEVELS];
-    unsigned pix[FCOS_MAX_LEVELS];
-    unsigned cu[FCOS_MAX_LEVELS];           // units per pixel of the classification map (channel stride / VEC)
-    unsigned rs[FCOS_MAX_LEVELS];           // channel stride of the regression map in floats (>= 4)
-    unsigned ts[FCOS_MAX_LEVELS];           // channel stride of the centerness map in floats (>= 1)
-    unsigned rrow[FCOS_MAX_LEVELS + 1];     // prefix sums of B * pix: the pixel rows of all levels
-};
+enum { CLS = 0, REG = 1, CTR = 2 };       // slots of PointMaps: (B, C, h, w), (B, 4, h, w), (B, 1, h, w)
 
 __device__ __forceinline__ void point_xy(const FcosPoints &pt, int l, unsigned p, float &x, float &y)
 {
@@ -168,122 +159,55 @@ __global__ __launch_bounds__(64) void fcos_targets_finish_kernel(const int *__re
 }
 
 // ---- loss --------------------------------------------------------------------------------------------------------------------
-// Classification maps: a lane group per pixel row [cu units] in the manner of retina_loss_kernel (one "anchor" per pixel).  Then
-// one thread per point for the four distances and the centerness logit: a sixteenth of the data.  partial [FCOS_BLOCKS][2] =
-// {sum focal, sum ctr_target * box loss}, partial + 2 * FCOS_BLOCKS: [FCOS_BLOCKS][2] = {sum centerness BCE, 0}, unscaled.
+// Classification maps: the sweep of point_maps.h with plain focal elements (one "anchor" per pixel).  Then one thread per point
+// for the four distances and the centerness logit: a sixteenth of the data.  partial [POINT_BLOCKS][2] = {sum focal, sum
+// ctr_target * box loss}, partial + 2 * POINT_BLOCKS: [POINT_BLOCKS][2] = {sum centerness BCE, 0}, unscaled.
 template <int VEC, bool G2>
-__global__ __launch_bounds__(256) void fcos_loss_kernel(FcosMaps mp, FcosPoints pt, int L, int C, const int64_t *__restrict__ gt_labels,
+__global__ __launch_bounds__(256) void fcos_loss_kernel(PointMaps mp, FcosPoints pt, int L, int C, const int64_t *__restrict__ gt_labels,
                                                         int K, const int *__restrict__ assigned,
                                                         const float *__restrict__ bbox_targets, const float *__restrict__ ctr_targets,
                                                         const float *__restrict__ norm, int box_kind, double eps, float gamma,
                                                         float alpha, float cls_weight, float box_weight, float ctr_weight,
                                                         int group_shift, float *__restrict__ partial)
 {
-    const unsigned P = pt.poff[L];
-    const float cs = cls_weight / norm[0];
     const unsigned n_rows = mp.rrow[L];
-    float s_cls = 0.f;
-    // 2^group_shift lanes sweep one pixel row, so a wavefront takes 64 >> group_shift rows at a time: 80 classes are 20 float4s, and
-    // a whole wavefront per row would leave two thirds of its lanes idle
-    const unsigned lane = threadIdx.x & 63u;
-    const unsigned gl = 1u << group_shift, sub = lane & (gl - 1u), rpw = 64u >> group_shift;
-    const unsigned wave = blockIdx.x * 4u + (threadIdx.x >> 6);
-    for (unsigned rw0 = wave * rpw; rw0 < n_rows; rw0 += gridDim.x * 4u * rpw) {
-        const unsigned rw = rw0 + (lane >> group_shift);
-        if (rw >= n_rows) continue;
-        const int l = level_of(mp.rrow, L, rw);
-        const unsigned row = rw - mp.rrow[l];                                       // b * pix + p
-        const unsigned b = row / mp.pix[l], p = row - b * mp.pix[l];
-        const unsigned cu = mp.cu[l];
-        const int as = assigned[(int64_t)b * P + pt.poff[l] + p];
-        const int64_t lab = as > 0 ? gt_labels[(int64_t)b * K + (as - 1)] : (int64_t)C;
-        const float *x_row = mp.cls[l] + (int64_t)row * cu * VEC;
-        float *g_row = mp.gcls[l] + (int64_t)row * cu * VEC;
-        for (unsigned j = sub; j < cu; j += gl) {
-            const unsigned c0 = j * VEC;
-            float go[VEC];
-#pragma unroll
-            for (int k = 0; k < VEC; ++k) go[k] = 0.f;
-            if (c0 < (unsigned)C) {                                                 // (VEC = 4: C % 4 == 0, whole units)
-                float xv[VEC];
-                load_unit<VEC>(x_row, j, xv);
-#pragma unroll
-                for (int k = 0; k < VEC; ++k) {
-                    float g;
-                    s_cls += focal_elem<G2>(xv[k], lab == (int64_t)(c0 + k), gamma, alpha, g);
-                    go[k] = g * cs;
-                }
-            }
-            store_unit<VEC>(g_row, j, go);
-        }
-    }
+    const float s_cls = cls_sweep<VEC>(mp, pt.poff, L, C, assigned, gt_labels, K, nullptr, cls_weight / norm[0], group_shift,
+                                       [=](float x, bool own, float, float &g) { return focal_elem<G2>(x, own, gamma, alpha, g); });
     // the points: decode prediction and target against the point (distance2bbox), the box loss weighted by the centerness target
     // over norm[2], the centerness BCE-with-logits over norm[1]; both in fp64 on the few positives
     double s_box = 0., s_ctr = 0.;
     for (unsigned rw = blockIdx.x * 256u + threadIdx.x; rw < n_rows; rw += gridDim.x * 256u) {
-        const int l = level_of(mp.rrow, L, rw);
-        const unsigned row = rw - mp.rrow[l];
-        const unsigned b = row / mp.pix[l], p = row - b * mp.pix[l];
-        const unsigned rs = mp.rs[l], ts = mp.ts[l];
-        const int64_t o = (int64_t)b * P + pt.poff[l] + p;
+        const PointRow r = point_row(mp, pt.poff, L, rw);
         float gr[4] = {0.f, 0.f, 0.f, 0.f}, gc = 0.f;
-        if (assigned[o] > 0) {
+        if (assigned[r.o] > 0) {
             float x, y;
-            point_xy(pt, l, p, x, y);
-            const float *d = mp.reg[l] + (int64_t)row * rs;
-            const float4 t = *reinterpret_cast<const float4 *>(bbox_targets + o * 4);
-            const double w = (double)ctr_targets[o];
+            point_xy(pt, r.l, r.p, x, y);
+            const float *d = slot_row(mp, REG, r);
+            const float4 t = *reinterpret_cast<const float4 *>(bbox_targets + r.o * 4);
+            const double w = (double)ctr_targets[r.o];
             const Box pb = {(double)x - d[0], (double)y - d[1], (double)x + d[2], (double)y + d[3]};
             const Box tb = {(double)x - t.x, (double)y - t.y, (double)x + t.z, (double)y + t.w};
             Box G;
             s_box += w * iou_family_loss(box_kind, pb, tb, eps, G);
             const double bs = w * (double)box_weight / (double)norm[2];
             gr[0] = (float)(-G.x1 * bs); gr[1] = (float)(-G.y1 * bs); gr[2] = (float)(G.x2 * bs); gr[3] = (float)(G.y2 * bs);
-            const double z = (double)mp.ctr[l][(int64_t)row * ts];
-            const double e = exp(-fabs(z));
-            s_ctr += fmax(z, 0.) - z * w + log1p(e);
-            const double sig = z >= 0. ? 1. / (1. + e) : e / (1. + e);
+            const double z = (double)slot_row(mp, CTR, r)[0];
+            double l1p, sig;
+            sigmoid_log1p(z, l1p, sig);
+            s_ctr += fmax(z, 0.) - z * w + l1p;
             gc = (float)((sig - w) * (double)ctr_weight / (double)norm[1]);
         }
-        float *g_reg = mp.greg[l] + (int64_t)row * rs;
-        for (unsigned k = 0; k < rs; ++k) g_reg[k] = k < 4u ? gr[k] : 0.f;
-        float *g_ctr = mp.gctr[l] + (int64_t)row * ts;
-        for (unsigned k = 0; k < ts; ++k) g_ctr[k] = k == 0u ? gc : 0.f;
+        store_padded(slot_grad_row(mp, REG, r), mp.cs[REG][r.l], gr, 4u);
+        store_padded(slot_grad_row(mp, CTR, r), mp.cs[CTR][r.l], &gc, 1u);
     }
     block_store_partial2(s_cls, (float)s_box, partial);
     __syncthreads();                        // the reduction's LDS is read before the second pair overwrites it
-    block_store_partial2((float)s_ctr, 0.f, partial + 2 * FCOS_BLOCKS);
-}
-
-// gradient maps *= the incoming gradients (device scalars); a map kind whose factor is exactly 1 is left alone, decided on the device
-__global__ __launch_bounds__(256) void fcos_scale_kernel(FcosMaps mp, int L, int cls_width, const float *__restrict__ g_cls,
-                                                         const float *__restrict__ g_box, const float *__restrict__ g_ctr)
-{
-    const float gc = *g_cls, gb = *g_box, gt = *g_ctr;
-    const unsigned n_rows = mp.rrow[L];
-    const unsigned lane = threadIdx.x & 63u;
-    const unsigned wave = __builtin_amdgcn_readfirstlane(blockIdx.x * 4u + (threadIdx.x >> 6));
-    if (gc != 1.f) {
-        for (unsigned rw = wave; rw < n_rows; rw += gridDim.x * 4u) {
-            const int l = level_of(mp.rrow, L, rw);
-            float *g_row = mp.gcls[l] + (int64_t)(rw - mp.rrow[l]) * mp.cu[l];      // cu: channel stride in floats here
-            for (unsigned j = lane; j < (unsigned)cls_width; j += 64u) g_row[j] *= gc;
-        }
-    }
-    if (gb != 1.f || gt != 1.f) {
-        for (unsigned rw = blockIdx.x * 256u + threadIdx.x; rw < n_rows; rw += gridDim.x * 256u) {
-            const int l = level_of(mp.rrow, L, rw);
-            const unsigned row = rw - mp.rrow[l];
-            float *g_reg = mp.greg[l] + (int64_t)row * mp.rs[l];
-            for (int k = 0; k < 4; ++k) g_reg[k] *= gb;
-            mp.gctr[l][(int64_t)row * mp.ts[l]] *= gt;
-        }
-    }
+    block_store_partial2((float)s_ctr, 0.f, partial + 2 * POINT_BLOCKS);
 }
 
 // key [B][P] = max_c sigmoid(cls) * sigmoid(centerness) = sigmoid(max_c cls) * sigmoid(centerness) (both factors rounded to fp32
 // as the reference's tensors are; the product with a positive factor keeps the order of the maximum): 16 lanes per point
-__global__ __launch_bounds__(256) void fcos_keys_kernel(FcosMaps mp, FcosPoints pt, int L, int B, int C, float *__restrict__ keys)
+__global__ __launch_bounds__(256) void fcos_keys_kernel(PointMaps mp, FcosPoints pt, int L, int B, int C, float *__restrict__ keys)
 {
     const int sub = threadIdx.x & 15;
     const unsigned P = pt.poff[L];
@@ -296,8 +220,8 @@ __global__ __launch_bounds__(256) void fcos_keys_kernel(FcosMaps mp, FcosPoints 
             const unsigned b = (unsigned)(i / P), pi = (unsigned)(i - (int64_t)b * P);
             const int l = level_of(pt.poff, L, pi);
             const int64_t row = (int64_t)b * mp.pix[l] + (pi - pt.poff[l]);
-            const float *x = mp.cls[l] + row * mp.cu[l];                           // cu: channel stride in floats here
-            if ((C & 3) == 0 && (mp.cu[l] & 3) == 0) {
+            const float *x = mp.map[CLS][l] + row * mp.cs[CLS][l];
+            if ((C & 3) == 0 && (mp.cs[CLS][l] & 3) == 0) {
                 for (int c = sub * 4; c < C; c += 64) {
                     const float4 v = *reinterpret_cast<const float4 *>(x + c);
                     m = fmaxf(fmaxf(m, fmaxf(v.x, v.y)), fmaxf(v.z, v.w));
@@ -305,7 +229,7 @@ __global__ __launch_bounds__(256) void fcos_keys_kernel(FcosMaps mp, FcosPoints 
             } else {
                 for (int c = sub; c < C; c += 16) m = fmaxf(m, x[c]);
             }
-            ct = mp.ctr[l][row * mp.ts[l]];
+            ct = mp.map[CTR][l][row * mp.cs[CTR][l]];
         }
 #pragma unroll
         for (int o = 8; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
@@ -337,57 +261,11 @@ int fill_points(FcosPoints &pt, const char *what, const int64_t *hw, const int64
     return HTD_OK;
 }
 
-// vec: units of the classification map (4: float4 units, 1: floats)
-int fill_maps(FcosMaps &mp, const char *what, const FcosPoints &pt, const float *const *cls, const int64_t *cls_stride,
-              const float *const *reg, const int64_t *reg_stride, const float *const *ctr, const int64_t *ctr_stride,
-              float *const *gcls, float *const *greg, float *const *gctr, int L, int B, int C, int vec)
-{
-    HTD_REQUIRE(B > 0 && C > 0, "%s: bad sizes", what);
-    HTD_REQUIRE(cls && cls_stride, "%s: null table", what);
-    int64_t rrow = 0, elems = 0;
-    for (int l = 0; l < L; ++l) {
-        const int64_t pix = (int64_t)pt.poff[l + 1] - pt.poff[l];
-        HTD_REQUIRE(cls_stride[l] >= C && cls_stride[l] % vec == 0, "%s: bad classification stride of level %d", what, l);
-        const bool f4 = vec == 4 || ((C & 3) == 0 && (cls_stride[l] & 3) == 0);
-        HTD_REQUIRE(cls[l] && (!f4 || ((uintptr_t)cls[l] & 15) == 0), "%s: map of level %d is null or not 16-byte aligned", what, l);
-        HTD_REQUIRE(!gcls || (gcls[l] && (vec != 4 || ((uintptr_t)gcls[l] & 15) == 0)),
-                    "%s: gradient map of level %d is null or not 16-byte aligned", what, l);
-        mp.cls[l] = cls[l];
-        mp.gcls[l] = gcls ? gcls[l] : nullptr;
-        mp.pix[l] = (unsigned)pix;
-        mp.cu[l] = (unsigned)(cls_stride[l] / vec);
-        mp.rrow[l] = (unsigned)rrow;
-        rrow += (int64_t)B * pix;
-        elems += (int64_t)B * pix * cls_stride[l];
-        if (reg) {
-            HTD_REQUIRE(reg_stride && reg_stride[l] >= 4 && reg[l], "%s: bad regression map of level %d", what, l);
-            HTD_REQUIRE(!greg || greg[l], "%s: null regression gradient map of level %d", what, l);
-            mp.reg[l] = reg[l];
-            mp.greg[l] = greg ? greg[l] : nullptr;
-            mp.rs[l] = (unsigned)reg_stride[l];
-            elems += (int64_t)B * pix * reg_stride[l];
-        }
-        if (ctr) {
-            HTD_REQUIRE(ctr_stride && ctr_stride[l] >= 1 && ctr[l], "%s: bad centerness map of level %d", what, l);
-            HTD_REQUIRE(!gctr || gctr[l], "%s: null centerness gradient map of level %d", what, l);
-            mp.ctr[l] = ctr[l];
-            mp.gctr[l] = gctr ? gctr[l] : nullptr;
-            mp.ts[l] = (unsigned)ctr_stride[l];
-            elems += (int64_t)B * pix * ctr_stride[l];
-        }
-    }
-    for (int l = L; l <= FCOS_MAX_LEVELS; ++l) mp.rrow[l] = (unsigned)rrow;
-    HTD_REQUIRE(rrow < ((int64_t)1 << 31) && elems < ((int64_t)1 << 40), "%s: more than 2^31 pixel rows", what);
-    return HTD_OK;
-}
-
 }  // namespace
-
-static int64_t fcos_blocks(int64_t P) { return (P + 255) / 256; }
 
 extern "C" int64_t htd_fcos_targets_workspace_bytes(int B, int64_t P)
 {
-    return (int64_t)B * fcos_blocks(P) * 16;      // one double and one int (padded to 8 bytes) per block
+    return (int64_t)B * blocks_of(P) * 16;      // one double and one int (padded to 8 bytes) per block
 }
 
 extern "C" int htd_fcos_targets(const int64_t *hw, const int64_t *strides, const float *ranges, int L, const float *gts,
@@ -405,7 +283,7 @@ extern "C" int htd_fcos_targets(const int64_t *hw, const int64_t *strides, const
     const int rc = fill_points(pt, "fcos_targets", hw, strides, ranges, L, radius, &P);
     if (rc != HTD_OK) return rc;
     HTD_REQUIRE((int64_t)B * P < ((int64_t)1 << 31), "fcos_targets: more than 2^31 points in the batch");
-    const int nblk = (int)fcos_blocks(P);
+    const int nblk = (int)blocks_of(P);
     double *part_c = (double *)workspace;
     int *part_n = (int *)(part_c + (int64_t)B * nblk);
     hipLaunchKernelGGL(fcos_targets_kernel, dim3(nblk, B), dim3(256), 0, (hipStream_t)stream, pt, L, gts, gt_valid, K,
@@ -415,7 +293,7 @@ extern "C" int htd_fcos_targets(const int64_t *hw, const int64_t *strides, const
     return htd::check_launch("fcos_targets");
 }
 
-extern "C" int htd_fcos_loss_partial_rows(void) { return 2 * FCOS_BLOCKS; }
+extern "C" int htd_fcos_loss_partial_rows(void) { return 2 * POINT_BLOCKS; }
 
 extern "C" int htd_fcos_loss(const float *const *cls, const int64_t *cls_stride, const float *const *reg, const int64_t *reg_stride,
                              const float *const *ctr, const int64_t *ctr_stride, const int64_t *hw, const int64_t *strides, int L,
@@ -424,7 +302,6 @@ extern "C" int htd_fcos_loss(const float *const *cls, const int64_t *cls_stride,
                              float cls_weight, float box_weight, float ctr_weight, float *partial, float *const *grad_cls,
                              float *const *grad_reg, float *const *grad_ctr, void *stream)
 {
-    HTD_REQUIRE(reg && ctr && grad_cls && grad_reg && grad_ctr, "fcos_loss: null table");
     HTD_REQUIRE(gt_labels && assigned && bbox_targets && ctr_targets && norm && partial, "fcos_loss: null pointer");
     HTD_REQUIRE(K > 0 && gamma >= 0.f && (box_kind == BOX_IOU || box_kind == BOX_GIOU), "fcos_loss: bad parameters");
     HTD_REQUIRE(((uintptr_t)bbox_targets & 15) == 0, "fcos_loss: bbox_targets must be 16-byte aligned");
@@ -432,26 +309,14 @@ extern "C" int htd_fcos_loss(const float *const *cls, const int64_t *cls_stride,
     int64_t P = 0;
     int rc = fill_points(pt, "fcos_loss", hw, strides, nullptr, L, 0., &P);
     if (rc != HTD_OK) return rc;
-    bool vec = (C & 3) == 0;
-    for (int l = 0; l < L && vec; ++l) vec = cls_stride && (cls_stride[l] & 3) == 0;
-    FcosMaps mp = {};
-    rc = fill_maps(mp, "fcos_loss", pt, cls, cls_stride, reg, reg_stride, ctr, ctr_stride, grad_cls, grad_reg, grad_ctr, L, B, C,
-                   vec ? 4 : 1);
+    const SweepForm f = sweep_form(C, cls_stride, L);
+    const PointSlot slots[POINT_SLOTS] = {{cls, grad_cls, cls_stride, C, true, true}, {reg, grad_reg, reg_stride, 4, true, true},
+                                          {ctr, grad_ctr, ctr_stride, 1, true, true}};
+    PointMaps mp = {};
+    rc = fill_point_maps(mp, "fcos_loss", pt.poff, L, B, slots, f.vec);
     if (rc != HTD_OK) return rc;
-    HTD_REQUIRE((int64_t)B * P < ((int64_t)1 << 31), "fcos_loss: more than 2^31 points in the batch");
-    // lanes per pixel row of the classification sweep: the smallest power of two that holds the widest row, from 4 to 64
-    unsigned widest = 1;
-    for (int l = 0; l < L; ++l) widest = mp.cu[l] > widest ? mp.cu[l] : widest;
-    int group_shift = 2;
-    while (group_shift < 6 && (1u << group_shift) < widest) ++group_shift;
-    const bool g2 = gamma == 2.f;
-#define HTD_FCOS_LAUNCH(V, G)                                                                                                       \
-    hipLaunchKernelGGL((fcos_loss_kernel<V, G>), dim3(FCOS_BLOCKS), dim3(256), 0, (hipStream_t)stream, mp, pt, L, C, gt_labels, K, \
-                       assigned, bbox_targets, ctr_targets, norm, box_kind, eps, gamma, alpha, cls_weight, box_weight, ctr_weight,  \
-                       group_shift, partial)
-    if (vec) { if (g2) HTD_FCOS_LAUNCH(4, true); else HTD_FCOS_LAUNCH(4, false); }
-    else { if (g2) HTD_FCOS_LAUNCH(1, true); else HTD_FCOS_LAUNCH(1, false); }
-#undef HTD_FCOS_LAUNCH
+    HTD_POINT_LAUNCH(fcos_loss_kernel, f.vec, gamma == 2.f, stream, mp, pt, L, C, gt_labels, K, assigned, bbox_targets, ctr_targets,
+                     norm, box_kind, eps, gamma, alpha, cls_weight, box_weight, ctr_weight, f.group_shift, partial);
     return htd::check_launch("fcos_loss");
 }
 
@@ -460,32 +325,28 @@ extern "C" int htd_fcos_grad_scale(float *const *grad_cls, const int64_t *cls_st
                                    const int64_t *strides, int L, int B, int C, const float *g_cls, const float *g_box,
                                    const float *g_ctr, void *stream)
 {
-    HTD_REQUIRE(grad_cls && grad_reg && grad_ctr && g_cls && g_box && g_ctr, "fcos_grad_scale: null pointer");
     FcosPoints pt = {};
     int64_t P = 0;
-    int rc = fill_points(pt, "fcos_grad_scale", hw, strides, nullptr, L, 0., &P);
+    const int rc = fill_points(pt, "fcos_grad_scale", hw, strides, nullptr, L, 0., &P);
     if (rc != HTD_OK) return rc;
-    FcosMaps mp = {};
-    rc = fill_maps(mp, "fcos_grad_scale", pt, grad_cls, cls_stride, grad_reg, reg_stride, grad_ctr, ctr_stride, grad_cls, grad_reg,
-                   grad_ctr, L, B, C, 1);
-    if (rc != HTD_OK) return rc;
-    hipLaunchKernelGGL(fcos_scale_kernel, dim3(FCOS_BLOCKS), dim3(256), 0, (hipStream_t)stream, mp, L, C, g_cls, g_box, g_ctr);
-    return htd::check_launch("fcos_grad_scale");
+    return point_grad_scale<4, 1>("fcos_grad_scale", pt.poff, L, B, grad_cls, cls_stride, C, grad_reg, reg_stride, grad_ctr, ctr_stride,
+                                  g_cls, g_box, g_ctr, stream);
 }
 
 extern "C" int htd_fcos_keys(const float *const *cls, const int64_t *cls_stride, const float *const *ctr, const int64_t *ctr_stride,
                              const int64_t *hw, const int64_t *strides, int L, int B, int C, float *keys, void *stream)
 {
-    HTD_REQUIRE(keys && ctr, "fcos_keys: null pointer");
+    HTD_REQUIRE(keys, "fcos_keys: null pointer");
     FcosPoints pt = {};
     int64_t P = 0;
     int rc = fill_points(pt, "fcos_keys", hw, strides, nullptr, L, 0., &P);
     if (rc != HTD_OK) return rc;
-    FcosMaps mp = {};
-    rc = fill_maps(mp, "fcos_keys", pt, cls, cls_stride, nullptr, nullptr, ctr, ctr_stride, nullptr, nullptr, nullptr, L, B, C, 1);
+    const PointSlot slots[POINT_SLOTS] = {{cls, nullptr, cls_stride, C, true, false}, {}, {ctr, nullptr, ctr_stride, 1, true, false}};
+    PointMaps mp = {};
+    rc = fill_point_maps(mp, "fcos_keys", pt.poff, L, B, slots, 1);
     if (rc != HTD_OK) return rc;
     const int64_t groups = htd::ceil_div((int64_t)B * P, 16);
-    hipLaunchKernelGGL(fcos_keys_kernel, dim3((unsigned)(groups < FCOS_BLOCKS ? groups : FCOS_BLOCKS)), dim3(256), 0,
+    hipLaunchKernelGGL(fcos_keys_kernel, dim3((unsigned)(groups < POINT_BLOCKS ? groups : POINT_BLOCKS)), dim3(256), 0,
                        (hipStream_t)stream, mp, pt, L, B, C, keys);
     return htd::check_launch("fcos_keys");
 }

@@ -1,6 +1,7 @@
-// The sigmoid focal loss of one element with its derivative, and the two-sum block reduction of the head-loss kernels: shared
-// by focal_loss.hip (htd_sigmoid_focal_loss, htd_retina_loss) and fcos.hip (htd_fcos_loss), so the dense heads take the same
-// arithmetic.  See focal_loss.hip for the formulation; how the kernels address their maps is in loss_units.h.
+// The sigmoid focal loss of one element with its derivative, the fp64 sigmoid / log1p of one logit and the two-sum block
+// reduction of the head-loss kernels: shared by focal_loss.hip (htd_sigmoid_focal_loss, htd_retina_loss) and, through
+// point_maps.h, the heads with one prediction per location (fcos.hip, atss.hip, gfl.hip, vfnet.hip), so the dense heads take the
+// same arithmetic.  See focal_loss.hip for the formulation; how the kernels address their maps is in loss_units.h.
 #pragma once
 #include "common.h"
 
@@ -33,6 +34,15 @@ __device__ __forceinline__ float focal_elem(float x, bool t, float gamma, float 
     const float gz = at * sg * (s + gamma * sp * s1);
     g = t ? -gz : gz;
     return at * sg * sp;
+}
+
+// fp64, for the few elements with a soft target: l1p = log1p(exp(-|z|)) and s = sigmoid(z).  softplus(z) = fmax(z, 0.) + l1p;
+// the callers add the terms of their BCE-with-logits in their own order, which their results are pinned to bit for bit.
+__device__ __forceinline__ void sigmoid_log1p(double z, double &l1p, double &s)
+{
+    const double e = exp(-fabs(z));
+    l1p = log1p(e);
+    s = z >= 0. ? 1. / (1. + e) : e / (1. + e);
 }
 
 __device__ __forceinline__ void block_store_partial2(float s0, float s1, float *__restrict__ partial)

@@ -16,24 +16,15 @@
 // No atomics: every sum has a fixed order and every element of every output is stored exactly once with plain vector stores.
 #include "common.h"
 #include "anchor_levels.h"
-#include "focal_elem.h"
 #include "iou_family.h"
-#include "loss_units.h"
 
 namespace {
 
 constexpr int GFL_MAX_REG_MAX = 31;         // at most 32 bins per side
 
-struct GflMaps {
-    const float *cls[ATSS_MAX_LEVELS], *reg[ATSS_MAX_LEVELS];
-    float *gcls[ATSS_MAX_LEVELS], *greg[ATSS_MAX_LEVELS];
-    unsigned pix[ATSS_MAX_LEVELS];
-    unsigned cs[ATSS_MAX_LEVELS];           // channel stride of the classification map in floats (>= C)
-    unsigned cu[ATSS_MAX_LEVELS];           // the same in units of VEC floats
-    unsigned rs[ATSS_MAX_LEVELS];           // channel stride of the regression map in floats (>= 4 * bins)
-    unsigned rrow[ATSS_MAX_LEVELS + 1];     // prefix sums of B * pix: the pixel rows of all levels
-    float stride[ATSS_MAX_LEVELS];
-};
+enum { CLS = 0, REG = 1 };                // slots of PointMaps: (B, C, h, w), (B, 4 * bins, h, w); the third is not used
+
+struct GflStrides { float v[ATSS_MAX_LEVELS]; };        // the pyramid's strides, as the reference's fp32 tensors hold them
 
 // softmax-integral sum_j j * softmax(x)_j of one side's `nb` logits, fp64; mx / den: the maximum and the sum of exp(x - mx)
 __device__ __forceinline__ double integral_of(const float *__restrict__ x, int nb, double &mx, double &den)
@@ -106,7 +97,7 @@ __device__ __forceinline__ void positive_row(const float *__restrict__ x, float 
 // grid (ceil(A / 256), B), one thread per anchor: weight = max_c sigmoid(cls) (the fp32 rounding of the fp64 sigmoid of the
 // largest logit) and score = aligned fp32 IoU (eps 1e-6) of the integral-decoded box with gt / stride on positives, 0 elsewhere;
 // the block's weight sum (fp64) goes to part
-__global__ __launch_bounds__(256) void gfl_quality_kernel(GflMaps mp, AtssLevels lv, int L, int C, int nb,
+__global__ __launch_bounds__(256) void gfl_quality_kernel(PointMaps mp, AtssLevels lv, GflStrides st, int L, int C, int nb,
                                                           const float *__restrict__ anchors, const float *__restrict__ gts, int K,
                                                           const int *__restrict__ assigned, float *__restrict__ weight,
                                                           float *__restrict__ score, double *__restrict__ part)
@@ -123,18 +114,18 @@ __global__ __launch_bounds__(256) void gfl_quality_kernel(GflMaps mp, AtssLevels
         if (as > 0 && as <= K) {
             const unsigned l = level_of(lv.aoff, L, i);
             const int64_t row = (int64_t)b * mp.pix[l] + (i - lv.aoff[l]);
-            const float *x = mp.cls[l] + row * mp.cs[l];
+            const float *x = mp.map[CLS][l] + row * mp.cs[CLS][l];
             float m = x[0];
             for (int c = 1; c < C; ++c) m = fmaxf(m, x[c]);
             w = (float)(1. / (1. + exp(-(double)m)));
-            const float *r = mp.reg[l] + row * mp.rs[l];
+            const float *r = mp.map[REG][l] + row * mp.cs[REG][l];
             float d[4];
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 double mx, den;
                 d[k] = (float)integral_of(r + k * nb, nb, mx, den);
             }
-            const GflGeometry q = geometry_of(load4(anchors, i), load4(gts, (int64_t)b * K + (as - 1)), mp.stride[l]);
+            const GflGeometry q = geometry_of(load4(anchors, i), load4(gts, (int64_t)b * K + (as - 1)), st.v[l]);
             s = iou_ref(make_float4(q.cx - d[0], q.cy - d[1], q.cx + d[2], q.cy + d[3]), q.t);
         }
         weight[o] = w;
@@ -164,10 +155,9 @@ __global__ __launch_bounds__(64) void gfl_quality_finish_kernel(const double *__
 __device__ __forceinline__ float qfl_positive(float xf, float yf, float beta, float &g)
 {
     const double x = (double)xf, y = (double)yf;
-    const double ez = exp(-fabs(x));
-    const double sp = fmax(x, 0.) + log1p(ez);
-    const double s = x >= 0. ? 1. / (1. + ez) : ez / (1. + ez);
-    const double bce = sp - x * y;
+    double l1p, s;
+    sigmoid_log1p(x, l1p, s);
+    const double bce = fmax(x, 0.) + l1p - x * y;
     const double d = y - s, ad = fabs(d);
     const double m = beta == 2.f ? d * d : pow(ad, (double)beta);
     const double dm = ad > 0. ? (double)beta * m / ad * (d > 0. ? 1. : -1.) : 0.;       // d m / d d; d d / d x = -s (1 - s)
@@ -175,13 +165,14 @@ __device__ __forceinline__ float qfl_positive(float xf, float yf, float beta, fl
     return (float)(bce * m);
 }
 
-// Classification maps: a lane group per pixel row [cu units], one anchor per pixel, label weight 1; the same group zero-fills the
-// regression gradient row of a non-positive anchor (0 * (1 / wsum): NaN when the batch has no positive, as the reference's
+// Classification maps: the sweep of point_maps.h, one anchor per pixel, label weight 1: QFL against the score on a positive's own
+// class, focal_elem with alpha = 0 (softplus(x) * sigmoid(x)^beta) elsewhere; the lane group of a row zero-fills the regression
+// gradient row of a non-positive anchor (0 * (1 / wsum): NaN when the batch has no positive, as the reference's
 // bbox_pred.sum() * 0 over avg_factor 0).  Then one thread per anchor: a positive's box and DFL terms and its gradient row.
-// partial [ATSS_BLOCKS][2] = {sum QFL, sum weight * box loss}, partial + 2 * ATSS_BLOCKS: [ATSS_BLOCKS][2] = {sum weight * DFL
+// partial [POINT_BLOCKS][2] = {sum QFL, sum weight * box loss}, partial + 2 * POINT_BLOCKS: [POINT_BLOCKS][2] = {sum weight * DFL
 // of the four sides, 0}, unscaled.
 template <int VEC, bool B2>
-__global__ __launch_bounds__(256) void gfl_loss_kernel(GflMaps mp, AtssLevels lv, int L, int C, int nb,
+__global__ __launch_bounds__(256) void gfl_loss_kernel(PointMaps mp, AtssLevels lv, GflStrides st, int L, int C, int nb,
                                                        const float *__restrict__ anchors, const float *__restrict__ gts,
                                                        const int64_t *__restrict__ gt_labels, int K,
                                                        const int *__restrict__ assigned, const float *__restrict__ weight,
@@ -190,68 +181,28 @@ __global__ __launch_bounds__(256) void gfl_loss_kernel(GflMaps mp, AtssLevels lv
                                                        float cls_weight, float box_weight, float dfl_weight, int group_shift,
                                                        float *__restrict__ partial)
 {
-    const unsigned A = lv.aoff[L];
-    const float cs = cls_weight / norm[0];
     const float ws = wsum[0];
     const float zfill = 0.f * (1.f / ws);
     const unsigned n_rows = mp.rrow[L];
     const unsigned nreg = 4u * (unsigned)nb;
-    float s_cls = 0.f;
-    const unsigned lane = threadIdx.x & 63u;
-    const unsigned gl = 1u << group_shift, sub = lane & (gl - 1u), rpw = 64u >> group_shift;
-    const unsigned wave = blockIdx.x * 4u + (threadIdx.x >> 6);
-    for (unsigned rw0 = wave * rpw; rw0 < n_rows; rw0 += gridDim.x * 4u * rpw) {
-        const unsigned rw = rw0 + (lane >> group_shift);
-        if (rw >= n_rows) continue;
-        const int l = level_of(mp.rrow, L, rw);
-        const unsigned row = rw - mp.rrow[l];                                       // b * pix + p
-        const unsigned b = row / mp.pix[l], p = row - b * mp.pix[l];
-        const unsigned cu = mp.cu[l];
-        const int64_t o = (int64_t)b * A + lv.aoff[l] + p;
-        const int as = assigned[o];
-        const bool pos = as > 0 && as <= K;
-        const int64_t lab = pos ? gt_labels[(int64_t)b * K + (as - 1)] : (int64_t)C;
-        const float sc = score[o];
-        const float *x_row = mp.cls[l] + (int64_t)row * cu * VEC;
-        float *g_row = mp.gcls[l] + (int64_t)row * cu * VEC;
-        for (unsigned j = sub; j < cu; j += gl) {
-            const unsigned c0 = j * VEC;
-            float go[VEC];
-#pragma unroll
-            for (int k = 0; k < VEC; ++k) go[k] = 0.f;
-            if (c0 < (unsigned)C) {                                                 // (VEC = 4: C % 4 == 0, whole units)
-                float xv[VEC];
-                load_unit<VEC>(x_row, j, xv);
-#pragma unroll
-                for (int k = 0; k < VEC; ++k) {
-                    float g;
-                    if (lab == (int64_t)(c0 + k)) s_cls += qfl_positive(xv[k], sc, beta, g);
-                    else s_cls += focal_elem<B2>(xv[k], false, beta, 0.f, g);       // softplus(x) * sigmoid(x)^beta
-                    go[k] = g * cs;
-                }
-            }
-            store_unit<VEC>(g_row, j, go);
-        }
-        if (!pos) {
-            const unsigned rs = mp.rs[l];
-            float *g_reg = mp.greg[l] + (int64_t)row * rs;
+    const float s_cls = cls_sweep<VEC>(
+        mp, lv.aoff, L, C, assigned, gt_labels, K, score, cls_weight / norm[0], group_shift,
+        [=](float x, bool own, float sc, float &g) { return own ? qfl_positive(x, sc, beta, g) : focal_elem<B2>(x, false, beta, 0.f, g); },
+        [&](const PointRow &r, bool pos, unsigned sub, unsigned gl) {
+            if (pos) return;
+            const unsigned rs = mp.cs[REG][r.l];
+            float *g_reg = slot_grad_row(mp, REG, r);
             for (unsigned j = sub; j < rs; j += gl) g_reg[j] = j < nreg ? zfill : 0.f;
-        }
-    }
+        });
     double s_box = 0., s_dfl = 0.;
     for (unsigned rw = blockIdx.x * 256u + threadIdx.x; rw < n_rows; rw += gridDim.x * 256u) {
-        const int l = level_of(mp.rrow, L, rw);
-        const unsigned row = rw - mp.rrow[l];
-        const unsigned b = row / mp.pix[l], p = row - b * mp.pix[l];
-        const unsigned ai = lv.aoff[l] + p;
-        const int64_t o = (int64_t)b * A + ai;
-        const int as = assigned[o];
+        const PointRow r = point_row(mp, lv.aoff, L, rw);
+        const int as = assigned[r.o];
         if (as > 0 && as <= K) {
-            const unsigned rs = mp.rs[l];
-            const double w = (double)weight[o];
+            const double w = (double)weight[r.o];
             double l_box, l_dfl;
-            positive_row(mp.reg[l] + (int64_t)row * rs, mp.greg[l] + (int64_t)row * rs, rs, nb, load4(anchors, ai),
-                         load4(gts, (int64_t)b * K + (as - 1)), mp.stride[l], box_kind, eps, w * (double)box_weight / (double)ws,
+            positive_row(slot_row(mp, REG, r), slot_grad_row(mp, REG, r), mp.cs[REG][r.l], nb, load4(anchors, r.i),
+                         load4(gts, (int64_t)r.b * K + (as - 1)), st.v[r.l], box_kind, eps, w * (double)box_weight / (double)ws,
                          w * (double)dfl_weight / (4. * (double)ws), l_box, l_dfl);
             s_box += w * l_box;
             s_dfl += w * l_dfl;
@@ -259,13 +210,13 @@ __global__ __launch_bounds__(256) void gfl_loss_kernel(GflMaps mp, AtssLevels lv
     }
     block_store_partial2(s_cls, (float)s_box, partial);
     __syncthreads();                        // the reduction's LDS is read before the second pair overwrites it
-    block_store_partial2((float)s_dfl, 0.f, partial + 2 * ATSS_BLOCKS);
+    block_store_partial2((float)s_dfl, 0.f, partial + 2 * POINT_BLOCKS);
 }
 
 // The gradient maps of gfl_loss_kernel under incoming gradients (device scalars): the classification map *= g_cls; a positive's
 // regression row, where the box and the DFL gradient are summed, is written again from the logits with the two scales times
 // g_box / g_dfl (the other rows are 0, or NaN, under any factor).  A factor of exactly 1 leaves its maps alone, decided here.
-__global__ __launch_bounds__(256) void gfl_scale_kernel(GflMaps mp, AtssLevels lv, int L, int cls_width, int nb,
+__global__ __launch_bounds__(256) void gfl_scale_kernel(PointMaps mp, AtssLevels lv, GflStrides st, int L, int cls_width, int nb,
                                                         const float *__restrict__ anchors, const float *__restrict__ gts, int K,
                                                         const int *__restrict__ assigned, const float *__restrict__ weight,
                                                         const float *__restrict__ wsum, int box_kind, double eps, float box_weight,
@@ -273,32 +224,26 @@ __global__ __launch_bounds__(256) void gfl_scale_kernel(GflMaps mp, AtssLevels l
                                                         const float *__restrict__ g_box, const float *__restrict__ g_dfl)
 {
     const float gc = *g_cls, gb = *g_box, gd = *g_dfl;
-    const unsigned A = lv.aoff[L];
     const unsigned n_rows = mp.rrow[L];
     const unsigned lane = threadIdx.x & 63u;
     const unsigned wave = __builtin_amdgcn_readfirstlane(blockIdx.x * 4u + (threadIdx.x >> 6));
     if (gc != 1.f) {
         for (unsigned rw = wave; rw < n_rows; rw += gridDim.x * 4u) {
             const int l = level_of(mp.rrow, L, rw);
-            float *g_row = mp.gcls[l] + (int64_t)(rw - mp.rrow[l]) * mp.cs[l];
+            float *g_row = mp.grad[CLS][l] + (int64_t)(rw - mp.rrow[l]) * mp.cs[CLS][l];
             for (unsigned j = lane; j < (unsigned)cls_width; j += 64u) g_row[j] *= gc;
         }
     }
     if (gb != 1.f || gd != 1.f) {
         const double ws = (double)wsum[0];
         for (unsigned rw = blockIdx.x * 256u + threadIdx.x; rw < n_rows; rw += gridDim.x * 256u) {
-            const int l = level_of(mp.rrow, L, rw);
-            const unsigned row = rw - mp.rrow[l];
-            const unsigned b = row / mp.pix[l], p = row - b * mp.pix[l];
-            const unsigned ai = lv.aoff[l] + p;
-            const int64_t o = (int64_t)b * A + ai;
-            const int as = assigned[o];
+            const PointRow r = point_row(mp, lv.aoff, L, rw);
+            const int as = assigned[r.o];
             if (as > 0 && as <= K) {
-                const unsigned rs = mp.rs[l];
-                const double w = (double)weight[o];
+                const double w = (double)weight[r.o];
                 double l_box, l_dfl;
-                positive_row(mp.reg[l] + (int64_t)row * rs, mp.greg[l] + (int64_t)row * rs, rs, nb, load4(anchors, ai),
-                             load4(gts, (int64_t)b * K + (as - 1)), mp.stride[l], box_kind, eps,
+                positive_row(slot_row(mp, REG, r), slot_grad_row(mp, REG, r), mp.cs[REG][r.l], nb, load4(anchors, r.i),
+                             load4(gts, (int64_t)r.b * K + (as - 1)), st.v[r.l], box_kind, eps,
                              w * (double)box_weight / ws * (double)gb, w * (double)dfl_weight / (4. * ws) * (double)gd, l_box, l_dfl);
             }
         }
@@ -308,7 +253,7 @@ __global__ __launch_bounds__(256) void gfl_scale_kernel(GflMaps mp, AtssLevels l
 // ---- inference ---------------------------------------------------------------------------------------------------------------
 // keys [B][A] = max_c sigmoid(cls) = sigmoid(max_c cls) and dist [B][A][4] = integral(reg) * stride, fp32 as the reference's
 // tensors: 16 lanes per anchor, 4 per side
-__global__ __launch_bounds__(256) void gfl_decode_kernel(GflMaps mp, AtssLevels lv, int L, int B, int C, int nb,
+__global__ __launch_bounds__(256) void gfl_decode_kernel(PointMaps mp, AtssLevels lv, GflStrides st_, int L, int B, int C, int nb,
                                                          float *__restrict__ keys, float *__restrict__ dist)
 {
     const int sub = threadIdx.x & 15, k = sub >> 2, q = sub & 3;
@@ -324,8 +269,8 @@ __global__ __launch_bounds__(256) void gfl_decode_kernel(GflMaps mp, AtssLevels 
             const unsigned b = (unsigned)(i / A), ai = (unsigned)(i - (int64_t)b * A);
             const int l = level_of(lv.aoff, L, ai);
             const int64_t row = (int64_t)b * mp.pix[l] + (ai - lv.aoff[l]);
-            const float *x = mp.cls[l] + row * mp.cs[l];
-            if ((C & 3) == 0 && (mp.cs[l] & 3) == 0 && ((uintptr_t)mp.cls[l] & 15) == 0) {
+            const float *x = mp.map[CLS][l] + row * mp.cs[CLS][l];
+            if ((C & 3) == 0 && (mp.cs[CLS][l] & 3) == 0 && ((uintptr_t)mp.map[CLS][l] & 15) == 0) {
                 for (int c = sub * 4; c < C; c += 64) {
                     const float4 v = *reinterpret_cast<const float4 *>(x + c);
                     m = fmaxf(fmaxf(m, fmaxf(v.x, v.y)), fmaxf(v.z, v.w));
@@ -333,9 +278,9 @@ __global__ __launch_bounds__(256) void gfl_decode_kernel(GflMaps mp, AtssLevels 
             } else {
                 for (int c = sub; c < C; c += 16) m = fmaxf(m, x[c]);
             }
-            xs = mp.reg[l] + row * mp.rs[l] + k * nb;
+            xs = mp.map[REG][l] + row * mp.cs[REG][l] + k * nb;
             for (int j = q; j < nb; j += 4) mx = fmaxf(mx, xs[j]);
-            st = mp.stride[l];
+            st = st_.v[l];
         }
 #pragma unroll
         for (int o = 8; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, 64));
@@ -356,74 +301,54 @@ __global__ __launch_bounds__(256) void gfl_decode_kernel(GflMaps mp, AtssLevels 
     }
 }
 
-// vec: units of the classification map (4: float4 units, 1: floats).  gcls / greg may be null tables (no gradient maps).
-int fill_gfl_maps(GflMaps &mp, const char *what, const AtssLevels &lv, const float *const *cls, const int64_t *cls_stride,
-                  const float *const *reg, const int64_t *reg_stride, float *const *gcls, float *const *greg, const int64_t *strides,
-                  int L, int B, int C, int reg_max, int vec)
+// The prologue of every entry point: the level table, the map table of the two slots (reg_slot.channels is filled in here) and
+// the pyramid's strides.  vec: units of the classification map.
+struct GflTables { AtssLevels lv; PointMaps mp; GflStrides st; int64_t A; };
+
+int gfl_tables(GflTables &t, const char *what, const PointSlot &cls_slot, PointSlot reg_slot, const int64_t *level_sizes,
+               const int64_t *strides, int L, int B, int reg_max, int vec)
 {
-    HTD_REQUIRE(B > 0 && B < 65536 && C > 0, "%s: bad sizes", what);
     HTD_REQUIRE(reg_max >= 1 && reg_max <= GFL_MAX_REG_MAX, "%s: reg_max must be 1 to %d, got %d", what, GFL_MAX_REG_MAX, reg_max);
-    HTD_REQUIRE(cls_stride && reg && reg_stride && strides, "%s: null table", what);
-    const int nreg = 4 * (reg_max + 1);
-    int64_t rrow = 0, elems = 0;
+    int rc = fill_levels(t.lv, what, level_sizes, L, &t.A);
+    if (rc != HTD_OK) return rc;
+    reg_slot.channels = 4 * (reg_max + 1);
+    const PointSlot slots[POINT_SLOTS] = {cls_slot, reg_slot, {}};
+    rc = fill_point_maps(t.mp, what, t.lv.aoff, L, B, slots, vec);
+    if (rc != HTD_OK) return rc;
+    HTD_REQUIRE(strides, "%s: null table", what);
     for (int l = 0; l < L; ++l) {
-        const int64_t pix = (int64_t)lv.aoff[l + 1] - lv.aoff[l];
-        HTD_REQUIRE(cls_stride[l] >= C && cls_stride[l] % vec == 0 && cls_stride[l] < (1 << 20),
-                    "%s: bad classification stride of level %d", what, l);
-        HTD_REQUIRE((!cls || cls[l]) && (!gcls || gcls[l]), "%s: classification map of level %d is null", what, l);
-        HTD_REQUIRE(vec != 4 || ((((uintptr_t)(cls ? cls[l] : nullptr) | (uintptr_t)(gcls ? gcls[l] : nullptr)) & 15) == 0),
-                    "%s: classification map of level %d is not 16-byte aligned", what, l);
-        HTD_REQUIRE(reg_stride[l] >= nreg && reg_stride[l] < (1 << 20) && reg[l] && (!greg || greg[l]),
-                    "%s: bad regression map of level %d (%d channels)", what, l, nreg);
         HTD_REQUIRE(strides[l] > 0 && strides[l] < (1 << 20), "%s: bad stride of level %d", what, l);
-        mp.cls[l] = cls ? cls[l] : nullptr; mp.gcls[l] = gcls ? gcls[l] : nullptr;
-        mp.reg[l] = reg[l]; mp.greg[l] = greg ? greg[l] : nullptr;
-        mp.pix[l] = (unsigned)pix;
-        mp.cs[l] = (unsigned)cls_stride[l];
-        mp.cu[l] = (unsigned)(cls_stride[l] / vec);
-        mp.rs[l] = (unsigned)reg_stride[l];
-        mp.stride[l] = (float)strides[l];
-        mp.rrow[l] = (unsigned)rrow;
-        rrow += (int64_t)B * pix;
-        elems += (int64_t)B * pix * (cls_stride[l] + reg_stride[l]);
+        t.st.v[l] = (float)strides[l];
     }
-    for (int l = L; l <= ATSS_MAX_LEVELS; ++l) mp.rrow[l] = (unsigned)rrow;
-    HTD_REQUIRE(rrow < ((int64_t)1 << 31) && elems < ((int64_t)1 << 40), "%s: more than 2^31 pixel rows", what);
     return HTD_OK;
 }
 
-int64_t gfl_blocks(int64_t A) { return (A + 255) / 256; }
-
 }  // namespace
 
-extern "C" int64_t htd_gfl_quality_workspace_bytes(int B, int64_t A) { return (int64_t)B * gfl_blocks(A) * 8; }
+extern "C" int64_t htd_gfl_quality_workspace_bytes(int B, int64_t A) { return (int64_t)B * blocks_of(A) * 8; }
 
 extern "C" int htd_gfl_quality(const float *const *cls, const int64_t *cls_stride, const float *const *reg, const int64_t *reg_stride,
                                const int64_t *level_sizes, const int64_t *strides, int L, int B, int C, int reg_max,
                                const float *anchors, const float *gts, int K, const int *assigned, float *weight, float *score,
                                float *wsum, void *workspace, void *stream)
 {
-    HTD_REQUIRE(cls && anchors && gts && assigned && weight && score && wsum && workspace, "gfl_quality: null pointer");
+    HTD_REQUIRE(anchors && gts && assigned && weight && score && wsum && workspace, "gfl_quality: null pointer");
     HTD_REQUIRE(K > 0, "gfl_quality: bad parameters");
     HTD_REQUIRE((((uintptr_t)anchors | (uintptr_t)gts) & 15) == 0 && ((uintptr_t)workspace & 7) == 0,
                 "gfl_quality: anchors / gts must be 16-byte aligned, the workspace 8-byte");
-    AtssLevels lv = {};
-    int64_t A = 0;
-    int rc = fill_levels(lv, "gfl_quality", level_sizes, L, &A);
+    GflTables t = {};
+    const int rc = gfl_tables(t, "gfl_quality", {cls, nullptr, cls_stride, C, true, false}, {reg, nullptr, reg_stride, 0, true, false},
+                              level_sizes, strides, L, B, reg_max, 1);
     if (rc != HTD_OK) return rc;
-    GflMaps mp = {};
-    rc = fill_gfl_maps(mp, "gfl_quality", lv, cls, cls_stride, reg, reg_stride, nullptr, nullptr, strides, L, B, C, reg_max, 1);
-    if (rc != HTD_OK) return rc;
-    HTD_REQUIRE((int64_t)B * A < ((int64_t)1 << 31), "gfl_quality: more than 2^31 anchors in the batch");
-    const int nblk = (int)gfl_blocks(A);
-    hipLaunchKernelGGL(gfl_quality_kernel, dim3(nblk, B), dim3(256), 0, (hipStream_t)stream, mp, lv, L, C, reg_max + 1, anchors, gts,
-                       K, assigned, weight, score, (double *)workspace);
+    const int nblk = (int)blocks_of(t.A);
+    hipLaunchKernelGGL(gfl_quality_kernel, dim3(nblk, B), dim3(256), 0, (hipStream_t)stream, t.mp, t.lv, t.st, L, C, reg_max + 1,
+                       anchors, gts, K, assigned, weight, score, (double *)workspace);
     hipLaunchKernelGGL(gfl_quality_finish_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const double *)workspace, B * nblk,
                        wsum);
     return htd::check_launch("gfl_quality");
 }
 
-extern "C" int htd_gfl_loss_partial_rows(void) { return 2 * ATSS_BLOCKS; }
+extern "C" int htd_gfl_loss_partial_rows(void) { return 2 * POINT_BLOCKS; }
 
 extern "C" int htd_gfl_loss(const float *const *cls, const int64_t *cls_stride, const float *const *reg, const int64_t *reg_stride,
                             const int64_t *level_sizes, const int64_t *strides, int L, int B, int C, int reg_max,
@@ -432,34 +357,17 @@ extern "C" int htd_gfl_loss(const float *const *cls, const int64_t *cls_stride, 
                             float beta, float cls_weight, float box_weight, float dfl_weight, float *partial,
                             float *const *grad_cls, float *const *grad_reg, void *stream)
 {
-    HTD_REQUIRE(cls && grad_cls && grad_reg && anchors && gts && gt_labels && assigned && weight && score && norm && wsum && partial,
-                "gfl_loss: null pointer");
+    HTD_REQUIRE(anchors && gts && gt_labels && assigned && weight && score && norm && wsum && partial, "gfl_loss: null pointer");
     HTD_REQUIRE(K > 0 && beta >= 0.f && (box_kind == BOX_IOU || box_kind == BOX_GIOU), "gfl_loss: bad parameters");
     HTD_REQUIRE((((uintptr_t)anchors | (uintptr_t)gts) & 15) == 0, "gfl_loss: anchors / gts must be 16-byte aligned");
-    AtssLevels lv = {};
-    int64_t A = 0;
-    int rc = fill_levels(lv, "gfl_loss", level_sizes, L, &A);
+    const SweepForm f = sweep_form(C, cls_stride, L);
+    GflTables t = {};
+    const int rc = gfl_tables(t, "gfl_loss", {cls, grad_cls, cls_stride, C, true, true}, {reg, grad_reg, reg_stride, 0, true, true},
+                              level_sizes, strides, L, B, reg_max, f.vec);
     if (rc != HTD_OK) return rc;
-    bool vec = (C & 3) == 0;
-    for (int l = 0; l < L && vec; ++l) vec = cls_stride && (cls_stride[l] & 3) == 0;
-    GflMaps mp = {};
-    rc = fill_gfl_maps(mp, "gfl_loss", lv, cls, cls_stride, reg, reg_stride, grad_cls, grad_reg, strides, L, B, C, reg_max,
-                       vec ? 4 : 1);
-    if (rc != HTD_OK) return rc;
-    HTD_REQUIRE((int64_t)B * A < ((int64_t)1 << 31), "gfl_loss: more than 2^31 anchors in the batch");
-    // lanes per pixel row of the classification sweep: the smallest power of two that holds the widest row, from 4 to 64
-    unsigned widest = 1;
-    for (int l = 0; l < L; ++l) widest = mp.cu[l] > widest ? mp.cu[l] : widest;
-    int group_shift = 2;
-    while (group_shift < 6 && (1u << group_shift) < widest) ++group_shift;
-    const bool b2 = beta == 2.f;
-#define HTD_GFL_LAUNCH(V, G)                                                                                                        \
-    hipLaunchKernelGGL((gfl_loss_kernel<V, G>), dim3(ATSS_BLOCKS), dim3(256), 0, (hipStream_t)stream, mp, lv, L, C, reg_max + 1,    \
-                       anchors, gts, gt_labels, K, assigned, weight, score, norm, wsum, box_kind, eps, beta, cls_weight, box_weight, \
-                       dfl_weight, group_shift, partial)
-    if (vec) { if (b2) HTD_GFL_LAUNCH(4, true); else HTD_GFL_LAUNCH(4, false); }
-    else { if (b2) HTD_GFL_LAUNCH(1, true); else HTD_GFL_LAUNCH(1, false); }
-#undef HTD_GFL_LAUNCH
+    HTD_POINT_LAUNCH(gfl_loss_kernel, f.vec, beta == 2.f, stream, t.mp, t.lv, t.st, L, C, reg_max + 1, anchors, gts, gt_labels, K,
+                     assigned, weight, score, norm, wsum, box_kind, eps, beta, cls_weight, box_weight, dfl_weight, f.group_shift,
+                     partial);
     return htd::check_launch("gfl_loss");
 }
 
@@ -469,21 +377,15 @@ extern "C" int htd_gfl_grad_scale(float *const *grad_cls, const int64_t *cls_str
                                   const float *weight, const float *wsum, int box_kind, double eps, float box_weight,
                                   float dfl_weight, const float *g_cls, const float *g_box, const float *g_dfl, void *stream)
 {
-    HTD_REQUIRE(grad_cls && grad_reg && anchors && gts && assigned && weight && wsum && g_cls && g_box && g_dfl,
-                "gfl_grad_scale: null pointer");
+    HTD_REQUIRE(anchors && gts && assigned && weight && wsum && g_cls && g_box && g_dfl, "gfl_grad_scale: null pointer");
     HTD_REQUIRE(K > 0 && (box_kind == BOX_IOU || box_kind == BOX_GIOU), "gfl_grad_scale: bad parameters");
     HTD_REQUIRE((((uintptr_t)anchors | (uintptr_t)gts) & 15) == 0, "gfl_grad_scale: anchors / gts must be 16-byte aligned");
-    AtssLevels lv = {};
-    int64_t A = 0;
-    int rc = fill_levels(lv, "gfl_grad_scale", level_sizes, L, &A);
+    GflTables t = {};
+    const int rc = gfl_tables(t, "gfl_grad_scale", {nullptr, grad_cls, cls_stride, C, false, true},
+                              {reg, grad_reg, reg_stride, 0, true, true}, level_sizes, strides, L, B, reg_max, 1);
     if (rc != HTD_OK) return rc;
-    GflMaps mp = {};
-    rc = fill_gfl_maps(mp, "gfl_grad_scale", lv, nullptr, cls_stride, reg, reg_stride, grad_cls, grad_reg, strides, L, B, C, reg_max,
-                       1);
-    if (rc != HTD_OK) return rc;
-    HTD_REQUIRE((int64_t)B * A < ((int64_t)1 << 31), "gfl_grad_scale: more than 2^31 anchors in the batch");
-    hipLaunchKernelGGL(gfl_scale_kernel, dim3(ATSS_BLOCKS), dim3(256), 0, (hipStream_t)stream, mp, lv, L, C, reg_max + 1, anchors, gts,
-                       K, assigned, weight, wsum, box_kind, eps, box_weight, dfl_weight, g_cls, g_box, g_dfl);
+    hipLaunchKernelGGL(gfl_scale_kernel, dim3(POINT_BLOCKS), dim3(256), 0, (hipStream_t)stream, t.mp, t.lv, t.st, L, C, reg_max + 1,
+                       anchors, gts, K, assigned, weight, wsum, box_kind, eps, box_weight, dfl_weight, g_cls, g_box, g_dfl);
     return htd::check_launch("gfl_grad_scale");
 }
 
@@ -491,16 +393,13 @@ extern "C" int htd_gfl_decode(const float *const *cls, const int64_t *cls_stride
                               const int64_t *level_sizes, const int64_t *strides, int L, int B, int C, int reg_max, float *keys,
                               float *dist, void *stream)
 {
-    HTD_REQUIRE(cls && keys && dist, "gfl_decode: null pointer");
-    AtssLevels lv = {};
-    int64_t A = 0;
-    int rc = fill_levels(lv, "gfl_decode", level_sizes, L, &A);
+    HTD_REQUIRE(keys && dist, "gfl_decode: null pointer");
+    GflTables t = {};
+    const int rc = gfl_tables(t, "gfl_decode", {cls, nullptr, cls_stride, C, true, false}, {reg, nullptr, reg_stride, 0, true, false},
+                              level_sizes, strides, L, B, reg_max, 1);
     if (rc != HTD_OK) return rc;
-    GflMaps mp = {};
-    rc = fill_gfl_maps(mp, "gfl_decode", lv, cls, cls_stride, reg, reg_stride, nullptr, nullptr, strides, L, B, C, reg_max, 1);
-    if (rc != HTD_OK) return rc;
-    const int64_t groups = ((int64_t)B * A + 15) / 16;
-    hipLaunchKernelGGL(gfl_decode_kernel, dim3((unsigned)(groups < ATSS_BLOCKS ? groups : ATSS_BLOCKS)), dim3(256), 0,
-                       (hipStream_t)stream, mp, lv, L, B, C, reg_max + 1, keys, dist);
+    const int64_t groups = ((int64_t)B * t.A + 15) / 16;
+    hipLaunchKernelGGL(gfl_decode_kernel, dim3((unsigned)(groups < POINT_BLOCKS ? groups : POINT_BLOCKS)), dim3(256), 0,
+                       (hipStream_t)stream, t.mp, t.lv, t.st, L, B, C, reg_max + 1, keys, dist);
     return htd::check_launch("gfl_decode");
 }

@@ -1,4 +1,4 @@
-// How focal_loss.hip, ghm_loss.hip and fcos.hip address their maps: the level of an index in a prefix-sum table, the VEC-wide
+// How focal_loss.hip, ghm_loss.hip and the heads of point_maps.h address their maps: the level of an index in a prefix-sum table, the VEC-wide
 // unit of logits or gradients, the unit of a logit matrix.  Each kernel keeps its own loops and calls these.
 #pragma once
 #include "common.h"

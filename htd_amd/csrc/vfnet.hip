@@ -16,22 +16,12 @@
 // No atomics: every sum has a fixed order and every element of every output is stored exactly once with plain vector stores.
 #include "common.h"
 #include "anchor_levels.h"
-#include "focal_elem.h"
 #include "iou_family.h"
-#include "loss_units.h"
+#include "point_scale.h"
 
 namespace {
 
-struct VfMaps {
-    const float *cls[ATSS_MAX_LEVELS], *reg[ATSS_MAX_LEVELS], *ref[ATSS_MAX_LEVELS];
-    float *gcls[ATSS_MAX_LEVELS], *greg[ATSS_MAX_LEVELS], *gref[ATSS_MAX_LEVELS];
-    unsigned pix[ATSS_MAX_LEVELS];
-    unsigned cs[ATSS_MAX_LEVELS];           // channel stride of the classification map in floats (>= C)
-    unsigned cu[ATSS_MAX_LEVELS];           // the same in units of VEC floats
-    unsigned rs[ATSS_MAX_LEVELS];           // channel stride of the initial regression map in floats (>= 4)
-    unsigned fs[ATSS_MAX_LEVELS];           // channel stride of the refined regression map in floats (>= 4)
-    unsigned rrow[ATSS_MAX_LEVELS + 1];     // prefix sums of B * pix: the pixel rows of all levels
-};
+enum { CLS = 0, REG = 1, REF = 2 };       // slots of PointMaps: (B, C, h, w), the initial and the refined (B, 4, h, w)
 
 // ---- star offsets ------------------------------------------------------------------------------------------------------------
 // vfnet_head.py:300-311: offset channel c takes sign * q[side] (q = l, t, r, b in map units) or nothing
@@ -123,7 +113,7 @@ __device__ __forceinline__ float vf_iou(const VfGeometry &q, const float *__rest
 // ---- quality -----------------------------------------------------------------------------------------------------------------
 // grid (ceil(A / 256), B), one thread per anchor: iou_ini / iou_rf of a positive, 0 elsewhere; the block's {count, sum iou_ini,
 // sum iou_rf} (fp64) go to part [B * blocks][3]
-__global__ __launch_bounds__(256) void vfnet_quality_kernel(VfMaps mp, AtssLevels lv, int L, const float *__restrict__ anchors,
+__global__ __launch_bounds__(256) void vfnet_quality_kernel(PointMaps mp, AtssLevels lv, int L, const float *__restrict__ anchors,
                                                             const float *__restrict__ gts, int K, const int *__restrict__ assigned,
                                                             float *__restrict__ iou_ini, float *__restrict__ iou_rf,
                                                             double *__restrict__ part)
@@ -141,8 +131,8 @@ __global__ __launch_bounds__(256) void vfnet_quality_kernel(VfMaps mp, AtssLevel
             const unsigned l = level_of(lv.aoff, L, i);
             const int64_t row = (int64_t)b * mp.pix[l] + (i - lv.aoff[l]);
             const VfGeometry q = vf_geometry(load4(anchors, i), load4(gts, (int64_t)b * K + (as - 1)));
-            qi = vf_iou(q, mp.reg[l] + row * mp.rs[l]);
-            qr = vf_iou(q, mp.ref[l] + row * mp.fs[l]);
+            qi = vf_iou(q, mp.map[REG][l] + row * mp.cs[REG][l]);
+            qr = vf_iou(q, mp.map[REF][l] + row * mp.cs[REF][l]);
             v[0] = 1.;
         }
         iou_ini[o] = qi;
@@ -180,12 +170,11 @@ __global__ __launch_bounds__(64) void vfnet_quality_finish_kernel(const double *
 __device__ __forceinline__ float vfl_positive(float xf, float qf, bool iou_weighted, float &g)
 {
     const double x = (double)xf, q = (double)qf;
-    const double ez = exp(-fabs(x));
-    const double sp = fmax(x, 0.) + log1p(ez);
-    const double s = x >= 0. ? 1. / (1. + ez) : ez / (1. + ez);
+    double l1p, s;
+    sigmoid_log1p(x, l1p, s);
     const double w = iou_weighted ? q : 1.;
     g = (float)((s - q) * w);
-    return (float)((sp - x * q) * w);
+    return (float)((fmax(x, 0.) + l1p - x * q) * w);
 }
 
 // one positive's box loss on decoded boxes, fp64; out [stride] = scale * d loss / d (l, t, r, b) and zeros on the padding
@@ -205,12 +194,13 @@ __device__ __forceinline__ double vf_box_row(const float *__restrict__ d, float 
     return loss;
 }
 
-// Classification maps: a lane group per pixel row [cu units], one anchor per pixel; the same group zero-fills both regression
-// gradient rows of a non-positive anchor.  Then one thread per anchor: a positive's two box losses and gradient rows.
-// partial [ATSS_BLOCKS][2] = {sum VFL, sum iou_ini * initial box loss}, partial + 2 * ATSS_BLOCKS: [ATSS_BLOCKS][2] =
+// Classification maps: the sweep of point_maps.h, one anchor per pixel: the varifocal element against iou_rf on a positive's own
+// class, focal_elem with alpha' = 1 - alpha (alpha * sigmoid(x)^gamma * softplus(x)) elsewhere; the lane group of a row zero-fills
+// both regression gradient rows of a non-positive anchor.  Then one thread per anchor: a positive's two box losses and gradient
+// rows.  partial [POINT_BLOCKS][2] = {sum VFL, sum iou_ini * initial box loss}, partial + 2 * POINT_BLOCKS: [POINT_BLOCKS][2] =
 // {sum iou_rf * refined box loss, 0}, unscaled.
 template <int VEC, bool G2>
-__global__ __launch_bounds__(256) void vfnet_loss_kernel(VfMaps mp, AtssLevels lv, int L, int C, const float *__restrict__ anchors,
+__global__ __launch_bounds__(256) void vfnet_loss_kernel(PointMaps mp, AtssLevels lv, int L, int C, const float *__restrict__ anchors,
                                                          const float *__restrict__ gts, const int64_t *__restrict__ gt_labels, int K,
                                                          const int *__restrict__ assigned, const float *__restrict__ iou_ini,
                                                          const float *__restrict__ iou_rf, const float *__restrict__ sums,
@@ -218,149 +208,43 @@ __global__ __launch_bounds__(256) void vfnet_loss_kernel(VfMaps mp, AtssLevels l
                                                          float gamma, int iou_weighted, float cls_weight, float box_weight,
                                                          float ref_weight, int group_shift, float *__restrict__ partial)
 {
-    const unsigned A = lv.aoff[L];
     const float n_pos = fmaxf(sums[0], 1.f), n_ini = fmaxf(sums[1], 1.f), n_rf = fmaxf(sums[2], 1.f);
-    const float cs = cls_weight / n_pos;
     const float neg_alpha = 1.f - alpha;        // focal_elem weighs a negative by 1 - its alpha
     const unsigned n_rows = mp.rrow[L];
-    float s_cls = 0.f;
-    const unsigned lane = threadIdx.x & 63u;
-    const unsigned gl = 1u << group_shift, sub = lane & (gl - 1u), rpw = 64u >> group_shift;
-    const unsigned wave = blockIdx.x * 4u + (threadIdx.x >> 6);
-    for (unsigned rw0 = wave * rpw; rw0 < n_rows; rw0 += gridDim.x * 4u * rpw) {
-        const unsigned rw = rw0 + (lane >> group_shift);
-        if (rw >= n_rows) continue;
-        const int l = level_of(mp.rrow, L, rw);
-        const unsigned row = rw - mp.rrow[l];                                       // b * pix + p
-        const unsigned b = row / mp.pix[l], p = row - b * mp.pix[l];
-        const unsigned cu = mp.cu[l];
-        const int64_t o = (int64_t)b * A + lv.aoff[l] + p;
-        const int as = assigned[o];
-        const bool pos = as > 0 && as <= K;
-        const int64_t lab = pos ? gt_labels[(int64_t)b * K + (as - 1)] : (int64_t)C;
-        const float qr = iou_rf[o];
-        const float *x_row = mp.cls[l] + (int64_t)row * cu * VEC;
-        float *g_row = mp.gcls[l] + (int64_t)row * cu * VEC;
-        for (unsigned j = sub; j < cu; j += gl) {
-            const unsigned c0 = j * VEC;
-            float go[VEC];
-#pragma unroll
-            for (int k = 0; k < VEC; ++k) go[k] = 0.f;
-            if (c0 < (unsigned)C) {                                                 // (VEC = 4: C % 4 == 0, whole units)
-                float xv[VEC];
-                load_unit<VEC>(x_row, j, xv);
-#pragma unroll
-                for (int k = 0; k < VEC; ++k) {
-                    float g;
-                    if (lab == (int64_t)(c0 + k)) s_cls += vfl_positive(xv[k], qr, iou_weighted != 0, g);
-                    else s_cls += focal_elem<G2>(xv[k], false, gamma, neg_alpha, g);  // alpha * sigmoid(x)^gamma * softplus(x)
-                    go[k] = g * cs;
-                }
-            }
-            store_unit<VEC>(g_row, j, go);
-        }
-        if (!pos) {
-            const unsigned rs = mp.rs[l], fs = mp.fs[l];
-            float *g_reg = mp.greg[l] + (int64_t)row * rs;
-            float *g_ref = mp.gref[l] + (int64_t)row * fs;
+    const float s_cls = cls_sweep<VEC>(
+        mp, lv.aoff, L, C, assigned, gt_labels, K, iou_rf, cls_weight / n_pos, group_shift,
+        [=](float x, bool own, float qr, float &g) {
+            return own ? vfl_positive(x, qr, iou_weighted != 0, g) : focal_elem<G2>(x, false, gamma, neg_alpha, g);
+        },
+        [&](const PointRow &r, bool pos, unsigned sub, unsigned gl) {
+            if (pos) return;
+            const unsigned rs = mp.cs[REG][r.l], fs = mp.cs[REF][r.l];
+            float *g_reg = slot_grad_row(mp, REG, r), *g_ref = slot_grad_row(mp, REF, r);
             for (unsigned j = sub; j < rs; j += gl) g_reg[j] = 0.f;
             for (unsigned j = sub; j < fs; j += gl) g_ref[j] = 0.f;
-        }
-    }
+        });
     double s_ini = 0., s_rf = 0.;
     for (unsigned rw = blockIdx.x * 256u + threadIdx.x; rw < n_rows; rw += gridDim.x * 256u) {
-        const int l = level_of(mp.rrow, L, rw);
-        const unsigned row = rw - mp.rrow[l];
-        const unsigned b = row / mp.pix[l], p = row - b * mp.pix[l];
-        const unsigned ai = lv.aoff[l] + p;
-        const int64_t o = (int64_t)b * A + ai;
-        const int as = assigned[o];
+        const PointRow r = point_row(mp, lv.aoff, L, rw);
+        const int as = assigned[r.o];
         if (as > 0 && as <= K) {
-            const unsigned rs = mp.rs[l], fs = mp.fs[l];
-            const VfGeometry q = vf_geometry(load4(anchors, ai), load4(gts, (int64_t)b * K + (as - 1)));
-            const double wi = (double)iou_ini[o], wr = (double)iou_rf[o];
-            s_ini += wi * vf_box_row(mp.reg[l] + (int64_t)row * rs, mp.greg[l] + (int64_t)row * rs, rs, q, box_kind, eps_ini,
+            const VfGeometry q = vf_geometry(load4(anchors, r.i), load4(gts, (int64_t)r.b * K + (as - 1)));
+            const double wi = (double)iou_ini[r.o], wr = (double)iou_rf[r.o];
+            s_ini += wi * vf_box_row(slot_row(mp, REG, r), slot_grad_row(mp, REG, r), mp.cs[REG][r.l], q, box_kind, eps_ini,
                                      wi * (double)box_weight / (double)n_ini);
-            s_rf += wr * vf_box_row(mp.ref[l] + (int64_t)row * fs, mp.gref[l] + (int64_t)row * fs, fs, q, ref_kind, eps_rf,
+            s_rf += wr * vf_box_row(slot_row(mp, REF, r), slot_grad_row(mp, REF, r), mp.cs[REF][r.l], q, ref_kind, eps_rf,
                                     wr * (double)ref_weight / (double)n_rf);
         }
     }
     block_store_partial2(s_cls, (float)s_ini, partial);
     __syncthreads();                        // the reduction's LDS is read before the second pair overwrites it
-    block_store_partial2((float)s_rf, 0.f, partial + 2 * ATSS_BLOCKS);
+    block_store_partial2((float)s_rf, 0.f, partial + 2 * POINT_BLOCKS);
 }
-
-// gradient maps *= the incoming gradients (device scalars); a map kind whose factor is exactly 1 is left alone, decided here
-__global__ __launch_bounds__(256) void vfnet_scale_kernel(VfMaps mp, int L, int cls_width, const float *__restrict__ g_cls,
-                                                          const float *__restrict__ g_box, const float *__restrict__ g_ref)
-{
-    const float gc = *g_cls, gb = *g_box, gr = *g_ref;
-    const unsigned n_rows = mp.rrow[L];
-    const unsigned lane = threadIdx.x & 63u;
-    const unsigned wave = __builtin_amdgcn_readfirstlane(blockIdx.x * 4u + (threadIdx.x >> 6));
-    if (gc != 1.f) {
-        for (unsigned rw = wave; rw < n_rows; rw += gridDim.x * 4u) {
-            const int l = level_of(mp.rrow, L, rw);
-            float *g_row = mp.gcls[l] + (int64_t)(rw - mp.rrow[l]) * mp.cs[l];
-            for (unsigned j = lane; j < (unsigned)cls_width; j += 64u) g_row[j] *= gc;
-        }
-    }
-    if (gb != 1.f || gr != 1.f) {
-        for (unsigned rw = blockIdx.x * 256u + threadIdx.x; rw < n_rows; rw += gridDim.x * 256u) {
-            const int l = level_of(mp.rrow, L, rw);
-            const unsigned row = rw - mp.rrow[l];
-            float *g_reg = mp.greg[l] + (int64_t)row * mp.rs[l];
-            float *g_rf = mp.gref[l] + (int64_t)row * mp.fs[l];
-            if (gb != 1.f)
-                for (int k = 0; k < 4; ++k) g_reg[k] *= gb;
-            if (gr != 1.f)
-                for (int k = 0; k < 4; ++k) g_rf[k] *= gr;
-        }
-    }
-}
-
-// vec: units of the classification map (4: float4 units, 1: floats).  Any of the six tables may be null (maps not used).
-int fill_vf_maps(VfMaps &mp, const char *what, const AtssLevels &lv, const float *const *cls, const int64_t *cls_stride,
-                 const float *const *reg, const int64_t *reg_stride, const float *const *ref, const int64_t *ref_stride,
-                 float *const *gcls, float *const *greg, float *const *gref, int L, int B, int C, int vec)
-{
-    HTD_REQUIRE(B > 0 && B < 65536 && C > 0, "%s: bad sizes", what);
-    HTD_REQUIRE(cls_stride && reg_stride && ref_stride, "%s: null stride table", what);
-    int64_t rrow = 0, elems = 0;
-    for (int l = 0; l < L; ++l) {
-        const int64_t pix = (int64_t)lv.aoff[l + 1] - lv.aoff[l];
-        HTD_REQUIRE(cls_stride[l] >= C && cls_stride[l] % vec == 0 && cls_stride[l] < (1 << 20),
-                    "%s: bad classification stride of level %d", what, l);
-        HTD_REQUIRE((!cls || cls[l]) && (!gcls || gcls[l]), "%s: classification map of level %d is null", what, l);
-        HTD_REQUIRE(vec != 4 || ((((uintptr_t)(cls ? cls[l] : nullptr) | (uintptr_t)(gcls ? gcls[l] : nullptr)) & 15) == 0),
-                    "%s: classification map of level %d is not 16-byte aligned", what, l);
-        HTD_REQUIRE(reg_stride[l] >= 4 && reg_stride[l] < (1 << 20) && ref_stride[l] >= 4 && ref_stride[l] < (1 << 20),
-                    "%s: bad regression stride of level %d", what, l);
-        HTD_REQUIRE((!reg || reg[l]) && (!ref || ref[l]) && (!greg || greg[l]) && (!gref || gref[l]),
-                    "%s: regression map of level %d is null", what, l);
-        mp.cls[l] = cls ? cls[l] : nullptr; mp.gcls[l] = gcls ? gcls[l] : nullptr;
-        mp.reg[l] = reg ? reg[l] : nullptr; mp.greg[l] = greg ? greg[l] : nullptr;
-        mp.ref[l] = ref ? ref[l] : nullptr; mp.gref[l] = gref ? gref[l] : nullptr;
-        mp.pix[l] = (unsigned)pix;
-        mp.cs[l] = (unsigned)cls_stride[l];
-        mp.cu[l] = (unsigned)(cls_stride[l] / vec);
-        mp.rs[l] = (unsigned)reg_stride[l];
-        mp.fs[l] = (unsigned)ref_stride[l];
-        mp.rrow[l] = (unsigned)rrow;
-        rrow += (int64_t)B * pix;
-        elems += (int64_t)B * pix * (cls_stride[l] + reg_stride[l] + ref_stride[l]);
-    }
-    for (int l = L; l <= ATSS_MAX_LEVELS; ++l) mp.rrow[l] = (unsigned)rrow;
-    HTD_REQUIRE(rrow < ((int64_t)1 << 31) && elems < ((int64_t)1 << 40), "%s: more than 2^31 pixel rows", what);
-    return HTD_OK;
-}
-
-int64_t vf_blocks(int64_t A) { return (A + 255) / 256; }
 
 unsigned star_grid(int64_t n)
 {
-    const int64_t blocks = (n + 255) / 256;
-    return (unsigned)(blocks < ATSS_BLOCKS ? blocks : ATSS_BLOCKS);
+    const int64_t blocks = blocks_of(n);
+    return (unsigned)(blocks < POINT_BLOCKS ? blocks : POINT_BLOCKS);
 }
 
 bool box_kind_ok(int k) { return k == BOX_IOU || k == BOX_GIOU; }
@@ -400,14 +284,14 @@ extern "C" int htd_vfnet_star_bwd(const float *bbox_pred, int64_t pred_stride, c
     return htd::check_launch("vfnet_star_bwd");
 }
 
-extern "C" int64_t htd_vfnet_quality_workspace_bytes(int B, int64_t A) { return (int64_t)B * vf_blocks(A) * 3 * 8; }
+extern "C" int64_t htd_vfnet_quality_workspace_bytes(int B, int64_t A) { return (int64_t)B * blocks_of(A) * 3 * 8; }
 
 extern "C" int htd_vfnet_quality(const float *const *reg, const int64_t *reg_stride, const float *const *ref,
                                  const int64_t *ref_stride, const int64_t *level_sizes, int L, int B, const float *anchors,
                                  const float *gts, int K, const int *assigned, float *iou_ini, float *iou_rf, float *sums,
                                  void *workspace, void *stream)
 {
-    HTD_REQUIRE(reg && ref && anchors && gts && assigned && iou_ini && iou_rf && sums && workspace, "vfnet_quality: null pointer");
+    HTD_REQUIRE(anchors && gts && assigned && iou_ini && iou_rf && sums && workspace, "vfnet_quality: null pointer");
     HTD_REQUIRE(K > 0, "vfnet_quality: bad parameters");
     HTD_REQUIRE((((uintptr_t)anchors | (uintptr_t)gts) & 15) == 0 && ((uintptr_t)workspace & 7) == 0,
                 "vfnet_quality: anchors / gts must be 16-byte aligned, the workspace 8-byte");
@@ -415,13 +299,11 @@ extern "C" int htd_vfnet_quality(const float *const *reg, const int64_t *reg_str
     int64_t A = 0;
     int rc = fill_levels(lv, "vfnet_quality", level_sizes, L, &A);
     if (rc != HTD_OK) return rc;
-    VfMaps mp = {};
-    int64_t one[ATSS_MAX_LEVELS];
-    for (int l = 0; l < ATSS_MAX_LEVELS; ++l) one[l] = 1;
-    rc = fill_vf_maps(mp, "vfnet_quality", lv, nullptr, one, reg, reg_stride, ref, ref_stride, nullptr, nullptr, nullptr, L, B, 1, 1);
+    const PointSlot slots[POINT_SLOTS] = {{}, {reg, nullptr, reg_stride, 4, true, false}, {ref, nullptr, ref_stride, 4, true, false}};
+    PointMaps mp = {};
+    rc = fill_point_maps(mp, "vfnet_quality", lv.aoff, L, B, slots, 1);
     if (rc != HTD_OK) return rc;
-    HTD_REQUIRE((int64_t)B * A < ((int64_t)1 << 31), "vfnet_quality: more than 2^31 anchors in the batch");
-    const int nblk = (int)vf_blocks(A);
+    const int nblk = (int)blocks_of(A);
     hipLaunchKernelGGL(vfnet_quality_kernel, dim3(nblk, B), dim3(256), 0, (hipStream_t)stream, mp, lv, L, anchors, gts, K, assigned,
                        iou_ini, iou_rf, (double *)workspace);
     hipLaunchKernelGGL(vfnet_quality_finish_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (const double *)workspace, B * nblk,
@@ -429,7 +311,7 @@ extern "C" int htd_vfnet_quality(const float *const *reg, const int64_t *reg_str
     return htd::check_launch("vfnet_quality");
 }
 
-extern "C" int htd_vfnet_loss_partial_rows(void) { return 2 * ATSS_BLOCKS; }
+extern "C" int htd_vfnet_loss_partial_rows(void) { return 2 * POINT_BLOCKS; }
 
 extern "C" int htd_vfnet_loss(const float *const *cls, const int64_t *cls_stride, const float *const *reg, const int64_t *reg_stride,
                               const float *const *ref, const int64_t *ref_stride, const int64_t *level_sizes, int L, int B, int C,
@@ -439,34 +321,22 @@ extern "C" int htd_vfnet_loss(const float *const *cls, const int64_t *cls_stride
                               float box_weight, float ref_weight, float *partial, float *const *grad_cls, float *const *grad_reg,
                               float *const *grad_ref, void *stream)
 {
-    HTD_REQUIRE(cls && reg && ref && grad_cls && grad_reg && grad_ref && anchors && gts && gt_labels && assigned && iou_ini &&
-                iou_rf && sums && partial, "vfnet_loss: null pointer");
+    HTD_REQUIRE(anchors && gts && gt_labels && assigned && iou_ini && iou_rf && sums && partial, "vfnet_loss: null pointer");
     HTD_REQUIRE(K > 0 && alpha >= 0.f && gamma >= 0.f && box_kind_ok(box_kind) && box_kind_ok(ref_kind), "vfnet_loss: bad parameters");
     HTD_REQUIRE((((uintptr_t)anchors | (uintptr_t)gts) & 15) == 0, "vfnet_loss: anchors / gts must be 16-byte aligned");
     AtssLevels lv = {};
     int64_t A = 0;
     int rc = fill_levels(lv, "vfnet_loss", level_sizes, L, &A);
     if (rc != HTD_OK) return rc;
-    bool vec = (C & 3) == 0;
-    for (int l = 0; l < L && vec; ++l) vec = cls_stride && (cls_stride[l] & 3) == 0;
-    VfMaps mp = {};
-    rc = fill_vf_maps(mp, "vfnet_loss", lv, cls, cls_stride, reg, reg_stride, ref, ref_stride, grad_cls, grad_reg, grad_ref, L, B, C,
-                      vec ? 4 : 1);
+    const SweepForm f = sweep_form(C, cls_stride, L);
+    const PointSlot slots[POINT_SLOTS] = {{cls, grad_cls, cls_stride, C, true, true}, {reg, grad_reg, reg_stride, 4, true, true},
+                                          {ref, grad_ref, ref_stride, 4, true, true}};
+    PointMaps mp = {};
+    rc = fill_point_maps(mp, "vfnet_loss", lv.aoff, L, B, slots, f.vec);
     if (rc != HTD_OK) return rc;
-    HTD_REQUIRE((int64_t)B * A < ((int64_t)1 << 31), "vfnet_loss: more than 2^31 anchors in the batch");
-    // lanes per pixel row of the classification sweep: the smallest power of two that holds the widest row, from 4 to 64
-    unsigned widest = 1;
-    for (int l = 0; l < L; ++l) widest = mp.cu[l] > widest ? mp.cu[l] : widest;
-    int group_shift = 2;
-    while (group_shift < 6 && (1u << group_shift) < widest) ++group_shift;
-    const bool g2 = gamma == 2.f;
-#define HTD_VFNET_LAUNCH(V, G)                                                                                                      \
-    hipLaunchKernelGGL((vfnet_loss_kernel<V, G>), dim3(ATSS_BLOCKS), dim3(256), 0, (hipStream_t)stream, mp, lv, L, C, anchors, gts, \
-                       gt_labels, K, assigned, iou_ini, iou_rf, sums, box_kind, eps_ini, ref_kind, eps_rf, alpha, gamma,            \
-                       iou_weighted, cls_weight, box_weight, ref_weight, group_shift, partial)
-    if (vec) { if (g2) HTD_VFNET_LAUNCH(4, true); else HTD_VFNET_LAUNCH(4, false); }
-    else { if (g2) HTD_VFNET_LAUNCH(1, true); else HTD_VFNET_LAUNCH(1, false); }
-#undef HTD_VFNET_LAUNCH
+    HTD_POINT_LAUNCH(vfnet_loss_kernel, f.vec, gamma == 2.f, stream, mp, lv, L, C, anchors, gts, gt_labels, K, assigned, iou_ini, iou_rf,
+                     sums, box_kind, eps_ini, ref_kind, eps_rf, alpha, gamma, iou_weighted, cls_weight, box_weight, ref_weight,
+                     f.group_shift, partial);
     return htd::check_launch("vfnet_loss");
 }
 
@@ -475,15 +345,10 @@ extern "C" int htd_vfnet_grad_scale(float *const *grad_cls, const int64_t *cls_s
                                     const int64_t *level_sizes, int L, int B, int C, const float *g_cls, const float *g_box,
                                     const float *g_ref, void *stream)
 {
-    HTD_REQUIRE(grad_cls && grad_reg && grad_ref && g_cls && g_box && g_ref, "vfnet_grad_scale: null pointer");
     AtssLevels lv = {};
     int64_t A = 0;
-    int rc = fill_levels(lv, "vfnet_grad_scale", level_sizes, L, &A);
+    const int rc = fill_levels(lv, "vfnet_grad_scale", level_sizes, L, &A);
     if (rc != HTD_OK) return rc;
-    VfMaps mp = {};
-    rc = fill_vf_maps(mp, "vfnet_grad_scale", lv, nullptr, cls_stride, nullptr, reg_stride, nullptr, ref_stride, grad_cls, grad_reg,
-                      grad_ref, L, B, C, 1);
-    if (rc != HTD_OK) return rc;
-    hipLaunchKernelGGL(vfnet_scale_kernel, dim3(ATSS_BLOCKS), dim3(256), 0, (hipStream_t)stream, mp, L, C, g_cls, g_box, g_ref);
-    return htd::check_launch("vfnet_grad_scale");
+    return point_grad_scale<4, 4>("vfnet_grad_scale", lv.aoff, L, B, grad_cls, cls_stride, C, grad_reg, reg_stride, grad_ref,
+                                  ref_stride, g_cls, g_box, g_ref, stream);
 }

@@ -1141,6 +1141,58 @@ def _hand_over_once(ctx, what, entry, tables, grads):
     capi.call(entry, *tables, *[_P(g.float().contiguous()) for g in grads], _S())
 
 
+def _point_tables(what, groups, channels):
+    """The per-level maps of a head with one prediction per location, one list per kind of map (None: a kind this call does not
+    read), checked: float32 (B, channels[k], h, w) GPU maps (channels[k] None: any count), every kind with the levels, the batch
+    and the map sizes of the first.  -> ([(pointer table, channel strides) per kind, (None, None) for a missing one], level sizes,
+    their sum), all HOST tables."""
+    first = next(g for g in groups if g is not None)
+    _need_gpu(first[0], what)
+    tabs = []
+    for maps, ch in zip(groups, channels):
+        if maps is None:
+            tabs.append((None, None))
+            continue
+        if len(maps) != len(first):
+            raise ValueError(f'{what}: every kind of map must have one entry per level, got {len(maps)} beside {len(first)}')
+        for m, f in zip(maps, first):
+            _f32(m, what)
+            if m.dim() != 4 or (ch is not None and m.size(1) != ch) or m.shape[-2:] != f.shape[-2:] or m.size(0) != f.size(0):
+                raise ValueError(f'{what}: a map of shape {tuple(m.shape)} beside one of shape {tuple(f.shape)}, expected '
+                                 f'{"any number of" if ch is None else ch} channels')
+        tabs.append(_level_tables(maps, what)[:2])
+    sizes = [int(m.shape[-2] * m.shape[-1]) for m in first]
+    return tabs, _i64s(sizes), sum(sizes)
+
+
+def _point_loss_forward(ctx, what, entry, kinds, maps, args, saved=()):
+    """The forward of the fused loss of a head with one prediction per location: `entry` (a (table, strides) pair per kind of
+    map, *args, partial sums, a gradient table per kind, stream) over `maps` (kind-major, `kinds` lists of L levels) in one
+    launch, which leaves the finished gradient maps; they are saved after `saved`.  -> the sums [[a, b], [c, 0]] of the three
+    losses, unscaled."""
+    L = len(maps) // kinds
+    groups = [maps[k * L:(k + 1) * L] for k in range(kinds)]
+    tabs = [_level_tables(g, what)[:2] for g in groups]
+    grads = [_grad_maps(g, strides, what) for g, (_, strides) in zip(groups, tabs)]
+    rows = getattr(capi.lib(), entry + '_partial_rows')()
+    partial = torch.empty(rows, 2, device=maps[0].device, dtype=torch.float32)
+    capi.call(entry, *[v for t in tabs for v in t], *args, _P(partial), *[table for _, table in grads], _S())
+    ctx.point_meta = (kinds, L, len(saved))
+    ctx.save_for_backward(*saved, *[g for gs, _ in grads for g in gs])
+    return partial.view(2, rows // 2, 2).sum(1)
+
+
+def _point_loss_backward(ctx, what, entry, args, incoming, arrange=None):
+    """The backward of _point_loss_forward: `entry` (the (table, strides) pairs of the saved gradient maps -- or what `arrange`
+    makes of the list of pairs --, *args, incoming gradients, stream) through _hand_over_once.  -> the gradient maps."""
+    kinds, L, first = ctx.point_meta
+    grads = ctx.saved_tensors[first:]
+    tabs = [_level_tables(grads[k * L:(k + 1) * L], what)[:2] for k in range(kinds)]
+    tables = arrange(tabs) if arrange else [v for t in tabs for v in t]
+    _hand_over_once(ctx, what, entry, (*tables, *args), incoming)
+    return tuple(grads)
+
+
 def _anchor_head_backward(ctx, what, g_cls, g_box):
     """-> the gradient maps of retina_loss / ghm_head_loss times the incoming gradients (htd_retina_grad_scale serves both)."""
     na, C, B, L = ctx.meta
@@ -1379,46 +1431,26 @@ class FcosLossFunction(Function):
     @staticmethod
     def forward(ctx, hw, st, C, gt_labels, assigned, bbox_targets, ctr_targets, norm, box_kind, eps, gamma, alpha, cls_weight,
                 box_weight, ctr_weight, *maps):
-        L = len(maps) // 3
-        cls, reg, ctr = maps[:L], maps[L:2 * L], maps[2 * L:]
         B, K = gt_labels.shape
-        ct, cs, _ = _level_tables(cls, 'fcos_loss')
-        rt, rs, _ = _level_tables(reg, 'fcos_loss')
-        tt, ts, _ = _level_tables(ctr, 'fcos_loss')
-        gcls, gct = _grad_maps(cls, cs, 'fcos_loss')
-        greg, grt = _grad_maps(reg, rs, 'fcos_loss')
-        gctr, gtt = _grad_maps(ctr, ts, 'fcos_loss')
-        rows = capi.lib().htd_fcos_loss_partial_rows()
-        partial = torch.empty(rows, 2, device=assigned.device, dtype=torch.float32)
-        capi.call('htd_fcos_loss', ct, cs, rt, rs, tt, ts, hw, st, L, B, int(C), _P(gt_labels), K, _P(assigned), _P(bbox_targets),
-                  _P(ctr_targets), _P(norm), int(box_kind), float(eps), float(gamma), float(alpha), float(cls_weight),
-                  float(box_weight), float(ctr_weight), _P(partial), gct, grt, gtt, _S())
-        ctx.meta = (hw, st, L, B, int(C))
-        ctx.save_for_backward(*gcls, *greg, *gctr)
-        sums = partial.view(2, rows // 2, 2).sum(1)             # [[focal, box], [centerness, 0]]
+        ctx.meta = (hw, st, len(maps) // 3, B, int(C))
+        sums = _point_loss_forward(ctx, 'fcos_loss', 'htd_fcos_loss', 3, maps,
+                                   (*ctx.meta, _P(gt_labels), K, _P(assigned), _P(bbox_targets), _P(ctr_targets), _P(norm),
+                                    int(box_kind), float(eps), float(gamma), float(alpha), float(cls_weight), float(box_weight),
+                                    float(ctr_weight)))                 # [[focal, box], [centerness, 0]]
         return sums[0, 0] / norm[0] * cls_weight, sums[0, 1] / norm[2].clamp(min=1e-30) * box_weight, \
             sums[1, 0] / norm[1] * ctr_weight
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g_cls, g_box, g_ctr):
-        hw, st, L, B, C = ctx.meta
-        grads = ctx.saved_tensors
-        gct, gcs, _ = _level_tables(grads[:L], 'fcos_loss')
-        grt, grs, _ = _level_tables(grads[L:2 * L], 'fcos_loss')
-        gtt, gts_, _ = _level_tables(grads[2 * L:], 'fcos_loss')
-        _hand_over_once(ctx, 'fcos_loss', 'htd_fcos_grad_scale', (gct, gcs, grt, grs, gtt, gts_, hw, st, L, B, C),
-                        (g_cls, g_box, g_ctr))
-        return (None, ) * 15 + tuple(grads)
+        return (None, ) * 15 + _point_loss_backward(ctx, 'fcos_loss', 'htd_fcos_grad_scale', ctx.meta, (g_cls, g_box, g_ctr))
 
 
 def fcos_loss(cls_maps, reg_maps, ctr_maps, strides, gt_labels, assigned, bbox_targets, ctr_targets, norm, box_kind, eps=1e-6,
               gamma=2.0, alpha=0.25, cls_weight=1.0, box_weight=1.0, ctr_weight=1.0):
     """-> (loss_cls, loss_bbox, loss_centerness) of an FCOS head from its per-level (B, C, h, w) / (B, 4, h, w) / (B, 1, h, w)
     maps and the outputs of fcos_targets.  box_kind: FCOS_BOX_KINDS[type of the box loss]."""
-    _need_gpu(assigned, 'fcos_loss')
-    for m in list(cls_maps) + list(reg_maps) + list(ctr_maps):
-        _f32(m, 'fcos_loss')
+    _point_tables('fcos_loss', (cls_maps, reg_maps, ctr_maps), (None, 4, 1))
     hw, st, P = _fcos_levels([m.shape[-2:] for m in cls_maps], strides)
     if assigned.shape != (cls_maps[0].size(0), P) or assigned.dtype != torch.int32:
         raise ValueError(f'fcos_loss: assigned must be int32 of shape {(cls_maps[0].size(0), P)}')
@@ -1429,12 +1461,8 @@ def fcos_loss(cls_maps, reg_maps, ctr_maps, strides, gt_labels, assigned, bbox_t
 
 def fcos_keys(cls_maps, ctr_maps, strides):
     """(B, P) max_c sigmoid(cls) * sigmoid(centerness) of every point of every level (level-major), one launch (htd_fcos_keys)."""
-    _need_gpu(cls_maps[0], 'fcos_keys')
-    for m in list(cls_maps) + list(ctr_maps):
-        _f32(m, 'fcos_keys')
+    ((ct, cs), (tt, ts)), _, _ = _point_tables('fcos_keys', (cls_maps, ctr_maps), (None, 1))
     hw, st, P = _fcos_levels([m.shape[-2:] for m in cls_maps], strides)
-    ct, cs, _ = _level_tables(cls_maps, 'fcos_keys')
-    tt, ts, _ = _level_tables(ctr_maps, 'fcos_keys')
     B = cls_maps[0].size(0)
     keys = torch.empty(B, P, device=cls_maps[0].device, dtype=torch.float32)
     capi.call('htd_fcos_keys', ct, cs, tt, ts, hw, st, len(cls_maps), B, cls_maps[0].size(1), _P(keys), _S())
@@ -1478,37 +1506,20 @@ class AtssLossFunction(Function):
     def forward(ctx, hw, st, sizes, C, anchors, gts, gt_labels, assigned, ctr_targets, norm, means, stds, wh_ratio_clip, box_kind,
                 eps, gamma, alpha, cls_weight, box_weight, ctr_weight, *maps):
         from .core.bbox import _d4
-        L = len(maps) // 3
-        cls, reg, ctr = maps[:L], maps[L:2 * L], maps[2 * L:]
         B, K = gt_labels.shape
-        ct, cs, _ = _level_tables(cls, 'atss_loss')
-        rt, rs, _ = _level_tables(reg, 'atss_loss')
-        tt, ts, _ = _level_tables(ctr, 'atss_loss')
-        gcls, gct = _grad_maps(cls, cs, 'atss_loss')
-        greg, grt = _grad_maps(reg, rs, 'atss_loss')
-        gctr, gtt = _grad_maps(ctr, ts, 'atss_loss')
-        rows = capi.lib().htd_atss_loss_partial_rows()
-        partial = torch.empty(rows, 2, device=assigned.device, dtype=torch.float32)
-        capi.call('htd_atss_loss', ct, cs, rt, rs, tt, ts, sizes, L, B, int(C), _P(anchors), _P(gts), _P(gt_labels), K, _P(assigned),
-                  _P(ctr_targets), _P(norm), _d4(means), _d4(stds), float(wh_ratio_clip), int(box_kind), float(eps), float(gamma),
-                  float(alpha), float(cls_weight), float(box_weight), float(ctr_weight), _P(partial), gct, grt, gtt, _S())
+        L = len(maps) // 3
         ctx.meta = (hw, st, L, B, int(C))
-        ctx.save_for_backward(*gcls, *greg, *gctr)
-        sums = partial.view(2, rows // 2, 2).sum(1)             # [[focal, box], [centerness, 0]]
+        sums = _point_loss_forward(ctx, 'atss_loss', 'htd_atss_loss', 3, maps,
+                                   (sizes, L, B, int(C), _P(anchors), _P(gts), _P(gt_labels), K, _P(assigned), _P(ctr_targets),
+                                    _P(norm), _d4(means), _d4(stds), float(wh_ratio_clip), int(box_kind), float(eps), float(gamma),
+                                    float(alpha), float(cls_weight), float(box_weight), float(ctr_weight)))
         box_norm = torch.where(norm[2] < 1e-12, torch.ones_like(norm[2]), norm[2])      # atss_head.py:289-290
         return sums[0, 0] / norm[0] * cls_weight, sums[0, 1] / box_norm * box_weight, sums[1, 0] / norm[1] * ctr_weight
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g_cls, g_box, g_ctr):
-        hw, st, L, B, C = ctx.meta
-        grads = ctx.saved_tensors
-        gct, gcs, _ = _level_tables(grads[:L], 'atss_loss')
-        grt, grs, _ = _level_tables(grads[L:2 * L], 'atss_loss')
-        gtt, gts_, _ = _level_tables(grads[2 * L:], 'atss_loss')
-        _hand_over_once(ctx, 'atss_loss', 'htd_fcos_grad_scale', (gct, gcs, grt, grs, gtt, gts_, hw, st, L, B, C),
-                        (g_cls, g_box, g_ctr))
-        return (None, ) * 20 + tuple(grads)
+        return (None, ) * 20 + _point_loss_backward(ctx, 'atss_loss', 'htd_fcos_grad_scale', ctx.meta, (g_cls, g_box, g_ctr))
 
 
 def atss_loss(cls_maps, reg_maps, ctr_maps, strides, anchors, gts, gt_labels, assigned, ctr_targets, norm, means, stds, box_kind,
@@ -1516,13 +1527,10 @@ def atss_loss(cls_maps, reg_maps, ctr_maps, strides, anchors, gts, gt_labels, as
     """-> (loss_cls, loss_bbox, loss_centerness) of an ATSS head with one anchor per location from its per-level (B, C, h, w) /
     (B, 4, h, w) / (B, 1, h, w) maps, the (A, 4) anchors, the padded gts and the outputs of atss_targets.  box_kind:
     FCOS_BOX_KINDS[type of the box loss]."""
-    _need_gpu(assigned, 'atss_loss')
-    for m in list(cls_maps) + list(reg_maps) + list(ctr_maps):
-        _f32(m, 'atss_loss')
+    _, sizes, _ = _point_tables('atss_loss', (cls_maps, reg_maps, ctr_maps), (None, 4, 1))
     hw, st, A = _fcos_levels([m.shape[-2:] for m in cls_maps], strides)
     if assigned.shape != (cls_maps[0].size(0), A) or assigned.dtype != torch.int32 or anchors.shape != (A, 4):
         raise ValueError(f'atss_loss: assigned must be int32 of shape {(cls_maps[0].size(0), A)}, anchors float32 {(A, 4)}')
-    sizes = _i64s([int(m.shape[-2] * m.shape[-1]) for m in cls_maps])
     return AtssLossFunction.apply(hw, st, sizes, cls_maps[0].size(1), _f32(anchors, 'atss_loss').contiguous(),
                                   _f32(gts, 'atss_loss').contiguous(), gt_labels.contiguous(), assigned.contiguous(),
                                   ctr_targets.contiguous(), norm, means, stds, wh_ratio_clip, box_kind, eps, gamma, alpha,
@@ -1530,30 +1538,12 @@ def atss_loss(cls_maps, reg_maps, ctr_maps, strides, anchors, gts, gt_labels, as
 
 
 # ====================================================================== GFL head (dense_heads/gfl_head.py)
-def _gfl_tables(cls_maps, reg_maps, strides, reg_max, what):
-    """-> (classification table, strides, regression table, strides, level sizes, pyramid strides, A) of a GFL head's maps, all
-    HOST tables; the maps checked for dtype and channel counts."""
-    _need_gpu(cls_maps[0], what)
-    if len(cls_maps) != len(reg_maps):
-        raise ValueError(f'{what}: {len(cls_maps)} classification maps for {len(reg_maps)} regression maps')
-    for c, r in zip(cls_maps, reg_maps):
-        _f32(c, what)
-        _f32(r, what)
-        if r.size(1) != 4 * (int(reg_max) + 1) or r.shape[-2:] != c.shape[-2:] or r.size(0) != c.size(0):
-            raise ValueError(f'{what}: a regression map of shape {tuple(r.shape)} beside a classification map {tuple(c.shape)} '
-                             f'with reg_max = {reg_max}')
-    _, st, A = _fcos_levels([m.shape[-2:] for m in cls_maps], strides)
-    ct, cs, _ = _level_tables(cls_maps, what)
-    rt, rs, _ = _level_tables(reg_maps, what)
-    sizes = _i64s([int(m.shape[-2] * m.shape[-1]) for m in cls_maps])
-    return ct, cs, rt, rs, sizes, st, A
-
-
 def gfl_quality(cls_maps, reg_maps, strides, reg_max, anchors, gts, assigned):
     """htd_gfl_quality: per positive of `assigned` (B, A) (atss_targets) the weight max_c sigmoid(cls) and the IoU score of its
     integral-decoded box with its gt, 0 elsewhere, and the sum of all weights: what the averaging factor of GFLHead.loss and the
     QFL targets are.  -> weight (B, A), score (B, A), wsum (1,); nothing read back."""
-    ct, cs, rt, rs, sizes, st, A = _gfl_tables(cls_maps, reg_maps, strides, reg_max, 'gfl_quality')
+    ((ct, cs), (rt, rs)), sizes, A = _point_tables('gfl_quality', (cls_maps, reg_maps), (None, 4 * (int(reg_max) + 1)))
+    st = _fcos_levels([m.shape[-2:] for m in cls_maps], strides)[1]
     B, L = cls_maps[0].size(0), len(cls_maps)
     if assigned.shape != (B, A) or assigned.dtype != torch.int32 or anchors.shape != (A, 4) or gts.dim() != 3 or gts.size(0) != B:
         raise ValueError(f'gfl_quality: assigned must be int32 of shape {(B, A)}, anchors float32 {(A, 4)}, gts (B, K, 4)')
@@ -1576,38 +1566,32 @@ class GflLossFunction(Function):
     @staticmethod
     def forward(ctx, st, sizes, C, reg_max, anchors, gts, gt_labels, assigned, weight, score, norm, wsum, box_kind, eps, beta,
                 cls_weight, box_weight, dfl_weight, *maps):
-        L = len(maps) // 2
-        cls, reg = maps[:L], maps[L:]
         B, K = gt_labels.shape
-        ct, cs, _ = _level_tables(cls, 'gfl_loss')
-        rt, rs, _ = _level_tables(reg, 'gfl_loss')
-        gcls, gct = _grad_maps(cls, cs, 'gfl_loss')
-        greg, grt = _grad_maps(reg, rs, 'gfl_loss')
-        rows = capi.lib().htd_gfl_loss_partial_rows()
-        partial = torch.empty(rows, 2, device=assigned.device, dtype=torch.float32)
-        capi.call('htd_gfl_loss', ct, cs, rt, rs, sizes, st, L, B, int(C), int(reg_max), _P(anchors), _P(gts), _P(gt_labels), K,
-                  _P(assigned), _P(weight), _P(score), _P(norm), _P(wsum), int(box_kind), float(eps), float(beta),
-                  float(cls_weight), float(box_weight), float(dfl_weight), _P(partial), gct, grt, _S())
-        ctx.meta = (st, sizes, L, B, int(C), int(reg_max), K, int(box_kind), float(eps), float(box_weight), float(dfl_weight))
-        ctx.save_for_backward(anchors, gts, assigned, weight, wsum, *reg, *gcls, *greg)
-        sums = partial.view(2, rows // 2, 2).sum(1)             # [[qfl, box], [dfl, 0]]
+        L = len(maps) // 2
+        head = (sizes, st, L, B, int(C), int(reg_max))
+        ctx.meta = (head, K, int(box_kind), float(eps), float(box_weight), float(dfl_weight))
+        sums = _point_loss_forward(ctx, 'gfl_loss', 'htd_gfl_loss', 2, maps,
+                                   (*head, _P(anchors), _P(gts), _P(gt_labels), K, _P(assigned), _P(weight), _P(score), _P(norm), _P(wsum), int(box_kind),
+                                    float(eps), float(beta), float(cls_weight), float(box_weight), float(dfl_weight)),
+                                   saved=(anchors, gts, assigned, weight, wsum, *maps[L:]))        # [[qfl, box], [dfl, 0]]
         # gfl_head.py:364-367: the averaging factor is not clamped (no positive: 0 / 0)
         return sums[0, 0] / norm[0] * cls_weight, sums[0, 1] / wsum[0] * box_weight, sums[1, 0] / (4 * wsum[0]) * dfl_weight
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g_cls, g_box, g_dfl):
-        st, sizes, L, B, C, reg_max, K, box_kind, eps, box_weight, dfl_weight = ctx.meta
+        head, K, box_kind, eps, box_weight, dfl_weight = ctx.meta
         anchors, gts, assigned, weight, wsum = ctx.saved_tensors[:5]
-        reg, gcls, greg = (ctx.saved_tensors[5 + i * L:5 + (i + 1) * L] for i in range(3))
-        gct, gcs, _ = _level_tables(gcls, 'gfl_loss')
-        rt, rs, _ = _level_tables(reg, 'gfl_loss')
-        grt, grs, _ = _level_tables(greg, 'gfl_loss')
-        assert list(grs) == list(rs)
-        _hand_over_once(ctx, 'gfl_loss', 'htd_gfl_grad_scale',
-                        (gct, gcs, rt, grt, rs, sizes, st, L, B, C, reg_max, _P(anchors), _P(gts), K, _P(assigned), _P(weight),
-                         _P(wsum), box_kind, eps, box_weight, dfl_weight), (g_cls, g_box, g_dfl))
-        return (None, ) * 18 + tuple(gcls) + tuple(greg)
+        rt, rs, _ = _level_tables(ctx.saved_tensors[5:5 + head[2]], 'gfl_loss')
+
+        def arrange(tabs):                                      # the logits' table between the two gradient tables
+            (gct, gcs), (grt, grs) = tabs
+            assert list(grs) == list(rs)
+            return gct, gcs, rt, grt, rs
+        return (None, ) * 18 + _point_loss_backward(
+            ctx, 'gfl_loss', 'htd_gfl_grad_scale',
+            (*head, _P(anchors), _P(gts), K, _P(assigned), _P(weight), _P(wsum), box_kind, eps, box_weight, dfl_weight),
+            (g_cls, g_box, g_dfl), arrange)
 
 
 def gfl_loss(cls_maps, reg_maps, strides, reg_max, anchors, gts, gt_labels, assigned, weight, score, norm, wsum, box_kind,
@@ -1615,7 +1599,8 @@ def gfl_loss(cls_maps, reg_maps, strides, reg_max, anchors, gts, gt_labels, assi
     """-> (loss_cls, loss_bbox, loss_dfl) of a GFL head from its per-level (B, C, h, w) / (B, 4 * (reg_max + 1), h, w) maps, the
     (A, 4) anchors, the padded gts, `assigned` and `norm` of atss_targets and the outputs of gfl_quality.  box_kind:
     FCOS_BOX_KINDS[type of the box loss]."""
-    *_, sizes, st, A = _gfl_tables(cls_maps, reg_maps, strides, reg_max, 'gfl_loss')
+    _, sizes, A = _point_tables('gfl_loss', (cls_maps, reg_maps), (None, 4 * (int(reg_max) + 1)))
+    st = _fcos_levels([m.shape[-2:] for m in cls_maps], strides)[1]
     B = cls_maps[0].size(0)
     if assigned.shape != (B, A) or assigned.dtype != torch.int32 or anchors.shape != (A, 4) or weight.shape != (B, A) or \
             score.shape != (B, A) or gt_labels.dtype != torch.int64:
@@ -1631,7 +1616,8 @@ def gfl_loss(cls_maps, reg_maps, strides, reg_max, anchors, gts, gt_labels, assi
 def gfl_decode(cls_maps, reg_maps, strides, reg_max):
     """htd_gfl_decode, one launch: keys (B, A) = max_c sigmoid(cls) and dist (B, A, 4) = integral(reg) * stride of every anchor of
     every level (level-major)."""
-    ct, cs, rt, rs, sizes, st, A = _gfl_tables(cls_maps, reg_maps, strides, reg_max, 'gfl_decode')
+    ((ct, cs), (rt, rs)), sizes, A = _point_tables('gfl_decode', (cls_maps, reg_maps), (None, 4 * (int(reg_max) + 1)))
+    st = _fcos_levels([m.shape[-2:] for m in cls_maps], strides)[1]
     B = cls_maps[0].size(0)
     keys = torch.empty(B, A, device=cls_maps[0].device, dtype=torch.float32)
     dist = torch.empty(B, A, 4, device=cls_maps[0].device, dtype=torch.float32)
@@ -1693,32 +1679,12 @@ def vfnet_star(x, denom, stride, gradient_mul):
     return VfnetStarFunction.apply(x, denom, stride, gradient_mul)
 
 
-def _vfnet_tables(cls_maps, reg_maps, ref_maps, what):
-    """-> (classification table, strides, initial table, strides, refined table, strides, level sizes, A), all HOST tables; the
-    maps checked for dtype and shapes.  cls_maps may be None (the quality pass reads no logits)."""
-    _need_gpu(reg_maps[0], what)
-    if len(ref_maps) != len(reg_maps) or (cls_maps is not None and len(cls_maps) != len(reg_maps)):
-        raise ValueError(f'{what}: the three lists of maps must have one entry per level')
-    for l, (r, f) in enumerate(zip(reg_maps, ref_maps)):
-        _f32(r, what)
-        _f32(f, what)
-        c = cls_maps[l] if cls_maps is not None else r
-        _f32(c, what)
-        if r.size(1) != 4 or f.shape != r.shape or c.shape[-2:] != r.shape[-2:] or c.size(0) != r.size(0):
-            raise ValueError(f'{what}: regression maps of shapes {tuple(r.shape)} / {tuple(f.shape)} beside a classification map '
-                             f'{tuple(c.shape)}')
-    ct, cs = (None, None) if cls_maps is None else _level_tables(cls_maps, what)[:2]
-    rt, rs, pix = _level_tables(reg_maps, what)
-    ft, fs, _ = _level_tables(ref_maps, what)
-    return ct, cs, rt, rs, ft, fs, pix, sum(pix)
-
-
 def vfnet_quality(reg_maps, ref_maps, anchors, gts, assigned):
     """htd_vfnet_quality: per positive of `assigned` (B, A) (atss_targets) the IoU of its initial and of its refined box with its
     gt, clamped to at least 1e-6, 0 elsewhere: the box weights, the varifocal targets and, with the number of positives, the three
     averaging factors of VFNetHead.loss.  -> iou_ini (B, A), iou_rf (B, A), sums (3,) = [positives, sum iou_ini, sum iou_rf];
     nothing read back."""
-    _, _, rt, rs, ft, fs, sizes, A = _vfnet_tables(None, reg_maps, ref_maps, 'vfnet_quality')
+    (_, (rt, rs), (ft, fs)), sizes, A = _point_tables('vfnet_quality', (None, reg_maps, ref_maps), (None, 4, 4))
     B, L = reg_maps[0].size(0), len(reg_maps)
     if assigned.shape != (B, A) or assigned.dtype != torch.int32 or anchors.shape != (A, 4) or gts.dim() != 3 or gts.size(0) != B:
         raise ValueError(f'vfnet_quality: assigned must be int32 of shape {(B, A)}, anchors float32 {(A, 4)}, gts (B, K, 4)')
@@ -1741,38 +1707,19 @@ class VfnetLossFunction(Function):
     @staticmethod
     def forward(ctx, sizes, C, anchors, gts, gt_labels, assigned, iou_ini, iou_rf, sums, box_kind, eps_ini, ref_kind, eps_rf,
                 alpha, gamma, iou_weighted, cls_weight, box_weight, ref_weight, *maps):
-        L = len(maps) // 3
-        cls, reg, ref = maps[:L], maps[L:2 * L], maps[2 * L:]
         B, K = gt_labels.shape
-        ct, cs, _ = _level_tables(cls, 'vfnet_loss')
-        rt, rs, _ = _level_tables(reg, 'vfnet_loss')
-        ft, fs, _ = _level_tables(ref, 'vfnet_loss')
-        gcls, gct = _grad_maps(cls, cs, 'vfnet_loss')
-        greg, grt = _grad_maps(reg, rs, 'vfnet_loss')
-        gref, gft = _grad_maps(ref, fs, 'vfnet_loss')
-        rows = capi.lib().htd_vfnet_loss_partial_rows()
-        partial = torch.empty(rows, 2, device=assigned.device, dtype=torch.float32)
-        capi.call('htd_vfnet_loss', ct, cs, rt, rs, ft, fs, sizes, L, B, int(C), _P(anchors), _P(gts), _P(gt_labels), K, _P(assigned),
-                  _P(iou_ini), _P(iou_rf), _P(sums), int(box_kind), float(eps_ini), int(ref_kind), float(eps_rf), float(alpha),
-                  float(gamma), int(bool(iou_weighted)), float(cls_weight), float(box_weight), float(ref_weight), _P(partial), gct,
-                  grt, gft, _S())
-        ctx.meta = (sizes, L, B, int(C))
-        ctx.save_for_backward(*gcls, *greg, *gref)
-        tot = partial.view(2, rows // 2, 2).sum(1)              # [[vfl, initial box], [refined box, 0]]
+        ctx.meta = (sizes, len(maps) // 3, B, int(C))
+        tot = _point_loss_forward(ctx, 'vfnet_loss', 'htd_vfnet_loss', 3, maps,
+                                  (*ctx.meta, _P(anchors), _P(gts), _P(gt_labels), K, _P(assigned), _P(iou_ini), _P(iou_rf), _P(sums),
+                                   int(box_kind), float(eps_ini), int(ref_kind), float(eps_rf), float(alpha), float(gamma),
+                                   int(bool(iou_weighted)), float(cls_weight), float(box_weight), float(ref_weight)))
         norm = sums.clamp(min=1.0)                              # vfnet_head.py:396,414,430: each factor at least 1
         return tot[0, 0] / norm[0] * cls_weight, tot[0, 1] / norm[1] * box_weight, tot[1, 0] / norm[2] * ref_weight
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g_cls, g_box, g_ref):
-        sizes, L, B, C = ctx.meta
-        grads = ctx.saved_tensors
-        gct, gcs, _ = _level_tables(grads[:L], 'vfnet_loss')
-        grt, grs, _ = _level_tables(grads[L:2 * L], 'vfnet_loss')
-        gft, gfs, _ = _level_tables(grads[2 * L:], 'vfnet_loss')
-        _hand_over_once(ctx, 'vfnet_loss', 'htd_vfnet_grad_scale', (gct, gcs, grt, grs, gft, gfs, sizes, L, B, C),
-                        (g_cls, g_box, g_ref))
-        return (None, ) * 19 + tuple(grads)
+        return (None, ) * 19 + _point_loss_backward(ctx, 'vfnet_loss', 'htd_vfnet_grad_scale', ctx.meta, (g_cls, g_box, g_ref))
 
 
 def vfnet_loss(cls_maps, reg_maps, ref_maps, anchors, gts, gt_labels, assigned, iou_ini, iou_rf, sums, box_kind, ref_kind,
@@ -1780,7 +1727,7 @@ def vfnet_loss(cls_maps, reg_maps, ref_maps, anchors, gts, gt_labels, assigned, 
     """-> (loss_cls, loss_bbox, loss_bbox_rf) of a VFNet head from its per-level (B, C, h, w) / (B, 4, h, w) / (B, 4, h, w) maps,
     the (A, 4) anchors, the padded gts, `assigned` of atss_targets and the outputs of vfnet_quality.  box_kind / ref_kind:
     FCOS_BOX_KINDS[type of the box loss]."""
-    *_, sizes, A = _vfnet_tables(cls_maps, reg_maps, ref_maps, 'vfnet_loss')
+    _, sizes, A = _point_tables('vfnet_loss', (cls_maps, reg_maps, ref_maps), (None, 4, 4))
     B = cls_maps[0].size(0)
     if assigned.shape != (B, A) or assigned.dtype != torch.int32 or anchors.shape != (A, 4) or iou_ini.shape != (B, A) or \
             iou_rf.shape != (B, A) or gt_labels.dtype != torch.int64 or sums.shape != (3, ):

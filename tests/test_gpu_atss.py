@@ -314,7 +314,7 @@ def _tensor_runs(head, cls_maps, reg_maps, ctr_maps, gts, labels, metas):
 def _fused_run(head, maps, gts, labels, metas, scale=1.0):
     ls = head.loss(*maps, gts, labels, metas)
     ls = torch.stack([ls['loss_cls'], ls['loss_bbox'], ls['loss_centerness']])
-    (ls * scale).sum().backward()
+    (ls * ls.new_tensor(scale)).sum().backward()            # scale: one factor, or one per loss
     return ls.detach().cpu().double()
 
 
@@ -353,7 +353,8 @@ def test_fused_head_loss_against_the_tensor_path_with_padded_channels(v):
 
 def test_fused_head_loss_without_positives_and_with_incoming_gradients():
     """No gt anywhere: the box and centerness losses and their gradients are exactly 0, the focal loss is averaged over the number
-    of images.  Incoming gradients of 2 double every gradient map exactly; a second backward through the same forward raises."""
+    of images.  Incoming gradients of 2, 3 and 5 on the three losses scale each kind of gradient map by its own factor exactly; a
+    second backward through the same forward raises."""
     dev = torch.device(DEV)
     _, metas, gts, labels = inputs(dev)
     head = _head_on_device('giou')
@@ -368,13 +369,15 @@ def test_fused_head_loss_without_positives_and_with_incoming_gradients():
     r64, r32 = ref[torch.float64][0][0].reshape(1), ref[torch.float32][0][0].reshape(1)
     assert _err(ls[0].reshape(1), r64) <= _bound(_err(r32, r64), r64)
     out = {}
-    for scale in (1.0, 2.0):
+    for scale in (1.0, (2.0, 3.0, 5.0)):
         maps = fresh()
         _fused_run(head, maps, gts, labels, metas, scale)
-        out[scale] = [m.grad.clone() for ms in maps for m in ms]
-    assert any(float(x.abs().max()) > 0 for x in out[1.0][5:])
-    for a, b in zip(out[1.0], out[2.0]):
-        assert torch.equal(a * 2.0, b)
+        out[scale] = [[m.grad.clone() for m in ms] for ms in maps]
+    ones, scaled = out.values()
+    assert all(any(float(x.abs().max()) > 0 for x in xs) for xs in ones)
+    for xs, ys, f in zip(ones, scaled, (2.0, 3.0, 5.0)):     # each kind of map with its own factor
+        for a, b in zip(xs, ys):
+            assert torch.equal(a * f, b)
     maps = fresh()
     ls = head.loss(*maps, gts, labels, metas)
     total = ls['loss_cls'] + ls['loss_bbox'] + ls['loss_centerness']

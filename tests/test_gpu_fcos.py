@@ -280,17 +280,19 @@ def test_loss_surface_scales_incoming_gradients_and_refuses_a_second_backward():
     n = int((tg[1] > 0).sum())
     norm = torch.tensor([n + 2, max(n, 1), float(tg[3][tg[1] > 0].double().sum())], dtype=torch.float32, device=dev)
     out = {}
-    for scale in (1.0, 2.0):
+    for scale in ((1.0, 1.0, 1.0), (2.0, 3.0, 5.0)):        # one factor per loss: a swap of two factors or widths would show
         maps = [[m[:, :c].to(dev).contiguous(memory_format=CL).requires_grad_() for m in case['maps'][k]]
                 for k, c in (('cls', 80), ('reg', 4), ('ctr', 1))]
         ls = M.fcos_loss(*maps, case['strides'], tg[0], tg[1], tg[2], tg[3], norm, M.FCOS_BOX_KINDS['IoULoss'])
-        total = scale * ls[0] + scale * ls[1] + scale * ls[2]
+        total = scale[0] * ls[0] + scale[1] * ls[1] + scale[2] * ls[2]
         total.backward(retain_graph=True)
-        out[scale] = [m.grad.clone() for ms in maps for m in ms]
-        assert all(torch.isfinite(x).all() for x in out[scale])
-    assert any(float(x.abs().max()) > 0 for x in out[1.0][5:])
-    for a, b in zip(out[1.0], out[2.0]):
-        assert torch.equal(a * 2.0, b)
+        out[scale] = [[m.grad.clone() for m in ms] for ms in maps]
+        assert all(torch.isfinite(x).all() for xs in out[scale] for x in xs)
+    ones, scaled = out.values()
+    assert all(any(float(x.abs().max()) > 0 for x in xs) for xs in ones)
+    for xs, ys, f in zip(ones, scaled, (2.0, 3.0, 5.0)):     # each kind of map with its own factor
+        for a, b in zip(xs, ys):
+            assert torch.equal(a * f, b)
     with pytest.raises(RuntimeError, match='second backward'):
         total.backward()
 

@@ -82,17 +82,23 @@ def reborn(ptr, shape):
     pytest.fail(f'precondition not met: the allocator never handed out the freed address again ({len(misses)} allocations)')
 
 
-def hole(shape=ODD_SHAPE, n=24):
+def hole(shape=ODD_SHAPE, n=24, most=480):
     """-> (address, guards): a FREE block of exactly this tensor's size between two live tensors (so it cannot merge with a free
-    neighbour), and the only free block of its size: the n allocations fill every older one first."""
-    vs = [victim(shape) for _ in range(n)]
-    step = (vs[0].numel() * 4 + 511) // 512 * 512
-    for i in range(1, n - 1):
-        if vs[i].data_ptr() - vs[i - 1].data_ptr() == step and vs[i + 1].data_ptr() - vs[i].data_ptr() == step:
-            ptr = vs[i].data_ptr()
-            vs[i] = None
-            return ptr, vs
-    pytest.fail('precondition not met: no three adjacent blocks among the allocations')
+    neighbour), and the only free block of its size: the allocations fill every older one first.  n at a time, until three
+    lie side by side: where the earlier tests of a run left the pool with many free blocks of about this size, each of the first
+    allocations lands in a block of its own, and only the ones after them are cut from one larger block in a row."""
+    vs, first = [], 1
+    while len(vs) < most:
+        vs += [victim(shape) for _ in range(n)]
+        step = (vs[0].numel() * 4 + 511) // 512 * 512
+        for i in range(first, len(vs) - 1):
+            if vs[i].data_ptr() - vs[i - 1].data_ptr() == step and vs[i + 1].data_ptr() - vs[i].data_ptr() == step:
+                print(f'hole: three adjacent blocks after {len(vs)} allocations')
+                ptr = vs[i].data_ptr()
+                vs[i] = None
+                return ptr, vs
+        first = len(vs) - 1
+    pytest.fail(f'precondition not met: no three adjacent blocks among {len(vs)} allocations')
 
 
 class Slot:

@@ -59,7 +59,8 @@ def bench_kernel(dev, reps, warmup, batch):
     weight, score, wsum = M.gfl_quality(cls, reg, strides, R, anchors, gts, assigned)
     B, A = assigned.shape
     K = gts.size(1)
-    ct, cs, rt, rs, lv, st, _ = M._gfl_tables(cls, reg, strides, R, 'bench_gfl')
+    ((ct, cs), (rt, rs)), lv, _ = M._point_tables('bench_gfl', (cls, reg), (None, 4 * (R + 1)))
+    st = M._fcos_levels(SIZES, strides)[1]
     ws = torch.empty(capi.lib().htd_gfl_quality_workspace_bytes(B, A) // 8, dtype=torch.float64, device=dev)
     stream = capi.current_stream_ptr()
     gts = gts.float().contiguous()

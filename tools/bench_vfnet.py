@@ -61,7 +61,7 @@ def bench_kernel(dev, reps, warmup, batch):
     iou_ini, iou_rf, sums = M.vfnet_quality(reg, ref, anchors, gts, assigned)
     B, A = assigned.shape
     K = gts.size(1)
-    ct, cs, rt, rs, ft, fs, lv, _ = M._vfnet_tables(cls, reg, ref, 'bench_vfnet')
+    ((ct, cs), (rt, rs), (ft, fs)), lv, _ = M._point_tables('bench_vfnet', (cls, reg, ref), (None, 4, 4))
     ws = torch.empty(capi.lib().htd_vfnet_quality_workspace_bytes(B, A) // 8, dtype=torch.float64, device=dev)
     stream = capi.current_stream_ptr()
     gts = gts.float().contiguous()
