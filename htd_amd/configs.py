@@ -10,7 +10,7 @@ retinanet_r50_fpn_1x_coco.py), its GHM variant retinanet_ghm_config (configs/ghm
 fcos_config (the two configs/fcos/fcos_*_r50_caffe_fpn_gn-head_4x4_1x_coco.py), atss_config (configs/atss/
 atss_r50_fpn_1x_coco.py and its R101 sibling), gfl_config (configs/gfl/gfl_r50_fpn_1x_coco.py and the mstrain 2x schedule
 of gfl_r101_fpn_mstrain_2x_coco.py) and vfnet_config (configs/vfnet/vfnet_r50_fpn_1x_coco.py and the mstrain 2x schedule of
-vfnet_r101_fpn_mstrain_2x_coco.py).
+vfnet_r101_fpn_mstrain_2x_coco.py) and fovea_config (the eight configs/foveabox/fovea_*_4x4_*_coco.py).
 """
 import copy
 
@@ -354,6 +354,49 @@ def vfnet_config(depth=50, mstrain=False):
     return cfg
 
 
+def fovea_model(depth=50, align=False):
+    """configs/foveabox/fovea_r50_fpn_4x4_1x_coco.py: RetinaNet's backbone and neck under a FoveaHead -- focal loss with gamma 1.5
+    and alpha 0.4, SmoothL1Loss (beta 0.11) on log distances, scale ranges of two octaves around each level's base edge.  align:
+    the fovea_align_*_gn-head configs -- the classification tower behind a FeatureAlign of 4 deformable groups, GroupNorm(32)."""
+    head = dict(type='FoveaHead', num_classes=80, in_channels=256, stacked_convs=4, feat_channels=256, strides=[8, 16, 32, 64, 128],
+                base_edge_list=[16, 32, 64, 128, 256], scale_ranges=((1, 64), (32, 128), (64, 256), (128, 512), (256, 2048)),
+                sigma=0.4, with_deform=bool(align),
+                loss_cls=dict(type='FocalLoss', use_sigmoid=True, gamma=1.50, alpha=0.4, loss_weight=1.0),
+                loss_bbox=dict(type='SmoothL1Loss', beta=0.11, loss_weight=1.0))
+    if align:
+        head['norm_cfg'] = dict(type='GN', num_groups=32, requires_grad=True)
+    return dict(
+        type='FOVEA', pretrained=f'torchvision://resnet{depth}', backbone=htd_model(depth)['backbone'],
+        neck=dict(type='FPN', in_channels=[256, 512, 1024, 2048], out_channels=256, start_level=1, num_outs=5,
+                  add_extra_convs='on_input'),
+        bbox_head=head)
+
+
+def fovea_config(depth=50, align=False, mstrain=False, schedule='1x'):
+    """fovea[_align]_r{depth}_fpn[_gn-head][_mstrain_640-800]_4x4_{schedule}_coco: an empty train_cfg (the head needs no assigner),
+    lr 0.01 and the linear warm-up of schedule_1x; '2x' trains 24 epochs with steps at 16 / 22; mstrain (2x only) draws the
+    short side from {640, 800} (Resize in `value` mode).  fovea_align_r50_fpn_gn-head_4x4_2x_coco alone clips gradients at norm
+    35, as the reference's file does (`python -m htd_amd.train` refuses grad_clip: apis.check_supported)."""
+    if schedule not in ('1x', '2x'):
+        raise ValueError(f"fovea_config: schedule must be '1x' or '2x', got {schedule!r}")
+    if mstrain and schedule != '2x':
+        raise ValueError('fovea_config: the multi-scale configs train the 2x schedule')
+    cfg = _baseline_config(fovea_model(depth, align), dict(), depth)
+    cfg.test_cfg = ConfigDict(nms_pre=1000, score_thr=0.05, nms=dict(type='nms', iou_threshold=0.5), max_per_img=100)
+    cfg.optimizer.lr = 0.01
+    if schedule == '2x':
+        cfg.lr_config.step = [16, 22]
+        cfg.total_epochs = 24
+    if align and depth == 50 and schedule == '2x' and not mstrain:
+        cfg.optimizer_config = ConfigDict(grad_clip=dict(max_norm=35, norm_type=2))
+    if mstrain:
+        resize = cfg.data.train.pipeline[2]
+        assert resize['type'] == 'Resize'
+        cfg.data.train.pipeline[2] = ConfigDict(type='Resize', img_scale=[(1333, 640), (1333, 800)], multiscale_mode='value',
+                                                keep_ratio=True)
+    return cfg
+
+
 IMG_NORM_CFG = dict(mean=[123.675, 116.28, 103.53], std=[58.395, 57.12, 57.375], to_rgb=True)
 
 
@@ -492,3 +535,9 @@ def build_retinanet_detector(depth=50, cfg=None, bf16=False):
 def build_retinanet_ghm_detector(depth=50, cfg=None, bf16=False):
     """The detector of retinanet_ghm_config(depth) (or of `cfg`); build_retinanet_detector with that config gives the same."""
     return build_baseline_detector(cfg=retinanet_ghm_config(depth) if cfg is None else cfg, bf16=bf16)
+
+
+def build_fovea_detector(depth=50, align=False, cfg=None, bf16=False):
+    """The detector of fovea_config(depth, align) (or of `cfg`), built like the other single-stage baselines: the `pretrained`
+    URL of the reference's config dropped.  (The head's towers stay fp32 under bf16, as every dense head's do.)"""
+    return build_baseline_detector(cfg=fovea_config(depth, align) if cfg is None else cfg, bf16=bf16)

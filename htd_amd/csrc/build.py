@@ -20,7 +20,8 @@ EXTRA = {'nms.hip': ['-ffp-contract=off'], 'box_ops.hip': ['-ffp-contract=off'],
          'ghm_loss.hip': ['-ffp-contract=off'],     # its two passes must bin an element alike
          'atss.hip': ['-ffp-contract=off'],         # distances and IoUs one rounded operation at a time
          'gfl.hip': ['-ffp-contract=off'],          # centres, targets and IoU scores in the reference's fp32 order
-         'vfnet.hip': ['-ffp-contract=off']}        # star offsets, target distances and both IoUs in that order too
+         'vfnet.hip': ['-ffp-contract=off'],        # star offsets, target distances and both IoUs in that order too
+         'fovea.hip': ['-ffp-contract=off']}        # the fovea rectangles one rounded operation at a time; offsets in channel order
 
 
 # Every *.hip / *.cpp of this directory is a translation unit of the library; what each one replaces (include/htd_amd.h cites
@@ -36,11 +37,14 @@ EXTRA = {'nms.hip': ['-ffp-contract=off'], 'box_ops.hip': ['-ffp-contract=off'],
 #                    (dense_heads/gfl_head.py:209-369,420-428, losses/gfocal_loss.py:8-74)
 #   vfnet.hip        VFNetHead's star offsets with their backward, quality pass and loss (varifocal loss, two IoU-weighted
 #                    IoU / GIoU losses) (dense_heads/vfnet_head.py:246-314,317-463, losses/varifocal_loss.py:8-53)
-# The six share focal_elem.h (the element arithmetic) and loss_units.h (level search, VEC-wide units, matrix units).  The last
-# four, the heads with one prediction per location, share point_maps.h (their map table and its checker, the loss grid and the
+#   fovea.hip        FoveaHead's fovea-rectangle targets and loss (focal, smooth-L1 on log distances) and FeatureAlign's offsets
+#                    with their backward (dense_heads/fovea_head.py:13-39,127-258)
+# The seven share focal_elem.h (the element arithmetic) and loss_units.h (level search, VEC-wide units, matrix units).  The last
+# five, the heads with one prediction per location, share point_maps.h (their map table and its checker, the loss grid and the
 # float4 / lane-group decision, the decoding of a pixel row, the classification sweep of their loss kernels), point_scale.h
-# (the kernel behind htd_fcos_grad_scale and htd_vfnet_grad_scale) and, but for FCOS, anchor_levels.h (the level table of
-# htd_atss_targets' anchors, the box load, the reference's fp32 IoU): each of the four files holds only what its head alone does.
+# (the kernel behind htd_fcos_grad_scale, htd_vfnet_grad_scale and htd_fovea_grad_scale) and, but for FCOS and FoveaBox,
+# anchor_levels.h (the level table of htd_atss_targets' anchors, the box load, the reference's fp32 IoU): each of the five files
+# holds only what its head alone does.
 def sources():
     return sorted(f for f in os.listdir(HERE) if f.endswith('.hip') or f.endswith('.cpp'))
 

@@ -1,5 +1,6 @@
 // The kernel that scales the finished gradient maps of a head with one prediction per location by incoming gradients, and its
-// host side: htd_fcos_grad_scale (FCOS and ATSS: widths C, 4, 1) and htd_vfnet_grad_scale (C, 4, 4) are two prologues onto it.
+// host side: htd_fcos_grad_scale (FCOS and ATSS: widths C, 4, 1), htd_vfnet_grad_scale (C, 4, 4) and htd_fovea_grad_scale (C, 4
+// and no third map: W2 = 0, whose slot and factor are then never touched) are three prologues onto it.
 #pragma once
 #include "point_maps.h"
 
@@ -12,7 +13,7 @@ template <int W1, int W2>
 __global__ __launch_bounds__(256) void point_scale_kernel(PointMaps mp, int L, int w0, const float *__restrict__ g0,
                                                           const float *__restrict__ g1, const float *__restrict__ g2)
 {
-    const float f0 = *g0, f1 = *g1, f2 = *g2;
+    const float f0 = *g0, f1 = *g1, f2 = W2 > 0 ? *g2 : 1.f;
     const unsigned n_rows = mp.rrow[L];
     const unsigned lane = threadIdx.x & 63u;
     const unsigned wave = __builtin_amdgcn_readfirstlane(blockIdx.x * 4u + (threadIdx.x >> 6));
@@ -28,12 +29,12 @@ __global__ __launch_bounds__(256) void point_scale_kernel(PointMaps mp, int L, i
             const int l = level_of(mp.rrow, L, rw);
             const unsigned row = rw - mp.rrow[l];
             float *a = mp.grad[1][l] + (int64_t)row * mp.cs[1][l];
-            float *b = mp.grad[2][l] + (int64_t)row * mp.cs[2][l];
             if (f1 != 1.f) {
 #pragma unroll
                 for (int k = 0; k < W1; ++k) a[k] *= f1;
             }
-            if (f2 != 1.f) {
+            if (W2 > 0 && f2 != 1.f) {
+                float *b = mp.grad[2][l] + (int64_t)row * mp.cs[2][l];
 #pragma unroll
                 for (int k = 0; k < W2; ++k) b[k] *= f2;
             }
@@ -47,9 +48,9 @@ int point_grad_scale(const char *what, const unsigned *off, int L, int B, float 
                      float *const *grad1, const int64_t *stride1, float *const *grad2, const int64_t *stride2, const float *g0,
                      const float *g1, const float *g2, void *stream)
 {
-    HTD_REQUIRE(g0 && g1 && g2, "%s: null pointer", what);
+    HTD_REQUIRE(g0 && g1 && (g2 || W2 == 0), "%s: null pointer", what);
     const PointSlot slots[POINT_SLOTS] = {{nullptr, grad0, stride0, C, false, true}, {nullptr, grad1, stride1, W1, false, true},
-                                          {nullptr, grad2, stride2, W2, false, true}};
+                                          W2 > 0 ? PointSlot{nullptr, grad2, stride2, W2, false, true} : PointSlot{}};
     PointMaps mp = {};
     const int rc = fill_point_maps(mp, what, off, L, B, slots, 1);
     if (rc != HTD_OK) return rc;

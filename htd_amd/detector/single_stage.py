@@ -1,8 +1,8 @@
-"""SingleStageDetector, RetinaNet, FCOS, ATSS, GFL and VFNet.
+"""SingleStageDetector, RetinaNet, FCOS, ATSS, GFL, VFNet and FOVEA.
 
 Reference: detectors/single_stage.py:9-149 (extract_feat :52-57, forward_train :68-96, simple_test :98-124),
-detectors/retinanet.py:5-17, detectors/fcos.py:5-17, detectors/atss.py:5-17, detectors/gfl.py:5-16, detectors/vfnet.py:5-16.  The dense head does the work
-(detector/anchor_heads.py, anchor_free_heads.py, vfnet_head.py); results of a batch leave the device in one copy (core.bbox.bbox2result_many).
+detectors/retinanet.py:5-17, detectors/fcos.py:5-17, detectors/atss.py:5-17, detectors/gfl.py:5-16, detectors/vfnet.py:5-16, detectors/fovea.py:5-17.  The dense head does the work
+(detector/anchor_heads.py, anchor_free_heads.py, vfnet_head.py, fovea_head.py); results of a batch leave the device in one copy (core.bbox.bbox2result_many).
 """
 from ..core.bbox import bbox2result_many
 from ..registry import DETECTORS, build_backbone, build_head, build_neck
@@ -84,6 +84,14 @@ class GFL(SingleStageDetector):
 @DETECTORS.register_module()
 class VFNet(SingleStageDetector):
     """detectors/vfnet.py:5-16."""
+
+    def __init__(self, backbone, neck, bbox_head, train_cfg=None, test_cfg=None, pretrained=None):
+        super().__init__(backbone, neck, bbox_head, train_cfg, test_cfg, pretrained)
+
+
+@DETECTORS.register_module()
+class FOVEA(SingleStageDetector):
+    """detectors/fovea.py:5-17."""
 
     def __init__(self, backbone, neck, bbox_head, train_cfg=None, test_cfg=None, pretrained=None):
         super().__init__(backbone, neck, bbox_head, train_cfg, test_cfg, pretrained)

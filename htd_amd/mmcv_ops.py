@@ -1738,3 +1738,116 @@ def vfnet_loss(cls_maps, reg_maps, ref_maps, anchors, gts, gt_labels, assigned, 
                                    _f32(iou_ini, 'vfnet_loss').contiguous(), _f32(iou_rf, 'vfnet_loss').contiguous(),
                                    _f32(sums, 'vfnet_loss').contiguous(), box_kind, eps_ini, ref_kind, eps_rf, alpha, gamma,
                                    iou_weighted, cls_weight, box_weight, ref_weight, *cls_maps, *reg_maps, *ref_maps)
+
+
+# ====================================================================== FoveaBox head (dense_heads/fovea_head.py)
+def fovea_targets(featmap_sizes, strides, base_edge_list, scale_ranges, sigma, gts, gt_valid):
+    """htd_fovea_targets: FoveaHead.get_targets of the whole batch in one launch (+ a finishing one).  gts (B, K, 4) float32 /
+    gt_valid (B, K) bool as pad_gt_batch leaves them (K = 0 allowed).  -> assigned (B, P) int32 (0 background, k + 1 = gt k),
+    bbox_targets (B, P, 4) (log distances, 0 on background), num_pos (B,) int32, norm (2,) = [sum num_pos + B, max(sum num_pos,
+    1)]; points level-major, nothing read back to the host."""
+    _need_gpu(gts, 'fovea_targets')
+    gts = _f32(gts, 'fovea_targets').contiguous()
+    gt_valid = gt_valid.to(torch.bool).contiguous()
+    B, K = gt_valid.shape
+    if gts.shape != (B, K, 4):
+        raise ValueError(f'fovea_targets: gts must be {(B, K, 4)}, got {tuple(gts.shape)}')
+    hw, st, P = _fcos_levels(featmap_sizes, strides)
+    if len(base_edge_list) != len(st) or len(scale_ranges) != len(st):
+        raise ValueError(f'fovea_targets: {len(base_edge_list)} base edges and {len(scale_ranges)} scale ranges for {len(st)} levels')
+    bases = (ctypes.c_float * len(st))(*[float(v) for v in base_edge_list])
+    ranges = (ctypes.c_float * (2 * len(st)))(*[float(v) for r in scale_ranges for v in r])
+    dev = gts.device
+    assigned = torch.empty(B, P, dtype=torch.int32, device=dev)
+    bbox_targets = torch.empty(B, P, 4, dtype=torch.float32, device=dev)
+    num_pos = torch.empty(B, dtype=torch.int32, device=dev)
+    norm = torch.empty(2, dtype=torch.float32, device=dev)
+    ws = torch.empty(capi.lib().htd_fovea_targets_workspace_bytes(B, P) // 4, dtype=torch.int32, device=dev)
+    capi.call('htd_fovea_targets', hw, st, bases, ranges, len(st), float(sigma), _P(gts) if K else None, _P(gt_valid) if K else None,
+              B, K, _P(assigned), _P(bbox_targets), _P(ws), _P(num_pos), _P(norm), _S())
+    return assigned, bbox_targets, num_pos, norm
+
+
+class FoveaLossFunction(Function):
+    """htd_fovea_loss: the two losses of FoveaHead.loss over every level and image in one launch, which also writes the two
+    finished gradient maps (loss weight and normaliser applied); backward hands them over, after htd_fovea_grad_scale applies
+    incoming gradients other than 1 on the device, in place.  Single use: a second backward through the same forward raises."""
+
+    @staticmethod
+    def forward(ctx, sizes, C, gt_labels, assigned, bbox_targets, norm, beta, gamma, alpha, cls_weight, box_weight, *maps):
+        B, K = gt_labels.shape
+        ctx.meta = (sizes, len(maps) // 2, B, int(C))
+        sums = _point_loss_forward(ctx, 'fovea_loss', 'htd_fovea_loss', 2, maps,
+                                   (*ctx.meta, _P(gt_labels) if K else None, K, _P(assigned), _P(bbox_targets), _P(norm), float(beta),
+                                    float(gamma), float(alpha), float(cls_weight), float(box_weight))).sum(0)    # [focal, smooth-L1]
+        return sums[0] / norm[0] * cls_weight, sums[1] / norm[1] * box_weight
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_cls, g_box):
+        return (None, ) * 11 + _point_loss_backward(ctx, 'fovea_loss', 'htd_fovea_grad_scale', ctx.meta, (g_cls, g_box))
+
+
+def fovea_loss(cls_maps, reg_maps, gt_labels, assigned, bbox_targets, norm, beta=1.0, gamma=2.0, alpha=0.25, cls_weight=1.0,
+               box_weight=1.0):
+    """-> (loss_cls, loss_bbox) of a FoveaBox head from its per-level (B, C, h, w) / (B, 4, h, w) maps and the outputs of
+    fovea_targets; beta is the SmoothL1Loss's."""
+    _, sizes, P = _point_tables('fovea_loss', (cls_maps, reg_maps), (None, 4))
+    B = cls_maps[0].size(0)
+    if assigned.shape != (B, P) or assigned.dtype != torch.int32 or bbox_targets.shape != (B, P, 4) or \
+            gt_labels.dtype != torch.int64 or gt_labels.dim() != 2 or gt_labels.size(0) != B or norm.shape != (2, ):
+        raise ValueError(f'fovea_loss: assigned must be int32 of shape {(B, P)}, bbox_targets float32 {(B, P, 4)}, gt_labels int64 '
+                         f'(B, K), norm float32 (2,)')
+    return FoveaLossFunction.apply(sizes, cls_maps[0].size(1), gt_labels.contiguous(), assigned.contiguous(),
+                                   _f32(bbox_targets, 'fovea_loss').contiguous(), _f32(norm, 'fovea_loss').contiguous(), beta, gamma,
+                                   alpha, cls_weight, box_weight, *cls_maps, *reg_maps)
+
+
+class FoveaAlignFunction(Function):
+    """htd_fovea_align_fwd / _bwd: the four regression logits x (B, 4, H, W) of one level and conv_offset's weight (O, 4, 1, 1) ->
+    the offsets conv_offset(exp(x)) (B, O, H, W) of FeatureAlign in one launch; backward gives the logits' and the weight's
+    gradients in one more (+ a finishing one), bitwise reproducible."""
+
+    @staticmethod
+    def forward(ctx, x, weight):
+        B, _, H, W = x.shape
+        xs = nhwc_channel_stride(x)
+        if xs is None:
+            x = x.contiguous(memory_format=CL)
+            xs = nhwc_channel_stride(x)
+        O = weight.size(0)
+        w = weight.detach().reshape(O, 4).contiguous()
+        off = torch.empty(B, O, H, W, device=x.device, dtype=torch.float32, memory_format=CL)
+        capi.call('htd_fovea_align_fwd', _P(x), xs, _P(w), B, H, W, O // 18, _P(off), O, _S())
+        ctx.meta = (B, H, W, xs, O)
+        ctx.save_for_backward(x, w)
+        return off
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_off):
+        B, H, W, xs, O = ctx.meta
+        x, w = ctx.saved_tensors
+        g_off = g_off.float()
+        gs = nhwc_channel_stride(g_off)
+        if gs is None:
+            g_off = g_off.contiguous(memory_format=CL)
+            gs = nhwc_channel_stride(g_off)
+        gx = _like_padded(x, xs)
+        gw = torch.empty(O, 4, 1, 1, device=x.device, dtype=torch.float32)
+        ws = torch.empty(capi.lib().htd_fovea_align_bwd_workspace_bytes(B, H, W, O // 18) // 4, device=x.device, dtype=torch.float32)
+        capi.call('htd_fovea_align_bwd', _P(x), xs, _P(w), _P(g_off), gs, B, H, W, O // 18, _P(gx), xs, _P(gw), _P(ws), _S())
+        return gx, gw
+
+
+def fovea_align(x, weight):
+    """-> conv_offset(exp(x)) (B, O, H, W), channels_last, of the regression logits x (B, 4, H, W) of one level (fp32, GPU) under
+    the bias-free 1 x 1 weight (O, 4, 1, 1), O = deform_groups * 18 with 1 to 8 deformable groups."""
+    _need_gpu(x, 'fovea_align')
+    _f32(x, 'fovea_align')
+    _f32(weight, 'fovea_align')
+    if x.dim() != 4 or x.size(1) != 4 or weight.dim() != 4 or tuple(weight.shape[1:]) != (4, 1, 1) or weight.size(0) % 18 or \
+            not 1 <= weight.size(0) // 18 <= 8:
+        raise ValueError(f'fovea_align: x must be (B, 4, H, W) and weight (deform_groups * 18, 4, 1, 1) with 1 to 8 groups, got '
+                         f'{tuple(x.shape)} and {tuple(weight.shape)}')
+    return FoveaAlignFunction.apply(x, weight)

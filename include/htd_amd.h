@@ -908,6 +908,59 @@ int htd_vfnet_grad_scale(float *const *grad_cls, const int64_t *cls_stride, floa
                          float *const *grad_ref, const int64_t *ref_stride, const int64_t *level_sizes, int L, int B, int C,
                          const float *g_cls, const float *g_box, const float *g_ref, void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * FoveaBox head (dense_heads/fovea_head.py).  The pyramid is given as HOST tables of L <= 8 levels: hw [L][2] = map height and
+ * width, strides [L], base_edges [L] = base_edge_list, ranges [L][2] = scale_ranges; point p of a level is (x, y) = (p % w + 0.5,
+ * p / w + 0.5) in map units (_get_points_single, fovea_head.py:123-125), computed in the kernels.  P = sum of h * w; points are
+ * level-major.  level_sizes [L] HOST = h * w per level.  Maps are HOST tables of L device pointers to channels_last maps
+ * [B][h * w][channel stride] read in place, as for the FCOS head: classification (C channels) and regression (4 log distances).
+ * ---------------------------------------------------------------------------------- */
+/* FoveaHead.get_targets / _get_target_single (fovea_head.py:177-258) of the whole batch in one launch (+ a finishing one), in
+ * the reference's fp32 arithmetic.  gts [B][K][4] and gt_valid [B][K] padded as pad_gt_batch leaves them (any K >= 0).  gt k lies
+ * on level l when ranges[l][0] <= sqrt(w * h) <= ranges[l][1] (:205-219); its rectangle there is ceil / floor of x1 + (1 -+ sigma)
+ * * half - 0.5 of the gt over the stride, clamped to the map, and holds the points inside it after the clamp (:226-246).  The
+ * reference paints in descending order of sqrt(w * h); a point goes to its last painter: the smallest root, and among equal
+ * roots the highest index (the reference's unstable sort leaves that case open; a stable sort gives this).
+ *   assigned [B][P]        0 = background, k + 1 = gt k
+ *   bbox_targets [B][P][4] log(clamp(((stride * x - x1), (stride * y - y1), (x2 - stride * x), (y2 - stride * y)) / base_edge,
+ *                          1/16, 16)) (:247-257), exactly 0 on background (the reference leaves uninitialised memory there)
+ *   num_pos [B], norm [2] = {sum num_pos + B, max(sum num_pos, 1)}: the averaging factors of FoveaHead.loss (:158-169), left on
+ *                          the device: no host read.
+ * workspace: htd_fovea_targets_workspace_bytes(B, P) bytes, 4-byte aligned.  Every output element is written. */
+int64_t htd_fovea_targets_workspace_bytes(int B, int64_t P);
+int htd_fovea_targets(const int64_t *hw, const int64_t *strides, const float *base_edges, const float *ranges, int L,
+                      double sigma, const float *gts, const uint8_t *gt_valid, int B, int K, int *assigned,
+                      float *bbox_targets, void *workspace, int *num_pos, float *norm, void *stream);
+/* FoveaHead.loss (fovea_head.py:127-175) over all levels in one launch: the focal loss of every point with the label
+ * gt_labels[b][assigned - 1] (background: none) and, per positive point, SmoothL1Loss (losses/smooth_l1_loss.py:9-32, beta > 0)
+ * between the four raw predictions and bbox_targets.
+ * partial [htd_fovea_loss_partial_rows()][2] = per-block {sum focal, sum smooth-L1}, unscaled (add in row order: reproducible).
+ * The gradient maps (layout of their inputs) receive d(cls_weight * focal / norm[0]) and d(box_weight * smooth-L1 / norm[1]);
+ * every element is written exactly once, zeros (padding channels, non-positive points) included.  Without positives the box sum
+ * and its gradient map are exactly 0 (:170-174). */
+int htd_fovea_loss_partial_rows(void);
+int htd_fovea_loss(const float *const *cls, const int64_t *cls_stride, const float *const *reg, const int64_t *reg_stride,
+                   const int64_t *level_sizes, int L, int B, int C, const int64_t *gt_labels, int K, const int *assigned,
+                   const float *bbox_targets, const float *norm, float beta, float gamma, float alpha, float cls_weight,
+                   float box_weight, float *partial, float *const *grad_cls, float *const *grad_reg, void *stream);
+/* The gradient maps of htd_fovea_loss times the incoming gradients *g_cls / *g_box (device scalars), in place; a factor of
+ * exactly 1 leaves its maps untouched, decided on the device. */
+int htd_fovea_grad_scale(float *const *grad_cls, const int64_t *cls_stride, float *const *grad_reg,
+                         const int64_t *reg_stride, const int64_t *level_sizes, int L, int B, int C, const float *g_cls,
+                         const float *g_box, void *stream);
+/* The offsets of FeatureAlign (fovea_head.py:22-23,36-37 with forward_single :117) for one level: offset [B][H][W][offset_stride
+ * >= O], O = deform_groups * 18 (1 <= deform_groups <= 8), offset[o] = sum_c weight[o][c] * exp(x[c]) over the four logits
+ * x [B][H][W][x_stride >= 4], c ascending, unfused; weight [O][4] is conv_offset's.  Padding channels are written as zeros. */
+int htd_fovea_align_fwd(const float *x, int64_t x_stride, const float *weight, int B, int H, int W, int deform_groups,
+                        float *offset, int64_t offset_stride, void *stream);
+/* Its backward: g_x [B][H][W][g_x_stride >= 4] = exp(x[c]) * sum_o weight[o][c] * g_offset[o] (written, zeros on padding) and
+ * g_weight [O][4] = sum over pixels of g_offset[o] * exp(x[c]) in a fixed order (bitwise reproducible).
+ * workspace: htd_fovea_align_bwd_workspace_bytes(B, H, W, deform_groups) bytes, 4-byte aligned. */
+int64_t htd_fovea_align_bwd_workspace_bytes(int B, int H, int W, int deform_groups);
+int htd_fovea_align_bwd(const float *x, int64_t x_stride, const float *weight, const float *g_offset,
+                        int64_t g_offset_stride, int B, int H, int W, int deform_groups, float *g_x, int64_t g_x_stride,
+                        float *g_weight, void *workspace, void *stream);
+
 /* nn.MaxPool2d(kernel, stride, padding) of the ResNet stem (backbones/resnet.py:509,629) on NHWC maps
  * x [B][H][W][C] -> y [B][Ho][Wo][C], C % 4 == 0, padding = -inf, floor mode.  idx (may be NULL for inference; int32
  * [B][Ho][Wo][C]) records the input pixel hi*W+wi of the first maximum of each window; bwd sends the gradient there

@@ -1,0 +1,317 @@
+"""FoveaBox without a GPU: the three configurations against the reference's merged configs, the state dict of both head forms and
+a reference-format checkpoint, get_targets / the tensor-path loss / the per-image get_bboxes / FeatureAlign's offsets against the
+reference's own run (tests/golden/fovea.npz, recipe in tests/golden/make_golden_fovea.py), the rule for equal sizes, and the new
+entry points of the C ABI."""
+import json
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import baselines_util as BU
+import fovea_util as U
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
+EPS32 = 2.0 ** -23
+
+
+def T(a):
+    return torch.from_numpy(np.asarray(a))
+
+
+def _bound(e32, ref):
+    """The project's rule: 4 x max(the reference's own fp32 error, one fp32 ulp of the largest entry)."""
+    return 4.0 * max(float(e32), EPS32 * float(torch.as_tensor(ref).abs().max()))
+
+
+LOG_TOL = 2.0 ** -22     # one fp32 ulp of a value in [2, 4) (|log target| <= log 16 = 2.77): what two CPU logarithms may differ by
+
+
+def targets_from_assignment(assigned, gts, sizes=U.LEVEL_SIZES, strides=U.STRIDES, bases=U.BASE_EDGES):
+    """fovea_head.py:247-257 for a given assignment (B, P), in fp32: every step but the last is one correctly rounded operation
+    (exact on every machine); the logarithm is this machine's, as in the head.  -> (B, P, 4), zeros under the background."""
+    xs, ys, st, be = [], [], [], []
+    for (h, w), s, b in zip(sizes, strides, bases):
+        y, x = torch.meshgrid(torch.arange(h, dtype=torch.float32) + 0.5, torch.arange(w, dtype=torch.float32) + 0.5, indexing='ij')
+        xs.append(s * x.flatten()), ys.append(s * y.flatten())
+        st.append(torch.full((h * w, ), float(s))), be.append(torch.full((h * w, ), float(b)))
+    xs, ys, be = torch.cat(xs), torch.cat(ys), torch.cat(be)
+    out = torch.zeros(*assigned.shape, 4)
+    for b in range(assigned.size(0)):
+        pos = assigned[b] > 0
+        if bool(pos.any()):
+            g = gts[b].float()[assigned[b][pos].long() - 1]
+            x, y, e = xs[pos], ys[pos], be[pos]
+            t = torch.stack([(x - g[:, 0]) / e, (y - g[:, 1]) / e, (g[:, 2] - x) / e, (g[:, 3] - y) / e], -1)
+            out[b][pos] = torch.log(t.clamp(min=1. / 16, max=16.))
+    return out
+
+
+def check_targets(bt, assigned, gts, fixture_bt):
+    """The log targets: bit for bit the logarithm (this machine's) of the exactly computed clamped ratios, within LOG_TOL of the
+    fixture's (another machine's logarithm may differ by an ulp), exactly 0 under the background."""
+    assert torch.equal(bt, targets_from_assignment(assigned, gts))
+    assert float((bt - fixture_bt).abs().max()) <= LOG_TOL
+    assert float(bt[assigned == 0].abs().max()) == 0
+
+
+def build_head(**extra):
+    from htd_amd.registry import build_head as build
+    import htd_amd.detector  # noqa: F401
+    return build(U.head_cfg(**extra))
+
+
+def inputs():
+    _, metas, gts, labels = BU.detector_inputs()
+    return metas, [T(g) for g in gts], [T(l) for l in labels]
+
+
+@pytest.mark.parametrize('which', list(U.CONFIGS))
+def test_fovea_config_equals_the_reference_merged_config(which):
+    from htd_amd.configs import fovea_config
+    ref = json.load(open(os.path.join(GOLDEN, os.path.basename(U.CONFIGS[which])[:-3] + '_cfg.json')))
+    cfg = fovea_config(**U.CONFIG_ARGS[which])
+    mine = {k: (cfg[k].to_dict() if hasattr(cfg[k], 'to_dict') else cfg[k]) for k in U.CFG_KEYS}
+    mine['train_pipeline'] = [p.to_dict() if hasattr(p, 'to_dict') else p for p in cfg.data.train.pipeline]
+    assert json.loads(json.dumps(mine)) == ref
+    assert ref['model']['type'] == 'FOVEA' and ref['model']['bbox_head']['type'] == 'FoveaHead' and ref['train_cfg'] == {}
+    assert ref['model']['bbox_head']['with_deform'] == (which != 'plain')
+    if which == 'align_r101_mstrain':
+        resize = ref['train_pipeline'][2]
+        assert resize['multiscale_mode'] == 'value' and resize['img_scale'] == [[1333, 640], [1333, 800]]
+        assert ref['lr_config']['step'] == [16, 22] and ref['total_epochs'] == 24 and ref['model']['backbone']['depth'] == 101
+    with pytest.raises(ValueError):
+        fovea_config(34)
+    with pytest.raises(ValueError, match='schedule'):
+        fovea_config(50, schedule='3x')
+    with pytest.raises(ValueError, match='2x'):
+        fovea_config(50, mstrain=True)
+
+
+def test_the_plain_configs_pass_check_supported():
+    from htd_amd.apis import check_supported
+    from htd_amd.configs import fovea_config
+    check_supported(fovea_config(50))
+    check_supported(fovea_config(101, align=True, mstrain=True, schedule='2x'))
+    with pytest.raises(NotImplementedError, match='grad_clip'):
+        check_supported(fovea_config(50, align=True, schedule='2x'))
+
+
+@pytest.mark.parametrize('which', U.DETECTOR_CONFIGS)
+def test_state_dict_keys_and_shapes_equal_the_fixture(golden, which):
+    from htd_amd.configs import build_fovea_detector
+    from htd_amd.detector import FOVEA, FeatureAlign, FoveaHead
+    g = golden('fovea')
+    det = build_fovea_detector(50, align=which == 'align')
+    sd = det.state_dict()
+    assert list(sd.keys()) == [str(k) for k in g[which + '.state_keys']]
+    assert [list(v.shape) + [0] * (4 - v.dim()) for v in sd.values()] == g[which + '.state_shapes'].tolist()
+    assert type(det) is FOVEA and type(det.bbox_head) is FoveaHead
+    h = det.bbox_head
+    b = h.conv_cls.bias
+    assert torch.allclose(b.sigmoid(), torch.full_like(b, 0.01))             # bias_init_with_prob(0.01)
+    if which == 'align':
+        fa = h.feature_adaption
+        assert type(fa) is FeatureAlign and fa.conv_offset.bias is None and tuple(fa.conv_offset.weight.shape) == (72, 4, 1, 1)
+        assert fa.conv_adaption.deform_groups == 4 and h.cls_convs[0].conv.bias is None and len(h.cls_convs) == 2
+        assert h.cls_convs[1].conv.kernel_size == (1, 1) and h.conv_cls.in_channels == 1024
+        torch.manual_seed(0)
+        h.init_weights()
+        assert 0.07 < float(fa.conv_offset.weight.detach().std()) < 0.13 and 0.008 < float(fa.conv_adaption.weight.detach().std()) < 0.012
+    else:
+        assert not hasattr(h, 'feature_adaption') and h.cls_convs[0].conv.bias is not None and len(h.cls_convs) == 4
+    from htd_amd.apis import _num_classes
+    assert _num_classes(det) == 80
+
+
+@pytest.mark.parametrize('which', U.DETECTOR_CONFIGS)
+def test_a_reference_format_checkpoint_loads(golden, which, tmp_path):
+    """A checkpoint as the reference writes it (meta + state_dict under the reference's keys) loads strictly."""
+    from htd_amd.checkpoint import load_checkpoint
+    from htd_amd.configs import build_fovea_detector
+    g = golden('fovea')
+    state = U.fixture_state(g[which + '.state_keys'], g[which + '.state_shapes'], float(g[which + '.cls_scale']),
+                            float(g[which + '.cls_bias_shift']))
+    path = str(tmp_path / 'fovea.pth')
+    torch.save(dict(meta=dict(mmdet_version='2.7.0'), state_dict=state), path)
+    det = build_fovea_detector(50, align=which == 'align')
+    load_checkpoint(det, path, strict=True)
+    want = U.load_fixture_weights_(build_fovea_detector(50, align=which == 'align'), float(g[which + '.cls_scale']),
+                                   float(g[which + '.cls_bias_shift'])).state_dict()
+    for k, v in det.state_dict().items():
+        assert torch.equal(v, want[k]), k
+
+
+def test_feature_align_tensor_form_matches_the_reference(golden):
+    from htd_amd.detector import FeatureAlign
+    from golden_util import seeded_tensor
+    g = golden('fovea')
+    fa = FeatureAlign(8, 8, kernel_size=3, deform_groups=4).double()
+    with torch.no_grad():
+        fa.conv_offset.weight.copy_(seeded_tensor('fovea.align.w', (72, 4, 1, 1), scale=0.1).double())
+    x = U.head_maps()[1][1].double().requires_grad_()
+    for off in (fa.offsets(shape=x.exp()), fa.offsets(logits=x)):
+        np.testing.assert_allclose(off.detach().numpy(), g['align.offset'], rtol=1e-12, atol=1e-15)
+    (off * seeded_tensor('fovea.align.g', tuple(off.shape)).double()).sum().backward()
+    np.testing.assert_allclose(x.grad.numpy(), g['align.gx'], rtol=1e-11, atol=1e-15)
+    np.testing.assert_allclose(fa.conv_offset.weight.grad.numpy(), g['align.gw'], rtol=1e-11, atol=1e-15)
+    # the restatement the GPU tests use
+    o2, gx2, gw2 = U.align_ref(x.detach(), fa.conv_offset.weight.detach(), seeded_tensor('fovea.align.g', tuple(off.shape)))
+    np.testing.assert_allclose(o2.numpy(), g['align.offset'], rtol=1e-12, atol=1e-15)
+    np.testing.assert_allclose(gx2.numpy(), g['align.gx'], rtol=1e-11, atol=1e-15)
+    np.testing.assert_allclose(gw2.numpy(), g['align.gw'], rtol=1e-11, atol=1e-15)
+
+
+def test_get_targets_equal_the_reference_on_the_targets_case(golden):
+    """Gts outside the map that still paint its border, an empty rectangle, gt_areas on the bounds of the ranges, nested gts whose
+    size decides against their index, both clamps of the targets, an empty image: the reference's fp32 run exactly, and exactly
+    0 under the background."""
+    g = golden('fovea')
+    gts, _ = U.targets_case()
+    head = build_head(scale_ranges=U.DEFAULT_RANGES)
+    assigned, bt = U.head_targets(head, gts)
+    assert torch.equal(assigned.long(), T(g['tc.assigned']).long())
+    check_targets(bt, assigned, gts, T(g['tc.bbox_targets']))
+    assert int((assigned[1] > 0).sum()) == 0 and int((assigned > 0).sum()) == 31
+    # the raw output of get_targets is exactly 0 (not merely masked) under the background
+    points = head.get_points(U.LEVEL_SIZES, torch.float32, 'cpu')
+    labels, raw = head.get_targets(gts, [torch.arange(len(x)) for x in gts], U.LEVEL_SIZES, points)
+    assert float(raw[labels == head.num_classes].abs().max()) == 0
+    a64, _ = U.head_targets(head, gts, torch.float64)
+    assert torch.equal(a64, assigned)
+
+
+def test_equal_sizes_go_to_the_higher_index():
+    """20 nested gts of equal gt_areas (from 17 elements on torch.sort is not stable unless asked to be): every point goes to the
+    highest index among the gts whose rectangle holds it."""
+    n = 20
+    gts, labels = U.tie_case(n)
+    head = build_head(scale_ranges=U.DEFAULT_RANGES)
+    areas = torch.sqrt((gts[:, 2] - gts[:, 0]) * (gts[:, 3] - gts[:, 1]))
+    assert bool((areas == 64).all())
+    assigned, _ = U.head_targets(head, [gts])
+    at = U.LEVEL_POINTS[0] + 3 * U.LEVEL_SIZES[1][1] + 3
+    assert int(assigned[0, at]) == n
+    # every painted point of level 1: the highest index whose rectangle (worked out here in plain arithmetic) holds it
+    h, w = U.LEVEL_SIZES[1]
+    want = torch.zeros(h, w, dtype=torch.long)
+    for k, (x1, y1, x2, y2) in enumerate((gts / 16).tolist()):
+        hw, hh = 0.5 * (x2 - x1), 0.5 * (y2 - y1)
+        l, r = int(np.ceil(x1 + 0.6 * hw - 0.5)), int(np.floor(x1 + 1.4 * hw - 0.5))
+        t, d = int(np.ceil(y1 + 0.6 * hh - 0.5)), int(np.floor(y1 + 1.4 * hh - 0.5))
+        l, r, t, d = max(0, min(l, w - 1)), max(0, min(r, w - 1)), max(0, min(t, h - 1)), max(0, min(d, h - 1))
+        want[t:d + 1, l:r + 1] = k + 1
+    assert torch.equal(assigned[0, U.LEVEL_POINTS[0]:U.LEVEL_POINTS[0] + h * w].reshape(h, w), want)
+    assert len(set(want.flatten().tolist())) > 2                # more than one gt wins somewhere
+
+
+def test_sizes_are_compared_as_rounded_square_roots():
+    """Two areas that round to the same fp32 root tie (fovea_head.py:205-206,224 sorts gt_areas, not the areas): the higher
+    index wins every painted point, although its area is the larger one."""
+    gts, _ = U.sqrt_tie_case()
+    prod = (gts[:, 2] - gts[:, 0]) * (gts[:, 3] - gts[:, 1])
+    assert float(prod[0]) < float(prod[1]) and float(torch.sqrt(prod)[0]) == float(torch.sqrt(prod)[1]) == 64
+    head = build_head(scale_ranges=U.DEFAULT_RANGES)
+    assigned, _ = U.head_targets(head, [gts])
+    assert set(assigned.flatten().tolist()) == {0, 2} and int((assigned == 2).sum()) >= 2
+
+
+def test_tensor_path_loss_on_the_cpu_matches_the_reference(golden):
+    """FoveaHead.loss (tensor path) on the seeded maps against the reference head's own result: targets exactly, losses and
+    gradients in fp64 to 1e-10, fp32 within 4 x max(the reference's own fp32 error, an ulp); the restatement fovea_util.loss_ref
+    likewise."""
+    g = golden('fovea')
+    metas, gts, labels = inputs()
+    head = build_head()
+    assigned, bt = U.head_targets(head, gts)
+    assert torch.equal(assigned.long(), T(g['head.assigned']).long())
+    check_targets(bt, assigned, gts, T(g['head.bbox_targets']))
+    padded, valid, plab = U.pad_gts(gts, labels)
+    lab = torch.where(assigned > 0, torch.gather(plab, 1, (assigned - 1).clamp(min=0)), torch.full_like(assigned, 80))
+    assert torch.equal(lab, T(g['head.labels']).long())
+    err = g['head.err32']
+    for dt in (torch.float64, torch.float32):
+        maps = [[m.to(dt).requires_grad_() for m in ms] for ms in U.head_maps()]
+        ls = head.loss(*maps, [x.to(dt) for x in gts], labels, metas)
+        assert set(ls) == {'loss_cls', 'loss_bbox'}
+        mine = torch.stack([ls['loss_cls'], ls['loss_bbox']])
+        mine.sum().backward()
+        grads = [U.maps_to_rows([m.grad for m in ms]) for ms in maps]
+        if dt == torch.float64:
+            np.testing.assert_allclose(mine.detach().numpy(), g['head.loss64'], rtol=1e-10)
+            np.testing.assert_allclose(grads[1].numpy(), g['head.greg64'], rtol=1e-9, atol=1e-15)
+            sums, sample = BU.digest(grads[0])
+            np.testing.assert_allclose(sums, g['head.gcls64.sums'], rtol=1e-9)
+            np.testing.assert_allclose(sample, g['head.gcls64.sample'], rtol=1e-9, atol=1e-15)
+        else:
+            for i in range(2):
+                assert abs(float(mine[i].detach()) - float(g['head.loss64'][i])) <= _bound(err[i], T(g['head.loss64'][i]))
+            assert float((grads[1].double() - T(g['head.greg64'])).abs().max()) <= _bound(err[3], T(g['head.greg64']))
+    r = U.loss_ref(*U.head_maps(), plab, assigned, bt)
+    np.testing.assert_allclose(float(r['losses'][0]), g['head.loss64'][0], rtol=1e-10)
+    assert abs(float(r['losses'][1]) - float(g['head.loss64'][1])) <= _bound(err[1], T(g['head.loss64'][1]))      # fp32 targets
+    assert float((U.maps_to_rows(r['greg']) - T(g['head.greg64'])).abs().max()) <= _bound(err[3], T(g['head.greg64']))
+    np.testing.assert_allclose(BU.digest(U.maps_to_rows(r['gcls']))[0], g['head.gcls64.sums'], rtol=1e-9)
+
+
+def test_tensor_path_loss_without_positives(golden):
+    """fovea_head.py:170-174: no positive point -> the box loss is exactly 0 and the regression gradient maps exactly zero."""
+    g = golden('fovea')
+    metas, gts, labels = inputs()
+    head = build_head()
+    maps = [[m.requires_grad_() for m in ms] for ms in U.head_maps()]
+    ls = head.loss(*maps, [x.new_zeros(0, 4) for x in gts], [x.new_zeros(0) for x in labels], metas)
+    assert float(ls['loss_bbox'].detach()) == 0
+    np.testing.assert_allclose(float(ls['loss_cls'].detach()), float(g['head.nopos.loss'][0]), rtol=1e-5)
+    (ls['loss_cls'] + ls['loss_bbox']).backward()
+    assert all(m.grad is not None and float(m.grad.abs().max()) == 0 for m in maps[1])
+    assert all(bool(torch.isfinite(m.grad).all()) and float(m.grad.abs().max()) > 0 for m in maps[0])
+
+
+def test_per_image_get_bboxes_on_the_cpu_matches_the_reference(golden):
+    """The nms_pre cut by the stable descending order of max_c sigmoid(cls), exp, stride * x -+ base_len * pred clamped to the
+    image and the scores with their background column: the reference's own output before its NMS."""
+    from htd_amd.registry import ConfigDict
+    g = golden('fovea')
+    metas, _, _ = inputs()
+    head = build_head()
+    k = int(g['head.nms_pre'])
+    res = head.get_bboxes(*U.head_maps(), metas, cfg=ConfigDict(dict(U.HEAD_TEST_CFG, nms_pre=k)), with_nms=False)
+    for i, (boxes, scores) in enumerate(res):
+        assert scores.shape == (boxes.size(0), 81) and float(scores[:, -1].abs().max()) == 0 and boxes.size(0) == 2 * k + 28
+        # stride * x -+ base_len * exp(pred): the exponential is this machine's (an ulp from the fixture's), times the largest
+        # base edge; the sum rounds once more
+        atol = 3 * EPS32 * 256 * float(torch.cat([r.abs().flatten() for r in U.head_maps()[1]]).max().exp())
+        np.testing.assert_allclose(boxes.numpy(), g[f'head.boxes{i}'], rtol=0, atol=atol)
+        assert atol < 2e-3
+        np.testing.assert_allclose(scores.double().sum(1).numpy(), g[f'head.score_rows{i}'], rtol=1e-12)
+        assert float(boxes[:, [0, 2]].max()) <= metas[i]['img_shape'][1] - 1 and float(boxes.min()) >= 0
+
+
+def test_fused_loss_dispatch_rule():
+    """CPU maps take the tensor form whatever the modules; other loss modules take it on any device."""
+    head = build_head()
+    cls, reg = U.head_maps()
+    assert not head._fused_loss_ok(cls, reg)
+    assert type(head.loss_cls).__name__ == 'FocalLoss' and type(head.loss_bbox).__name__ == 'SmoothL1Loss'
+    other = build_head(loss_bbox=dict(type='L1Loss', loss_weight=1.0))
+    other.fused_loss = True
+    assert not other._fused_loss_ok(cls, reg)
+    fa = build_head(with_deform=True, norm_cfg=dict(type='GN', num_groups=32, requires_grad=True)).feature_adaption
+    assert not fa._kernel_ok(reg[0]) and not fa._kernel_ok(None)
+
+
+def test_new_abi_symbols_are_declared_and_exported():
+    from htd_amd import capi
+    names = {n for n, _, _ in capi.declared_functions()}
+    want = {'htd_fovea_targets_workspace_bytes', 'htd_fovea_targets', 'htd_fovea_loss_partial_rows', 'htd_fovea_loss',
+            'htd_fovea_grad_scale', 'htd_fovea_align_fwd', 'htd_fovea_align_bwd_workspace_bytes', 'htd_fovea_align_bwd'}
+    assert want <= names
+    lib = capi.lib()
+    assert all(hasattr(lib, n) for n in want)
+    assert lib.htd_fovea_loss_partial_rows() > 0 and lib.htd_fovea_loss_partial_rows() % 2 == 0
+    assert lib.htd_fovea_targets_workspace_bytes(2, 428) >= 2 * 2 * 4
+    assert lib.htd_fovea_align_bwd_workspace_bytes(2, 8, 10, 4) >= 3 * 72 * 4 * 4
+    header = open(capi.HEADER).read()
+    assert 'fovea_head.py:177-258' in header and 'fovea_head.py:127-175' in header and 'fovea_head.py:22-23,36-37' in header
