@@ -677,8 +677,8 @@ def batched_random_sample(assigned, num, pos_fraction, neg_pos_ub=-1, keys=None)
     pos_mask = pick(is_pos, torch.full((B, 1), int(num * pos_fraction), device=assigned.device))
     n_pos = pos_mask.sum(dim=1, keepdim=True)
     n_neg = num - n_pos
-    if neg_pos_ub >= 0:
-        n_neg = torch.min(n_neg, (neg_pos_ub * n_pos.clamp(min=1)).long())
+    if neg_pos_ub >= 0:      # int(neg_pos_ub * max(1, n_pos)) is a double product (base_sampler.py:90-92); fp32 rounds 0.29 * 100 up to 29
+        n_neg = torch.min(n_neg, (float(neg_pos_ub) * n_pos.clamp(min=1).double()).long())
     return pos_mask, pick(is_neg, n_neg)
 
 

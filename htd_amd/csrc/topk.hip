@@ -299,7 +299,7 @@ __device__ void sort_ascending(unsigned *w, int n)
 // one workgroup per image: how many of the ranked candidates are drawn, the two masks, the counts and (optionally) the
 // slot order of SamplingResult: drawn positives by ascending index, then drawn negatives by ascending index
 __global__ __launch_bounds__(1024) void sample_finish_kernel(const int64_t *__restrict__ idx, const float *__restrict__ val,
-                                                             int B, int64_t A, int kpos, int kneg, int num, float neg_pos_ub,
+                                                             int B, int64_t A, int kpos, int kneg, int num, double neg_pos_ub,
                                                              unsigned char *__restrict__ pos_mask,
                                                              unsigned char *__restrict__ neg_mask, int64_t *__restrict__ counts,
                                                              int64_t *__restrict__ order, int slots)
@@ -318,9 +318,10 @@ __global__ __launch_bounds__(1024) void sample_finish_kernel(const int64_t *__re
     __syncthreads();
     const int n_pos = cnt[0];
     int64_t limit = num - n_pos;
-    if (neg_pos_ub >= 0.f) {
-        const int64_t ub = (int64_t)(neg_pos_ub * (float)(n_pos > 1 ? n_pos : 1));      // base_sampler.py:86-91
-        limit = limit < ub ? limit : ub;
+    if (neg_pos_ub >= 0.0) {
+        // base_sampler.py:86-92: int(neg_pos_ub * max(1, n_pos)) is Python's double product; in fp32 0.29 * 100 rounds up to 29
+        const double ub = neg_pos_ub * (double)(n_pos > 1 ? n_pos : 1);
+        if (ub < (double)limit) limit = (int64_t)ub;
     }
     const int lim = (int)(limit < 0 ? 0 : (limit < kneg ? limit : kneg));
     c = 0;
@@ -376,8 +377,9 @@ extern "C" int64_t htd_random_sample_workspace_bytes(int B, int64_t A, int64_t n
 // is the candidates with the smallest keys.  segs / chunk_tab: the tables of htd_segmented_topk for the 2B segments
 // (b * A, A, kpos, b * kpos) and (B * A + b * A, A, kneg, B * kpos + b * kneg), kpos = min(max_pos, A), kneg = min(num, A).
 // pos_mask / neg_mask [B][A] bytes (0 / 1), counts [B][2] = (positives, negatives) drawn, order [B][slots] (may be NULL).
+// neg_pos_ub (< 0: no bound) is a double: the bound is the reference's int(neg_pos_ub * max(1, positives drawn)).
 extern "C" int htd_random_sample(const int64_t *assigned, const float *keys, int B, int64_t A, int num, int max_pos,
-                                 float neg_pos_ub, const int64_t *segs, const int32_t *chunk_tab, int64_t nchunks,
+                                 double neg_pos_ub, const int64_t *segs, const int32_t *chunk_tab, int64_t nchunks,
                                  unsigned char *pos_mask, unsigned char *neg_mask, int64_t *counts, int64_t *order, int slots,
                                  void *workspace, void *stream)
 {

@@ -32,7 +32,7 @@ extern "C" {
 const char *htd_last_error(void);
 /* ABI version, bumped on any signature change (added entry points do not bump it).  A binding compares
  * htd_abi_version() of the loaded library with the HTD_ABI_VERSION of the header it was written against. */
-#define HTD_ABI_VERSION 7
+#define HTD_ABI_VERSION 8
 int htd_abi_version(void);
 
 /* ------------------------------------------------------------------------------------
@@ -156,13 +156,15 @@ int htd_segmented_topk(const float *keys, const int64_t *segs, const int32_t *ch
 /* RandomSampler for a batch (core/bbox/samplers/base_sampler.py:34-101, random_sampler.py:33-78) without a host round trip:
  * a uniformly random subset of n candidates is the n candidates with the smallest i.i.d. keys.  assigned [B][A] =
  * AssignResult.gt_inds (> 0 positive, 0 negative, < 0 ignored), keys [B][A] in [0, 1).  Draws min(max_pos, #positives)
- * positives, then min(num - drawn positives, neg_pos_ub bound, #negatives) negatives.  segs / chunk_tab: the device tables of
+ * positives, then min(num - drawn positives, neg_pos_ub bound, #negatives) negatives; the bound is the reference's
+ * int(neg_pos_ub * max(1, drawn positives)), a DOUBLE product (in fp32 0.29 * 100 rounds up to 29), hence `double neg_pos_ub`
+ * (< 0: no bound).  segs / chunk_tab: the device tables of
  * htd_segmented_topk for the 2B segments (b*A, A, kpos, b*kpos) and (B*A + b*A, A, kneg, B*kpos + b*kneg), kpos =
  * min(max_pos, A), kneg = min(num, A), num <= 2048.  pos_mask / neg_mask [B][A] bytes 0/1; counts [B][2] drawn (pos, neg);
  * order [B][slots] (may be NULL): drawn positives by ascending index, then drawn negatives by ascending index (the row order
  * of SamplingResult.bboxes, sampling_result.py:23-38), unused slots 0. */
 int64_t htd_random_sample_workspace_bytes(int B, int64_t A, int64_t nchunks);
-int htd_random_sample(const int64_t *assigned, const float *keys, int B, int64_t A, int num, int max_pos, float neg_pos_ub,
+int htd_random_sample(const int64_t *assigned, const float *keys, int B, int64_t A, int num, int max_pos, double neg_pos_ub,
                       const int64_t *segs, const int32_t *chunk_tab, int64_t nchunks, unsigned char *pos_mask,
                       unsigned char *neg_mask, int64_t *counts, int64_t *order, int slots, void *workspace, void *stream);
 

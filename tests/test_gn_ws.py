@@ -178,7 +178,7 @@ def test_new_abi_symbols_are_declared_and_exported():
     assert want <= names
     lib = capi.lib()
     assert all(hasattr(lib, n) for n in want)
-    assert lib.htd_abi_version() == 7
+    assert lib.htd_abi_version() == 8
     assert lib.htd_group_norm_map_slab(200 * 336, 256) > 0
     assert lib.htd_group_norm_map_workspace_bytes(4, 200 * 336, 256, 32) >= 4 * 32 * 16
     assert lib.htd_group_norm_map_slab(100, 2050) != 0 and b'group_norm_map_slab' in lib.htd_last_error()

@@ -133,7 +133,7 @@ def test_head_loss_classes_argument_checks():
         _raw('htd_roi_head_loss_classes', cls, labels, lw, full, tgt, bw, 5, 4, 0, 0.0)
     with pytest.raises(ValueError, match='box_loss'):
         _raw('htd_roi_head_loss_classes', cls, labels, lw, full, tgt, bw, 5, 4, 2)
-    assert capi.lib().htd_abi_version() == 7
+    assert capi.lib().htd_abi_version() == 8
 
 
 # ---------------------------------------------------------------------------------------------------- the two detectors
