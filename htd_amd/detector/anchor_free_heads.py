@@ -14,10 +14,8 @@ that computes the points itself (htd_fcos_targets: no (points, gts) matrices, th
 takes the three losses and the three gradient maps of all levels in one more (htd_fcos_loss) that reads the maps where they are: no
 permute, concatenation or gather of the predictions, no nonzero(), no host read.
 
-`get_bboxes` handles the whole batch on the GPU: one key launch (htd_fcos_keys) and one segmented top-k give every (image, level)
-cut to nms_pre, one gather, one multiclass NMS over all images with the centerness as score factor; the decode stays
-distance2bbox image by image, so the result is bit-identical to the per-image loop, which ranks by the same launch form.  The
-code is BaseDenseHead's (`_ctr_get_bboxes`), which ATSSHead shares.
+`get_bboxes` is BaseDenseHead._get_bboxes, which all dense heads share, with the points as priors, distance2bbox as decode and the
+centerness maps as score factors of the ranking (htd_fcos_keys) and of the NMS.
 """
 import os
 
@@ -322,26 +320,14 @@ class FCOSHead(AnchorFreeHead):
         return dict(loss_cls=loss_cls, loss_bbox=loss_bbox, loss_centerness=loss_centerness)
 
     # ------------------------------------------------------------------ boxes
-    @staticmethod
-    def _decode(points, distances, img_shape):
+    def _bbox_priors(self, featmap_sizes, dtype, device):
+        return self.get_points(featmap_sizes, dtype, device)
+
+    def _bbox_decode(self, points, distances, img_shape):
         return distance2bbox(points, distances, max_shape=img_shape)
 
     @torch.no_grad()
     def get_bboxes(self, cls_scores, bbox_preds, centernesses, img_metas, cfg=None, rescale=False, with_nms=True):
-        """fcos_head.py:255-401 -> list (per image) of (dets (k, 5), labels (k,)): BaseDenseHead._ctr_get_bboxes with the points
-        as priors and distance2bbox as decode.  GPU fp32 maps with hard NMS take the batched form; everything else the
-        per-image loop."""
-        featmap_sizes = [c.shape[-2:] for c in cls_scores]
-        dev = cls_scores[0].device
-
-        def flat_points():
-            return self._cached('_points_cache', 32, (self._shape_key(featmap_sizes), str(dev)),
-                                lambda: torch.cat(self.get_points(featmap_sizes, torch.float32, dev)))
-        return self._ctr_get_bboxes(cls_scores, bbox_preds, centernesses, img_metas, cfg, rescale, with_nms, self.strides,
-                                    lambda: self.get_points(featmap_sizes, bbox_preds[0].dtype, dev), flat_points, self._decode)
-
-    def _get_bboxes_single(self, cls_scores, bbox_preds, centernesses, mlvl_points, img_shape, scale_factor, cfg, rescale=False,
-                           with_nms=True):
-        """fcos_head.py:315-401 for one image."""
-        return self._ctr_bboxes_single(cls_scores, bbox_preds, centernesses, mlvl_points, self._decode, self.strides, img_shape,
-                                       scale_factor, cfg, rescale, with_nms)
+        """fcos_head.py:255-401 -> list (per image) of (dets (k, 5), labels (k,)), the centerness as score factor of the ranking
+        and of the NMS."""
+        return self._get_bboxes(cls_scores, bbox_preds, centernesses, img_metas, cfg, rescale, with_nms)

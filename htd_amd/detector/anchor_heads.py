@@ -7,8 +7,8 @@ atss_cls / atss_reg / atss_centerness / scales.N.scale; gfl_cls / gfl_reg / inte
 (detector/rpn_head.py), as in the reference: anchors, per-image targets (gt_labels None: foreground is class 0), the
 reference-order loss are written once, here; forward_train, simple_test and the cache of constants of the pyramid's map shapes
 (`_shape_key` makes their key, `_cached` fetches them) come from BaseDenseHead (detector/base_dense_head.py), which the
-anchor-free heads share: `_anchors_inside`, the RPN's proposal constants and the level-concatenated anchors of
-`_get_bboxes_batched` all go through the two.
+anchor-free heads share: `_anchors_inside`, the RPN's proposal constants and the level-concatenated priors of `_get_bboxes` all go
+through the two.
 
 `loss` has two forms, like RPNHead.loss.  The tensor form follows the reference's order of operations (per image targets, per
 level losses) and works with any loss modules, `reg_decoded_bbox`, ignore boxes and on the CPU.  The fused form -- FocalLoss with
@@ -18,10 +18,10 @@ both gradients of all levels in one launch (htd_retina_loss; htd_ghm_head_loss i
 the convolution outputs where they are: no labels / label_weights /
 bbox_targets / bbox_weights tensors, no permute or concatenation of the logits, no host read.
 
-`get_bboxes` handles the whole batch: one key launch (htd_retina_keys) and one segmented top-k give every (image, level) cut
-to nms_pre, one gather of the kept logits and deltas, one multiclass NMS over all images.  The decode and the rescale stay the
-coder's own tensor operations applied image by image (a handful of element-wise launches on nms_pre x levels rows each), so the
-result is bit-identical to the per-image loop, which is the rule the two-stage post-processing follows.
+`get_bboxes` of RetinaHead, ATSSHead and GFLHead is BaseDenseHead._get_bboxes (the dispatch, the per-image loop and the batched
+form, written once for all dense heads); a head gives its priors (`_bbox_priors`: the anchors, GFLHead their centres) and its
+decode (`_bbox_decode`), ATSSHead passes its centerness maps as score factors and GFLHead takes keys and distances from its one
+htd_gfl_decode launch (`_keys_and_preds`).
 """
 import os
 
@@ -242,13 +242,6 @@ class AnchorHead(BaseDenseHead):
                str(dev), border)
         return self._cached('_inside_cache', 64, key, make)
 
-    def _level_cuts(self, cls_scores, nms_pre):
-        """Per level: its number of anchors, how many of them the cut to nms_pre keeps (all when nms_pre <= 0) and its first
-        column in the level-concatenated order."""
-        Ns = [int(c.shape[2] * c.shape[3]) * self.num_anchors for c in cls_scores]
-        ks = [n if nms_pre <= 0 else min(nms_pre, n) for n in Ns]
-        return Ns, ks, [sum(Ns[:l]) for l in range(len(Ns))]
-
     def loss_fused(self, cls_scores, bbox_preds, gt_bboxes, gt_labels, img_metas):
         from ..core.bbox import batched_max_iou_assign, pad_gt_batch
         dev = cls_scores[0].device
@@ -275,110 +268,21 @@ class AnchorHead(BaseDenseHead):
         return dict(loss_cls=[loss_cls], loss_bbox=[loss_bbox])
 
     # ------------------------------------------------------------------ boxes
+    @property
+    def strides(self):
+        return self.anchor_generator.strides
+
+    def _bbox_priors(self, featmap_sizes, dtype, device):
+        return self.anchor_generator.grid_anchors(featmap_sizes, device=device)
+
+    def _bbox_decode(self, anchors, deltas, img_shape):
+        return self.bbox_coder.decode(anchors, deltas, max_shape=img_shape)
+
     @torch.no_grad()
     def get_bboxes(self, cls_scores, bbox_preds, img_metas, cfg=None, rescale=False, with_nms=True):
-        """anchor_head.py:490-664 -> list (per image) of (dets (k, 5), labels (k,)).  GPU fp32 sigmoid heads with hard NMS take
-        the batched form; everything else the per-image loop."""
-        cfg = self.test_cfg if cfg is None else cfg
-        assert len(cls_scores) == len(bbox_preds)
-        nms_pre = cfg.get('nms_pre', -1)
-        Ns = [int(c.shape[2] * c.shape[3]) * self.num_anchors for c in cls_scores]
-        batched = with_nms and self.use_sigmoid_cls and cls_scores[0].is_cuda and len(cls_scores) <= 8 and \
-            all(t.dtype == torch.float32 for t in list(cls_scores) + list(bbox_preds)) and \
-            cfg.nms.get('type', 'nms') == 'nms' and (nms_pre <= 0 or nms_pre <= M.TOPK_KMAX) and \
-            getattr(self, 'batched_get_bboxes', True) and (nms_pre > 0 or max(Ns) <= M.TOPK_KMAX)
-        if batched:
-            return self._get_bboxes_batched(cls_scores, bbox_preds, img_metas, cfg, rescale)
-        dev = cls_scores[0].device
-        featmap_sizes = [c.shape[-2:] for c in cls_scores]
-        mlvl_anchors = self.anchor_generator.grid_anchors(featmap_sizes, device=dev)
-        out = []
-        for b, meta in enumerate(img_metas):
-            out.append(self._get_bboxes_single([c[b].detach() for c in cls_scores], [r[b].detach() for r in bbox_preds],
-                                               mlvl_anchors, meta['img_shape'], meta['scale_factor'], cfg, rescale, with_nms))
-        return out
-
-    def _level_keys(self, cls_score_list):
-        """per level (n_l,) max_c sigmoid(score): htd_retina_keys on the GPU (the same launch form as the batched path, so
-        the two rank identically), tensor operations elsewhere."""
-        if cls_score_list[0].is_cuda and cls_score_list[0].dtype == torch.float32 and self.use_sigmoid_cls and \
-                len(cls_score_list) <= 8:
-            keys = M.retina_keys([c[None] for c in cls_score_list], self.num_anchors, self.cls_out_channels)[0]
-            sizes = [int(c.shape[1] * c.shape[2]) * self.num_anchors for c in cls_score_list]
-            return list(keys.split(sizes))
-        out = []
-        for c in cls_score_list:
-            s = c.permute(1, 2, 0).reshape(-1, self.cls_out_channels)
-            out.append(s.sigmoid().max(dim=1)[0] if self.use_sigmoid_cls else s.softmax(-1)[:, :-1].max(dim=1)[0])
-        return out
-
-    def _get_bboxes_single(self, cls_score_list, bbox_pred_list, mlvl_anchors, img_shape, scale_factor, cfg, rescale=False,
-                           with_nms=True):
-        """anchor_head.py:581-664 for one image."""
-        from ..core.post_processing import multiclass_nms
-        cfg = self.test_cfg if cfg is None else cfg
-        assert len(cls_score_list) == len(bbox_pred_list) == len(mlvl_anchors)
-        nms_pre = cfg.get('nms_pre', -1)
-        keys = self._level_keys(cls_score_list) if nms_pre > 0 and any(a.size(0) > nms_pre for a in mlvl_anchors) else None
-        mlvl_bboxes, mlvl_scores = [], []
-        for lvl, (cls_score, bbox_pred, anchors) in enumerate(zip(cls_score_list, bbox_pred_list, mlvl_anchors)):
-            assert cls_score.size()[-2:] == bbox_pred.size()[-2:]
-            cls_score = cls_score.permute(1, 2, 0).reshape(-1, self.cls_out_channels)
-            bbox_pred = bbox_pred.permute(1, 2, 0).reshape(-1, 4)
-            if nms_pre > 0 and cls_score.shape[0] > nms_pre:
-                # the first nms_pre of the stable descending order (equal keys: lower anchor index first)
-                topk_inds = keys[lvl].sort(descending=True, stable=True)[1][:nms_pre]
-                anchors, bbox_pred, cls_score = anchors[topk_inds, :], bbox_pred[topk_inds, :], cls_score[topk_inds, :]
-            scores = cls_score.sigmoid() if self.use_sigmoid_cls else cls_score.softmax(-1)
-            mlvl_bboxes.append(self.bbox_coder.decode(anchors, bbox_pred, max_shape=img_shape))
-            mlvl_scores.append(scores)
-        mlvl_bboxes = torch.cat(mlvl_bboxes)
-        if rescale:
-            mlvl_bboxes = mlvl_bboxes / mlvl_bboxes.new_tensor(scale_factor)
-        mlvl_scores = torch.cat(mlvl_scores)
-        if self.use_sigmoid_cls:
-            mlvl_scores = torch.cat([mlvl_scores, mlvl_scores.new_zeros(mlvl_scores.shape[0], 1)], dim=1)
-        if with_nms:
-            return multiclass_nms(mlvl_bboxes, mlvl_scores, cfg.score_thr, cfg.nms, cfg.max_per_img)
-        return mlvl_bboxes, mlvl_scores
-
-    def _get_bboxes_batched(self, cls_scores, bbox_preds, img_metas, cfg, rescale):
-        from ..core.post_processing import multiclass_nms_images
-        B, L = cls_scores[0].size(0), len(cls_scores)
-        dev = cls_scores[0].device
-        C, na = self.cls_out_channels, self.num_anchors
-        featmap_sizes = [c.shape[-2:] for c in cls_scores]
-        Ns, ks, offs = self._level_cuts(cls_scores, cfg.get('nms_pre', -1))
-        total = sum(Ns)
-        cls_scores = [c.detach() for c in cls_scores]
-        anchors = self._cached('_bbox_cache', 32, (self._shape_key(featmap_sizes), tuple(ks), str(dev)),
-                               lambda: torch.cat(self.anchor_generator.grid_anchors(featmap_sizes, device=dev)))
-        cut = [l for l in range(L) if ks[l] < Ns[l]]
-        pieces = [torch.arange(offs[l], offs[l] + Ns[l], device=dev)[None].expand(B, Ns[l]) for l in range(L)]
-        if cut:
-            # every (image, level) cut of the call in one key launch and one segmented top-k; a level that is not cut keeps its
-            # anchors in their own order, as the per-image form does
-            keys = M.retina_keys(cls_scores, na, C)                                   # (B, total)
-            top_idx, _ = M.segmented_topk(keys, [(b * total + offs[l], Ns[l], ks[l]) for b in range(B) for l in cut])
-            top_idx, at = top_idx.view(B, -1), 0
-            for l in cut:
-                pieces[l] = top_idx[:, at:at + ks[l]] + offs[l]
-                at += ks[l]
-        gidx = torch.cat(pieces, 1)
-        K = gidx.size(1)
-        logits = torch.cat([c.permute(0, 2, 3, 1).reshape(B, -1, C) for c in cls_scores], 1)
-        deltas = torch.cat([r.detach().permute(0, 2, 3, 1).reshape(B, -1, 4) for r in bbox_preds], 1)
-        scores = torch.gather(logits, 1, gidx[..., None].expand(B, K, C)).sigmoid()
-        deltas = torch.gather(deltas, 1, gidx[..., None].expand(B, K, 4))
-        boxes = torch.stack([self.bbox_coder.decode(anchors[gidx[b]], deltas[b], max_shape=img_metas[b]['img_shape'])
-                             for b in range(B)])
-        if rescale:
-            boxes = torch.stack([boxes[b] / boxes.new_tensor(img_metas[b]['scale_factor']) for b in range(B)])
-        scores = torch.cat([scores, scores.new_zeros(B, K, 1)], dim=2)
-        img_of = torch.arange(B, device=dev).repeat_interleave(K)
-        dets, labels = multiclass_nms_images(boxes.reshape(B * K, 4), scores.reshape(B * K, C + 1), img_of, B, cfg.score_thr,
-                                             cfg.nms, cfg.max_per_img)
-        return list(zip(dets, labels))
+        """anchor_head.py:490-664 -> list (per image) of (dets (k, 5), labels (k,)): BaseDenseHead._get_bboxes with the anchors
+        as priors and the coder's decode.  Softmax heads take the per-image loop."""
+        return self._get_bboxes(cls_scores, bbox_preds, None, img_metas, cfg, rescale, with_nms)
 
 
 @HEADS.register_module()
@@ -434,7 +338,7 @@ class ATSSHead(AnchorHead):
     (htd_atss_targets), and takes the three losses and the three gradient maps of all levels in one more launch (htd_atss_loss)
     that reads the maps where they are: no permute, concatenation or gather of the predictions, no nonzero(), no host read.
 
-    `get_bboxes` is BaseDenseHead._ctr_get_bboxes, shared with FCOSHead, with the anchors as priors and the coder's decode."""
+    `get_bboxes` is BaseDenseHead._get_bboxes with the anchors as priors, the coder's decode and the centerness as score factor."""
 
     def __init__(self, num_classes, in_channels, stacked_convs=4, conv_cfg=None,
                  norm_cfg=dict(type='GN', num_groups=32, requires_grad=True),
@@ -664,28 +568,11 @@ class ATSSHead(AnchorHead):
         return dict(loss_cls=loss_cls, loss_bbox=loss_bbox, loss_centerness=loss_centerness)
 
     # ------------------------------------------------------------------ boxes
-    def _decode(self, anchors, deltas, img_shape):
-        return self.bbox_coder.decode(anchors, deltas, max_shape=img_shape)
-
     @torch.no_grad()
     def get_bboxes(self, cls_scores, bbox_preds, centernesses, img_metas, cfg=None, rescale=False, with_nms=True):
-        """atss_head.py:316-469 -> list (per image) of (dets (k, 5), labels (k,)), the centerness as score factor of the NMS.
-        Several anchors per location take the per-image loop with the reference's own tensor operations."""
-        featmap_sizes = [c.shape[-2:] for c in cls_scores]
-        dev = cls_scores[0].device
-
-        def flat_anchors():
-            return self._cached('_bbox_cache', 32, (self._shape_key(featmap_sizes), str(dev)),
-                                lambda: torch.cat(self.anchor_generator.grid_anchors(featmap_sizes, device=dev)))
-        return self._ctr_get_bboxes(cls_scores, bbox_preds, centernesses, img_metas, cfg, rescale, with_nms,
-                                    self.anchor_generator.strides,
-                                    lambda: self.anchor_generator.grid_anchors(featmap_sizes, device=dev), flat_anchors, self._decode)
-
-    def _get_bboxes_single(self, cls_scores, bbox_preds, centernesses, mlvl_anchors, img_shape, scale_factor, cfg, rescale=False,
-                           with_nms=True):
-        """atss_head.py:379-469 for one image."""
-        return self._ctr_bboxes_single(cls_scores, bbox_preds, centernesses, mlvl_anchors, self._decode, self.anchor_generator.strides,
-                                       img_shape, scale_factor, cfg, rescale, with_nms)
+        """atss_head.py:316-469 -> list (per image) of (dets (k, 5), labels (k,)), the centerness as score factor of the ranking
+        and of the NMS.  Several anchors per location take the per-image loop with the reference's own tensor operations."""
+        return self._get_bboxes(cls_scores, bbox_preds, centernesses, img_metas, cfg, rescale, with_nms)
 
 
 class Integral(nn.Module):
@@ -888,110 +775,31 @@ class GFLHead(AnchorHead):
         return dict(loss_cls=loss_cls, loss_bbox=loss_bbox, loss_dfl=loss_dfl)
 
     # ------------------------------------------------------------------ boxes
-    def _device_decode_ok(self, cls_scores, bbox_preds):
-        """htd_gfl_decode takes fp32 channels_last GPU maps (of a batch, or of one image of one) of at most 8 levels; anything
-        else, NCHW-contiguous maps included, takes the tensor operations."""
+    def _device_keys_ok(self, cls_scores, bbox_preds, score_factors=None):
+        """htd_gfl_decode takes fp32 channels_last GPU maps of at most 8 levels; anything else, NCHW-contiguous maps included,
+        takes the tensor operations."""
         return cls_scores[0].is_cuda and len(cls_scores) <= 8 and 1 <= self.reg_max <= 31 and \
-            all(t.dtype == torch.float32 and M.nhwc_channel_stride(t if t.dim() == 4 else t[None]) is not None
-                for t in list(cls_scores) + list(bbox_preds))
+            all(t.dtype == torch.float32 and M.nhwc_channel_stride(t) is not None for t in list(cls_scores) + list(bbox_preds))
+
+    def _bbox_priors(self, featmap_sizes, dtype, device):
+        return [self.anchor_center(a) for a in self.anchor_generator.grid_anchors(featmap_sizes, device=device)]
+
+    def _bbox_decode(self, centres, dists, img_shape):
+        from ..core.bbox import distance2bbox
+        return distance2bbox(centres, dists, max_shape=img_shape)
+
+    def _keys_and_preds(self, cls_scores, bbox_preds, score_factors, want_keys):
+        """-> (B, A) max_c sigmoid(score) and (B, A, 4) integral * stride: one htd_gfl_decode launch gives both, so it runs
+        whether or not a level is cut; the reference's tensor operations elsewhere."""
+        if self._device_keys_ok(cls_scores, bbox_preds):
+            return M.gfl_decode(cls_scores, bbox_preds, self.strides, self.reg_max)
+        B = cls_scores[0].size(0)
+        keys = [c.permute(0, 2, 3, 1).reshape(B, -1, self.cls_out_channels).sigmoid().max(dim=-1)[0] for c in cls_scores]
+        dists = [(self.integral(r.permute(0, 2, 3, 1)) * s[0]).reshape(B, -1, 4) for r, s in zip(bbox_preds, self.strides)]
+        return torch.cat(keys, 1), torch.cat(dists, 1)
 
     @torch.no_grad()
     def get_bboxes(self, cls_scores, bbox_preds, img_metas, cfg=None, rescale=False, with_nms=True):
-        """gfl_head.py:371-455 over a batch -> list (per image) of (dets (k, 5), labels (k,)).  GPU fp32 maps with hard NMS take
-        the batched form; everything else the per-image loop."""
-        cfg = self.test_cfg if cfg is None else cfg
-        assert len(cls_scores) == len(bbox_preds)
-        featmap_sizes = [c.shape[-2:] for c in cls_scores]
-        dev = cls_scores[0].device
-        nms_pre = cfg.get('nms_pre', -1)
-        Ns = [int(h * w) for h, w in featmap_sizes]
-        batched = with_nms and self._device_decode_ok(cls_scores, bbox_preds) and cfg.nms.get('type', 'nms') == 'nms' and \
-            (nms_pre <= 0 or nms_pre <= M.TOPK_KMAX) and getattr(self, 'batched_get_bboxes', True) and \
-            (nms_pre > 0 or max(Ns) <= M.TOPK_KMAX)
-        if batched:
-            return self._get_bboxes_batched(cls_scores, bbox_preds, img_metas, cfg, rescale)
-        mlvl_anchors = self.anchor_generator.grid_anchors(featmap_sizes, device=dev)
-        return [self._get_bboxes_single([c[b].detach() for c in cls_scores], [r[b].detach() for r in bbox_preds], mlvl_anchors,
-                                        meta['img_shape'], meta['scale_factor'], cfg, rescale, with_nms)
-                for b, meta in enumerate(img_metas)]
-
-    def _level_keys_dists(self, cls_scores, bbox_preds):
-        """per level (n_l,) max_c sigmoid(score) and (n_l, 4) integral * stride of one image: htd_gfl_decode on the GPU (the
-        launch form of the batched path, so the two rank and decode identically), the reference's tensor operations elsewhere."""
-        strides = self.anchor_generator.strides
-        if self._device_decode_ok(cls_scores, bbox_preds):
-            keys, dists = M.gfl_decode([c[None] for c in cls_scores], [r[None] for r in bbox_preds], strides, self.reg_max)
-            Ns = [int(c.shape[1] * c.shape[2]) for c in cls_scores]
-            return list(keys[0].split(Ns)), list(dists[0].split(Ns))
-        keys = [c.permute(1, 2, 0).reshape(-1, self.cls_out_channels).sigmoid().max(dim=1)[0] for c in cls_scores]
-        dists = [self.integral(r.permute(1, 2, 0)) * s[0] for r, s in zip(bbox_preds, strides)]
-        return keys, dists
-
-    def _get_bboxes_single(self, cls_scores, bbox_preds, mlvl_anchors, img_shape, scale_factor, cfg, rescale=False, with_nms=True):
-        """gfl_head.py:371-455 for one image."""
-        from ..core.bbox import distance2bbox
-        from ..core.post_processing import multiclass_nms
-        cfg = self.test_cfg if cfg is None else cfg
-        assert len(cls_scores) == len(bbox_preds) == len(mlvl_anchors)
-        nms_pre = cfg.get('nms_pre', -1)
-        keys, dists = self._level_keys_dists(cls_scores, bbox_preds)
-        mlvl_bboxes, mlvl_scores = [], []
-        for lvl, (cls_score, anchors) in enumerate(zip(cls_scores, mlvl_anchors)):
-            assert cls_score.size()[-2:] == bbox_preds[lvl].size()[-2:]
-            scores = cls_score.permute(1, 2, 0).reshape(-1, self.cls_out_channels).sigmoid()
-            bbox_pred = dists[lvl]
-            if nms_pre > 0 and scores.shape[0] > nms_pre:
-                # the first nms_pre of the stable descending order (equal keys: lower location index first)
-                topk_inds = keys[lvl].sort(descending=True, stable=True)[1][:nms_pre]
-                anchors, bbox_pred, scores = anchors[topk_inds, :], bbox_pred[topk_inds, :], scores[topk_inds, :]
-            mlvl_bboxes.append(distance2bbox(self.anchor_center(anchors), bbox_pred, max_shape=img_shape))
-            mlvl_scores.append(scores)
-        mlvl_bboxes = torch.cat(mlvl_bboxes)
-        if rescale:
-            mlvl_bboxes = mlvl_bboxes / mlvl_bboxes.new_tensor(scale_factor)
-        mlvl_scores = torch.cat(mlvl_scores)
-        mlvl_scores = torch.cat([mlvl_scores, mlvl_scores.new_zeros(mlvl_scores.shape[0], 1)], dim=1)
-        if with_nms:
-            return multiclass_nms(mlvl_bboxes, mlvl_scores, cfg.score_thr, cfg.nms, cfg.max_per_img)
-        return mlvl_bboxes, mlvl_scores
-
-    def _get_bboxes_batched(self, cls_scores, bbox_preds, img_metas, cfg, rescale):
-        """The whole batch on the GPU: one decode launch (htd_gfl_decode) and one segmented top-k give every (image, level) cut
-        to nms_pre, one gather, one multiclass NMS over all images without score factors; distance2bbox stays the tensor
-        operation, image by image, so the result is bit-identical to the per-image loop."""
-        from ..core.bbox import distance2bbox
-        from ..core.post_processing import multiclass_nms_images
-        B, L = cls_scores[0].size(0), len(cls_scores)
-        dev = cls_scores[0].device
-        C = self.cls_out_channels
-        featmap_sizes = [c.shape[-2:] for c in cls_scores]
-        nms_pre = cfg.get('nms_pre', -1)
-        Ns = [int(h * w) for h, w in featmap_sizes]
-        ks = [n if nms_pre <= 0 else min(nms_pre, n) for n in Ns]
-        offs = [sum(Ns[:l]) for l in range(L)]
-        total = sum(Ns)
-        cls_scores = [c.detach() for c in cls_scores]
-        centres = self._cached('_centre_cache', 32, (self._shape_key(featmap_sizes), str(dev)),
-                               lambda: self.anchor_center(torch.cat(self.anchor_generator.grid_anchors(featmap_sizes, device=dev))))
-        keys, dists = M.gfl_decode(cls_scores, [r.detach() for r in bbox_preds], self.anchor_generator.strides, self.reg_max)
-        cut = [l for l in range(L) if ks[l] < Ns[l]]
-        pieces = [torch.arange(offs[l], offs[l] + Ns[l], device=dev)[None].expand(B, Ns[l]) for l in range(L)]
-        if cut:
-            top_idx, _ = M.segmented_topk(keys, [(b * total + offs[l], Ns[l], ks[l]) for b in range(B) for l in cut])
-            top_idx, at = top_idx.view(B, -1), 0
-            for l in cut:
-                pieces[l] = top_idx[:, at:at + ks[l]] + offs[l]
-                at += ks[l]
-        gidx = torch.cat(pieces, 1)
-        K = gidx.size(1)
-        logits = torch.cat([c.permute(0, 2, 3, 1).reshape(B, -1, C) for c in cls_scores], 1)
-        scores = torch.gather(logits, 1, gidx[..., None].expand(B, K, C)).sigmoid()
-        dists = torch.gather(dists, 1, gidx[..., None].expand(B, K, 4))
-        boxes = torch.stack([distance2bbox(centres[gidx[b]], dists[b], max_shape=img_metas[b]['img_shape']) for b in range(B)])
-        if rescale:
-            boxes = torch.stack([boxes[b] / boxes.new_tensor(img_metas[b]['scale_factor']) for b in range(B)])
-        scores = torch.cat([scores, scores.new_zeros(B, K, 1)], dim=2)
-        img_of = torch.arange(B, device=dev).repeat_interleave(K)
-        dets, labels = multiclass_nms_images(boxes.reshape(B * K, 4), scores.reshape(B * K, C + 1), img_of, B, cfg.score_thr,
-                                             cfg.nms, cfg.max_per_img)
-        return list(zip(dets, labels))
+        """gfl_head.py:371-455 over a batch -> list (per image) of (dets (k, 5), labels (k,)): BaseDenseHead._get_bboxes with the
+        anchor centres as priors and distance2bbox as decode."""
+        return self._get_bboxes(cls_scores, bbox_preds, None, img_metas, cfg, rescale, with_nms)

@@ -1,13 +1,28 @@
 """BaseDenseHead: what the anchor-based (detector/anchor_heads.py) and the anchor-free (detector/anchor_free_heads.py) dense
 heads share.
 
-Reference: dense_heads/base_dense_head.py:22-59 (forward_train), dense_test_mixins.py (simple_test).  A head gives `forward`,
-`loss` and `get_bboxes`; the step plumbing and the cache of constants of the pyramid's map shapes are written once, here, and
-so is get_bboxes of the heads that predict one box and one centerness per location (FCOSHead from points and distances, ATSSHead
-from anchors and deltas): `_ctr_get_bboxes` with the head's priors and its decode.
+Reference: dense_heads/base_dense_head.py:22-59 (forward_train), dense_test_mixins.py (simple_test), and the get_bboxes /
+_get_bboxes_single pair that anchor_head.py, fcos_head.py, atss_head.py, gfl_head.py, vfnet_head.py and fovea_head.py each
+restate.  A head gives `forward`, `loss` and `get_bboxes`; the step plumbing, the cache of constants of the pyramid's map shapes
+and get_bboxes are written once, here.
+
+`_get_bboxes` is the whole inference path of RetinaHead, FCOSHead, ATSSHead, GFLHead, VFNetHead and FoveaHead: the dispatch, the
+reference's per-image loop (`_get_bboxes_single`) and the batched form (`_get_bboxes_batched`: one key launch and one segmented
+top-k give every (image, level) cut to nms_pre, one gather, one multiclass NMS over all images).  The decode and the rescale stay
+tensor operations applied image by image, and the loop ranks by the launch form of the batched path, so the two agree bit for
+bit.  A head contributes its priors (`_bbox_priors`, and `_prior_deps` if they depend on more than the map shapes), its decode
+(`_bbox_decode`), `strides`, and -- GFLHead alone -- its own `_keys_and_preds`; a head with a centerness branch passes those maps
+as `score_factors`.
 """
 import torch
 import torch.nn as nn
+
+from .. import mmcv_ops as M
+
+
+def _channels_last(maps):
+    """The key kernels read channels_last maps: any other layout (NCHW-contiguous maps) is converted, not refused."""
+    return [m if M.nhwc_channel_stride(m) is not None else m.contiguous(memory_format=torch.channels_last) for m in maps]
 
 
 class BaseDenseHead(nn.Module):
@@ -44,104 +59,124 @@ class BaseDenseHead(nn.Module):
             cache[key] = make()
         return cache[key]
 
-    # ------------------------------------------------------------------ boxes of a head with a centerness map
-    # One prediction per location (the device forms; several anchors per location take the tensor forms) and a centerness map (fcos_head.py:255-401, atss_head.py:316-469).  `strides`: the pyramid's;
-    # `mlvl_priors()` -> per level the (n_l, 2 or 4) points or anchors, `flat_priors()` -> the same concatenated (a head caches
-    # it); `decode(priors, preds, img_shape)` -> boxes clamped to the image.
-    def _ctr_get_bboxes(self, cls_scores, bbox_preds, centernesses, img_metas, cfg, rescale, with_nms, strides, mlvl_priors,
-                        flat_priors, decode):
-        """-> list (per image) of (dets (k, 5), labels (k,)).  GPU fp32 maps with hard NMS take the batched form; everything
-        else the per-image loop."""
-        from .. import mmcv_ops as M
+    # ------------------------------------------------------------------ boxes
+    num_anchors = 1                     # predictions per location (AnchorHead: its generator's base anchors)
+    use_sigmoid_cls = True              # (AnchorHead: its classification loss's)
+    _prior_deps = ()                    # what the priors depend on besides the map shapes, their dtype and the device
+
+    def _bbox_priors(self, featmap_sizes, dtype, device):
+        """-> per level the (n_l, k) prior rows that `_bbox_decode` takes, one per prediction."""
+        raise NotImplementedError
+
+    def _bbox_decode(self, priors, preds, img_shape):
+        """(n, k) prior rows and their (n, 4) regression rows -> (n, 4) boxes clamped to the image."""
+        raise NotImplementedError
+
+    def _level_cuts(self, cls_scores, nms_pre):
+        """Per level: its number of predictions, how many of them the cut to nms_pre keeps (all when nms_pre <= 0) and its first
+        column in the level-concatenated order."""
+        Ns = [int(c.shape[2] * c.shape[3]) * self.num_anchors for c in cls_scores]
+        ks = [n if nms_pre <= 0 else min(nms_pre, n) for n in Ns]
+        return Ns, ks, [sum(Ns[:l]) for l in range(len(Ns))]
+
+    def _device_keys_ok(self, cls_scores, bbox_preds, score_factors):
+        """htd_retina_keys and htd_fcos_keys take fp32 GPU maps of at most 8 levels under a sigmoid, htd_fcos_keys with one
+        prediction per location; anything else ranks by the tensor operations."""
+        return cls_scores[0].is_cuda and len(cls_scores) <= 8 and self.use_sigmoid_cls and \
+            all(t.dtype == torch.float32 for t in list(cls_scores) + list(score_factors or [])) and \
+            (score_factors is None or self.num_anchors == 1)
+
+    def _keys_and_preds(self, cls_scores, bbox_preds, score_factors, want_keys):
+        """-> (B, total) ranking keys, level-major (None unless want_keys: no level is cut), and the (B, total, 4) regression
+        rows.  The keys are max_c sigmoid(score) (softmax heads: of the foreground classes' softmax), times sigmoid(score factor)
+        where there is one: one launch on the GPU, the reference's tensor operations elsewhere."""
+        B, C = cls_scores[0].size(0), self.cls_out_channels
+        preds = torch.cat([r.permute(0, 2, 3, 1).reshape(B, -1, 4) for r in bbox_preds], 1)
+        if not want_keys:
+            return None, preds
+        if self._device_keys_ok(cls_scores, bbox_preds, score_factors):
+            if score_factors is None:
+                return M.retina_keys(_channels_last(cls_scores), self.num_anchors, C), preds
+            return M.fcos_keys(_channels_last(cls_scores), _channels_last(score_factors), self.strides), preds
+        keys = []
+        for lvl, c in enumerate(cls_scores):
+            s = c.permute(0, 2, 3, 1).reshape(B, -1, C)
+            s = s.sigmoid() if self.use_sigmoid_cls else s.softmax(-1)[..., :-1]
+            if score_factors is not None:
+                s = s * score_factors[lvl].permute(0, 2, 3, 1).reshape(B, -1, 1).sigmoid()
+            keys.append(s.max(dim=-1)[0])
+        return torch.cat(keys, 1), preds
+
+    def _get_bboxes(self, cls_scores, bbox_preds, score_factors, img_metas, cfg, rescale, with_nms):
+        """-> list (per image) of (dets (k, 5), labels (k,)); with_nms=False: of (boxes, scores[, score factors]).  Sigmoid
+        heads on the GPU with fp32 maps and hard NMS take the batched form; everything else the per-image loop."""
         cfg = self.test_cfg if cfg is None else cfg
-        assert len(cls_scores) == len(bbox_preds) == len(centernesses)
+        maps = [None if g is None else [t.detach() for t in g] for g in (cls_scores, bbox_preds, score_factors)]
+        assert all(g is None or len(g) == len(cls_scores) for g in maps)
+        dev = cls_scores[0].device
+        featmap_sizes = [c.shape[-2:] for c in cls_scores]
         nms_pre = cfg.get('nms_pre', -1)
-        Ns = [int(c.shape[2] * c.shape[3]) for c in cls_scores]
-        maps = list(cls_scores) + list(bbox_preds) + list(centernesses)
-        batched = with_nms and cls_scores[0].is_cuda and len(cls_scores) <= 8 and all(t.dtype == torch.float32 for t in maps) and \
-            getattr(self, 'num_anchors', 1) == 1 and \
+        Ns = self._level_cuts(cls_scores, nms_pre)[0]
+        key = (self._shape_key(featmap_sizes), str(dev), bbox_preds[0].dtype, self._prior_deps)
+        priors = self._cached('_prior_cache', 32, key,
+                              lambda: torch.cat(self._bbox_priors(featmap_sizes, bbox_preds[0].dtype, dev)))
+        assert priors.size(0) == sum(Ns)
+        batched = with_nms and self._device_keys_ok(*maps) and all(t.dtype == torch.float32 for g in maps if g for t in g) and \
             cfg.nms.get('type', 'nms') == 'nms' and (nms_pre <= 0 or nms_pre <= M.TOPK_KMAX) and \
             getattr(self, 'batched_get_bboxes', True) and (nms_pre > 0 or max(Ns) <= M.TOPK_KMAX)
         if batched:
-            return self._ctr_bboxes_batched(cls_scores, bbox_preds, centernesses, flat_priors(), decode, strides, img_metas, cfg,
-                                            rescale)
-        priors = mlvl_priors()
-        out = []
-        for b, meta in enumerate(img_metas):
-            out.append(self._ctr_bboxes_single([c[b].detach() for c in cls_scores], [r[b].detach() for r in bbox_preds],
-                                               [t[b].detach() for t in centernesses], priors, decode, strides, meta['img_shape'],
-                                               meta['scale_factor'], cfg, rescale, with_nms))
-        return out
+            return self._get_bboxes_batched(*maps, priors, img_metas, cfg, rescale)
+        return [self._get_bboxes_single(*[g and [t[b:b + 1] for t in g] for g in maps], priors, meta['img_shape'],
+                                        meta['scale_factor'], cfg, rescale, with_nms) for b, meta in enumerate(img_metas)]
 
-    def _ctr_level_keys(self, cls_score_list, centerness_list, strides):
-        """per level (n_l,) max_c sigmoid(score) * sigmoid(centerness): htd_fcos_keys on the GPU (the same launch form as the
-        batched path, so the two rank identically), the reference's tensor operations elsewhere."""
-        from .. import mmcv_ops as M
-        if cls_score_list[0].is_cuda and cls_score_list[0].dtype == torch.float32 and len(cls_score_list) <= 8 and \
-                getattr(self, 'num_anchors', 1) == 1:
-            keys = M.fcos_keys([c[None] for c in cls_score_list], [t[None] for t in centerness_list], strides)[0]
-            return list(keys.split([int(c.shape[1] * c.shape[2]) for c in cls_score_list]))
-        out = []
-        for c, t in zip(cls_score_list, centerness_list):
-            s = c.permute(1, 2, 0).reshape(-1, self.cls_out_channels).sigmoid()
-            out.append((s * t.permute(1, 2, 0).reshape(-1).sigmoid()[:, None]).max(dim=1)[0])
-        return out
-
-    def _ctr_bboxes_single(self, cls_scores, bbox_preds, centernesses, mlvl_priors, decode, strides, img_shape, scale_factor, cfg,
-                           rescale=False, with_nms=True):
-        """fcos_head.py:315-401 / atss_head.py:379-469 for one image."""
+    def _get_bboxes_single(self, cls_scores, bbox_preds, score_factors, priors, img_shape, scale_factor, cfg, rescale=False,
+                           with_nms=True):
+        """The reference's _get_bboxes_single, level by level, for one image: its maps as batches of one."""
         from ..core.post_processing import multiclass_nms
-        cfg = self.test_cfg if cfg is None else cfg
-        assert len(cls_scores) == len(bbox_preds) == len(mlvl_priors)
         nms_pre = cfg.get('nms_pre', -1)
-        keys = self._ctr_level_keys(cls_scores, centernesses, strides) \
-            if nms_pre > 0 and any(p.size(0) > nms_pre for p in mlvl_priors) else None
-        mlvl_bboxes, mlvl_scores, mlvl_centerness = [], [], []
-        for lvl, (cls_score, bbox_pred, centerness, priors) in enumerate(zip(cls_scores, bbox_preds, centernesses, mlvl_priors)):
-            assert cls_score.size()[-2:] == bbox_pred.size()[-2:]
-            scores = cls_score.permute(1, 2, 0).reshape(-1, self.cls_out_channels).sigmoid()
-            centerness = centerness.permute(1, 2, 0).reshape(-1).sigmoid()
-            bbox_pred = bbox_pred.permute(1, 2, 0).reshape(-1, 4)
-            if nms_pre > 0 and scores.shape[0] > nms_pre:
-                # the first nms_pre of the stable descending order (equal keys: lower location index first)
-                topk_inds = keys[lvl].sort(descending=True, stable=True)[1][:nms_pre]
-                priors, bbox_pred = priors[topk_inds, :], bbox_pred[topk_inds, :]
-                scores, centerness = scores[topk_inds, :], centerness[topk_inds]
-            mlvl_bboxes.append(decode(priors, bbox_pred, img_shape))
-            mlvl_scores.append(scores)
-            mlvl_centerness.append(centerness)
-        mlvl_bboxes = torch.cat(mlvl_bboxes)
+        Ns, ks, offs = self._level_cuts(cls_scores, nms_pre)
+        keys, preds = self._keys_and_preds(cls_scores, bbox_preds, score_factors, ks != Ns)
+        mlvl = []
+        for lvl, cls_score in enumerate(cls_scores):
+            assert cls_score.size()[-2:] == bbox_preds[lvl].size()[-2:]
+            at = slice(offs[lvl], offs[lvl] + Ns[lvl])
+            scores = cls_score.permute(0, 2, 3, 1).reshape(-1, self.cls_out_channels)
+            rows = [priors[at], preds[0, at], scores.sigmoid() if self.use_sigmoid_cls else scores.softmax(-1)]
+            if score_factors is not None:
+                rows.append(score_factors[lvl].permute(0, 2, 3, 1).reshape(-1).sigmoid())
+            if ks[lvl] < Ns[lvl]:
+                # the first nms_pre of the stable descending order (equal keys: lower index first)
+                topk_inds = keys[0, at].sort(descending=True, stable=True)[1][:nms_pre]
+                rows = [r[topk_inds] for r in rows]
+            rows[0] = self._bbox_decode(rows[0], rows[1], img_shape)
+            mlvl.append(rows)
+        mlvl_bboxes = torch.cat([r[0] for r in mlvl])
         if rescale:
             mlvl_bboxes = mlvl_bboxes / mlvl_bboxes.new_tensor(scale_factor)
-        mlvl_scores = torch.cat(mlvl_scores)
-        mlvl_scores = torch.cat([mlvl_scores, mlvl_scores.new_zeros(mlvl_scores.shape[0], 1)], dim=1)
-        mlvl_centerness = torch.cat(mlvl_centerness)
+        mlvl_scores = torch.cat([r[2] for r in mlvl])
+        if self.use_sigmoid_cls:
+            mlvl_scores = torch.cat([mlvl_scores, mlvl_scores.new_zeros(mlvl_scores.shape[0], 1)], dim=1)
+        mlvl_factors = None if score_factors is None else torch.cat([r[3] for r in mlvl])
         if with_nms:
-            return multiclass_nms(mlvl_bboxes, mlvl_scores, cfg.score_thr, cfg.nms, cfg.max_per_img, score_factors=mlvl_centerness)
-        return mlvl_bboxes, mlvl_scores, mlvl_centerness
+            return multiclass_nms(mlvl_bboxes, mlvl_scores, cfg.score_thr, cfg.nms, cfg.max_per_img, score_factors=mlvl_factors)
+        return (mlvl_bboxes, mlvl_scores) if score_factors is None else (mlvl_bboxes, mlvl_scores, mlvl_factors)
 
-    def _ctr_bboxes_batched(self, cls_scores, bbox_preds, centernesses, priors, decode, strides, img_metas, cfg, rescale):
-        """The whole batch on the GPU: one key launch (htd_fcos_keys) and one segmented top-k give every (image, level) cut to
-        nms_pre, one gather, one multiclass NMS over all images with the centerness as score factor; the decode stays the
-        head's own, image by image, so the result is bit-identical to the per-image loop."""
-        from .. import mmcv_ops as M
+    def _get_bboxes_batched(self, cls_scores, bbox_preds, score_factors, priors, img_metas, cfg, rescale):
+        """The whole batch on the GPU: one key launch and one segmented top-k give every (image, level) cut to nms_pre, one
+        gather, one multiclass NMS over all images; the decode stays the head's own, image by image, so the result is
+        bit-identical to the per-image loop."""
         from ..core.post_processing import multiclass_nms_images
         B, L = cls_scores[0].size(0), len(cls_scores)
         dev = cls_scores[0].device
         C = self.cls_out_channels
-        nms_pre = cfg.get('nms_pre', -1)
-        Ns = [int(c.shape[2] * c.shape[3]) for c in cls_scores]
-        ks = [n if nms_pre <= 0 else min(nms_pre, n) for n in Ns]
-        offs = [sum(Ns[:l]) for l in range(L)]
+        Ns, ks, offs = self._level_cuts(cls_scores, cfg.get('nms_pre', -1))
         total = sum(Ns)
-        cls_scores = [c.detach() for c in cls_scores]
-        centernesses = [t.detach() for t in centernesses]
         cut = [l for l in range(L) if ks[l] < Ns[l]]
+        keys, preds = self._keys_and_preds(cls_scores, bbox_preds, score_factors, bool(cut))
         pieces = [torch.arange(offs[l], offs[l] + Ns[l], device=dev)[None].expand(B, Ns[l]) for l in range(L)]
         if cut:
-            # every (image, level) cut of the call in one key launch and one segmented top-k; a level that is not cut keeps its
-            # locations in their own order, as the per-image form does
-            keys = M.fcos_keys(cls_scores, centernesses, strides)                     # (B, total)
+            # every (image, level) cut of the call in one segmented top-k; a level that is not cut keeps its predictions in their
+            # own order, as the per-image form does
             top_idx, _ = M.segmented_topk(keys, [(b * total + offs[l], Ns[l], ks[l]) for b in range(B) for l in cut])
             top_idx, at = top_idx.view(B, -1), 0
             for l in cut:
@@ -150,16 +185,17 @@ class BaseDenseHead(nn.Module):
         gidx = torch.cat(pieces, 1)
         K = gidx.size(1)
         logits = torch.cat([c.permute(0, 2, 3, 1).reshape(B, -1, C) for c in cls_scores], 1)
-        preds = torch.cat([r.detach().permute(0, 2, 3, 1).reshape(B, -1, 4) for r in bbox_preds], 1)
-        ctrs = torch.cat([t.permute(0, 2, 3, 1).reshape(B, -1) for t in centernesses], 1)
         scores = torch.gather(logits, 1, gidx[..., None].expand(B, K, C)).sigmoid()
         preds = torch.gather(preds, 1, gidx[..., None].expand(B, K, 4))
-        ctrs = torch.gather(ctrs, 1, gidx).sigmoid()
-        boxes = torch.stack([decode(priors[gidx[b]], preds[b], img_metas[b]['img_shape']) for b in range(B)])
+        factors = None
+        if score_factors is not None:
+            factors = torch.cat([t.permute(0, 2, 3, 1).reshape(B, -1) for t in score_factors], 1)
+            factors = torch.gather(factors, 1, gidx).sigmoid().reshape(B * K)
+        boxes = torch.stack([self._bbox_decode(priors[gidx[b]], preds[b], img_metas[b]['img_shape']) for b in range(B)])
         if rescale:
             boxes = torch.stack([boxes[b] / boxes.new_tensor(img_metas[b]['scale_factor']) for b in range(B)])
         scores = torch.cat([scores, scores.new_zeros(B, K, 1)], dim=2)
         img_of = torch.arange(B, device=dev).repeat_interleave(K)
         dets, labels = multiclass_nms_images(boxes.reshape(B * K, 4), scores.reshape(B * K, C + 1), img_of, B, cfg.score_thr,
-                                             cfg.nms, cfg.max_per_img, score_factors=ctrs.reshape(B * K))
+                                             cfg.nms, cfg.max_per_img, score_factors=factors)
         return list(zip(dets, labels))

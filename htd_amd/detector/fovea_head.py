@@ -20,8 +20,8 @@ more (htd_fovea_loss): no permute, concatenation, gather or nonzero() of the pre
 1 x 1 convolution of exp(bbox_pred); on fp32 channels_last GPU maps one autograd function around htd_fovea_align_fwd / _bwd turns
 the regression logits into the offsets, elsewhere `conv_offset(shape)` is the reference's tensor form.
 
-`get_bboxes` ranks by max_c sigmoid(cls) without a score factor; GPU fp32 maps with hard NMS take the batched form of the other
-dense heads (htd_retina_keys, one segmented top-k, one gather, one NMS over all images), bit for bit the per-image loop.
+`get_bboxes` is BaseDenseHead._get_bboxes, which all dense heads share: it ranks by max_c sigmoid(cls) without a score factor, the
+priors are rows of x, y, stride and base edge, and the decode takes the exp() of the kept predictions.
 """
 import os
 
@@ -228,9 +228,16 @@ class FoveaHead(AnchorFreeHead):
         return dict(loss_cls=loss_cls, loss_bbox=loss_bbox)
 
     # ------------------------------------------------------------------ boxes
-    @staticmethod
-    def _decode(x, y, stride, base_len, bbox_pred, img_shape):
-        """fovea_head.py:319-327: bbox_pred already exponentiated; stride / base_len numbers or per-row tensors."""
+    def _bbox_priors(self, featmap_sizes, dtype, device):
+        """per level (n_l, 4) rows of x, y, stride and base edge: the reference's per-level numbers, one copy per point."""
+        points = self.get_points(featmap_sizes, dtype, device, flatten=True)
+        return [torch.stack([x, y, torch.full_like(x, stride), torch.full_like(x, base_len)], -1)
+                for (y, x), stride, base_len in zip(points, self.strides, self.base_edge_list)]
+
+    def _bbox_decode(self, priors, bbox_pred, img_shape):
+        """fovea_head.py:311,319-327."""
+        x, y, stride, base_len = priors.unbind(-1)
+        bbox_pred = bbox_pred.exp()
         x1 = (stride * x - base_len * bbox_pred[:, 0]).clamp(min=0, max=img_shape[1] - 1)
         y1 = (stride * y - base_len * bbox_pred[:, 1]).clamp(min=0, max=img_shape[0] - 1)
         x2 = (stride * x + base_len * bbox_pred[:, 2]).clamp(min=0, max=img_shape[1] - 1)
@@ -239,110 +246,5 @@ class FoveaHead(AnchorFreeHead):
 
     @torch.no_grad()
     def get_bboxes(self, cls_scores, bbox_preds, img_metas, cfg=None, rescale=None, with_nms=True):
-        """fovea_head.py:260-341 -> list (per image) of (dets (k, 5), labels (k,)).  GPU fp32 maps with hard NMS take the batched
-        form; everything else the per-image loop."""
-        cfg = self.test_cfg if cfg is None else cfg
-        assert len(cls_scores) == len(bbox_preds)
-        featmap_sizes = [c.shape[-2:] for c in cls_scores]
-        nms_pre = cfg.get('nms_pre', -1)
-        Ns = [int(h * w) for h, w in featmap_sizes]
-        batched = with_nms and cls_scores[0].is_cuda and len(cls_scores) <= 8 and \
-            all(t.dtype == torch.float32 for t in list(cls_scores) + list(bbox_preds)) and \
-            cfg.nms.get('type', 'nms') == 'nms' and (nms_pre <= 0 or nms_pre <= M.TOPK_KMAX) and \
-            getattr(self, 'batched_get_bboxes', True) and (nms_pre > 0 or max(Ns) <= M.TOPK_KMAX)
-        if batched:
-            return self._get_bboxes_batched(cls_scores, bbox_preds, img_metas, cfg, rescale)
-        points = self.get_points(featmap_sizes, bbox_preds[0].dtype, bbox_preds[0].device, flatten=True)
-        return [self._get_bboxes_single([c[b].detach() for c in cls_scores], [r[b].detach() for r in bbox_preds], featmap_sizes,
-                                        points, meta['img_shape'], meta['scale_factor'], cfg, rescale, with_nms)
-                for b, meta in enumerate(img_metas)]
-
-    def _level_keys(self, cls_scores):
-        """per level (n_l,) max_c sigmoid(score) of one image: htd_retina_keys on the GPU (the launch form of the batched path,
-        so the two rank identically), tensor operations elsewhere."""
-        if cls_scores[0].is_cuda and cls_scores[0].dtype == torch.float32 and len(cls_scores) <= 8:
-            maps = [c[None] for c in cls_scores]
-            maps = [c.contiguous(memory_format=torch.channels_last) if M.nhwc_channel_stride(c) is None else c for c in maps]
-            keys = M.retina_keys(maps, 1, self.cls_out_channels)[0]
-            return list(keys.split([int(c.shape[1] * c.shape[2]) for c in cls_scores]))
-        return [c.permute(1, 2, 0).reshape(-1, self.cls_out_channels).sigmoid().max(dim=1)[0] for c in cls_scores]
-
-    def _get_bboxes_single(self, cls_scores, bbox_preds, featmap_sizes, point_list, img_shape, scale_factor, cfg, rescale=False,
-                           with_nms=True):
-        """fovea_head.py:291-341 for one image."""
-        from ..core.post_processing import multiclass_nms
-        cfg = self.test_cfg if cfg is None else cfg
-        assert len(cls_scores) == len(bbox_preds) == len(point_list)
-        nms_pre = cfg.get('nms_pre', -1)
-        keys = self._level_keys(cls_scores) if nms_pre > 0 and any(y.size(0) > nms_pre for y, _ in point_list) else None
-        det_bboxes, det_scores = [], []
-        for lvl, (cls_score, bbox_pred, stride, base_len, (y, x)) in enumerate(zip(cls_scores, bbox_preds, self.strides,
-                                                                                  self.base_edge_list, point_list)):
-            assert cls_score.size()[-2:] == bbox_pred.size()[-2:]
-            scores = cls_score.permute(1, 2, 0).reshape(-1, self.cls_out_channels).contiguous().sigmoid()
-            bbox_pred = bbox_pred.permute(1, 2, 0).reshape(-1, 4).contiguous().exp()
-            if 0 < nms_pre < scores.shape[0]:
-                # the first nms_pre of the stable descending order (equal keys: lower location index first)
-                topk_inds = keys[lvl].sort(descending=True, stable=True)[1][:nms_pre]
-                bbox_pred, scores, y, x = bbox_pred[topk_inds, :], scores[topk_inds, :], y[topk_inds], x[topk_inds]
-            det_bboxes.append(self._decode(x, y, stride, base_len, bbox_pred, img_shape))
-            det_scores.append(scores)
-        det_bboxes = torch.cat(det_bboxes)
-        if rescale:
-            det_bboxes = det_bboxes / det_bboxes.new_tensor(scale_factor)
-        det_scores = torch.cat(det_scores)
-        det_scores = torch.cat([det_scores, det_scores.new_zeros(det_scores.shape[0], 1)], dim=1)
-        if with_nms:
-            return multiclass_nms(det_bboxes, det_scores, cfg.score_thr, cfg.nms, cfg.max_per_img)
-        return det_bboxes, det_scores
-
-    def _flat_tables(self, featmap_sizes, dev):
-        """(P,) x, y, stride and base edge of every point, level-major."""
-        pts = self.get_points(featmap_sizes, torch.float32, dev, flatten=True)
-        xs, ys = torch.cat([x for _, x in pts]), torch.cat([y for y, _ in pts])
-        st = torch.cat([torch.full((y.numel(), ), float(s), device=dev) for (y, _), s in zip(pts, self.strides)])
-        be = torch.cat([torch.full((y.numel(), ), float(b), device=dev) for (y, _), b in zip(pts, self.base_edge_list)])
-        return xs, ys, st, be
-
-    def _get_bboxes_batched(self, cls_scores, bbox_preds, img_metas, cfg, rescale):
-        """The whole batch on the GPU: one key launch (htd_retina_keys) and one segmented top-k give every (image, level) cut to
-        nms_pre, one gather, one multiclass NMS over all images without score factors; the decode stays the reference's tensor
-        operations, image by image, so the result is bit-identical to the per-image loop."""
-        from ..core.post_processing import multiclass_nms_images
-        B, L = cls_scores[0].size(0), len(cls_scores)
-        dev = cls_scores[0].device
-        C = self.cls_out_channels
-        featmap_sizes = [c.shape[-2:] for c in cls_scores]
-        nms_pre = cfg.get('nms_pre', -1)
-        Ns = [int(h * w) for h, w in featmap_sizes]
-        ks = [n if nms_pre <= 0 else min(nms_pre, n) for n in Ns]
-        offs = [sum(Ns[:l]) for l in range(L)]
-        total = sum(Ns)
-        cls_scores = [c.detach() for c in cls_scores]
-        xs, ys, st, be = self._cached('_points_cache', 32, (self._shape_key(featmap_sizes), str(dev)),
-                                      lambda: self._flat_tables(featmap_sizes, dev))
-        cut = [l for l in range(L) if ks[l] < Ns[l]]
-        pieces = [torch.arange(offs[l], offs[l] + Ns[l], device=dev)[None].expand(B, Ns[l]) for l in range(L)]
-        if cut:
-            keys = M.retina_keys([c.contiguous(memory_format=torch.channels_last) if M.nhwc_channel_stride(c) is None else c
-                                  for c in cls_scores], 1, C)                        # (B, total)
-            top_idx, _ = M.segmented_topk(keys, [(b * total + offs[l], Ns[l], ks[l]) for b in range(B) for l in cut])
-            top_idx, at = top_idx.view(B, -1), 0
-            for l in cut:
-                pieces[l] = top_idx[:, at:at + ks[l]] + offs[l]
-                at += ks[l]
-        gidx = torch.cat(pieces, 1)
-        K = gidx.size(1)
-        logits = torch.cat([c.permute(0, 2, 3, 1).reshape(B, -1, C) for c in cls_scores], 1)
-        preds = torch.cat([r.detach().permute(0, 2, 3, 1).reshape(B, -1, 4) for r in bbox_preds], 1)
-        scores = torch.gather(logits, 1, gidx[..., None].expand(B, K, C)).sigmoid()
-        preds = torch.gather(preds, 1, gidx[..., None].expand(B, K, 4)).exp()
-        boxes = torch.stack([self._decode(xs[gidx[b]], ys[gidx[b]], st[gidx[b]], be[gidx[b]], preds[b], img_metas[b]['img_shape'])
-                             for b in range(B)])
-        if rescale:
-            boxes = torch.stack([boxes[b] / boxes.new_tensor(img_metas[b]['scale_factor']) for b in range(B)])
-        scores = torch.cat([scores, scores.new_zeros(B, K, 1)], dim=2)
-        img_of = torch.arange(B, device=dev).repeat_interleave(K)
-        dets, labels = multiclass_nms_images(boxes.reshape(B * K, 4), scores.reshape(B * K, C + 1), img_of, B, cfg.score_thr,
-                                             cfg.nms, cfg.max_per_img)
-        return list(zip(dets, labels))
+        """fovea_head.py:260-341 -> list (per image) of (dets (k, 5), labels (k,))."""
+        return self._get_bboxes(cls_scores, bbox_preds, None, img_metas, cfg, rescale, with_nms)

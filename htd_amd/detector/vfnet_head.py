@@ -20,9 +20,8 @@ one pass (htd_vfnet_quality) and the three losses with the three gradient maps o
 that of the whole batch, clamped once -- not AnchorHead's sum of per-image counts clamped per image, which htd_atss_targets
 leaves in norm[0].
 
-`get_bboxes` ranks by max_c sigmoid(cls) without a score factor and decodes the refined distances; GPU fp32 maps with hard NMS
-take the batched form of the other dense heads (htd_retina_keys, one segmented top-k, one gather, one NMS over all images), bit
-for bit the per-image loop.
+`get_bboxes` is BaseDenseHead._get_bboxes, which all dense heads share, on the refined distances: ranked by max_c sigmoid(cls)
+without a score factor (FCOSHead passes one, this head does not), FCOSHead's priors and decode.
 """
 import os
 
@@ -338,102 +337,11 @@ class VFNetHead(FCOSHead):
         return dict(loss_cls=loss_cls, loss_bbox=loss_bbox, loss_bbox_rf=loss_bbox_rf)
 
     # ------------------------------------------------------------------ boxes
+    _prior_deps = property(lambda self: (self.use_atss, ))      # the points sit on the anchor centres under use_atss
+
     @torch.no_grad()
     def get_bboxes(self, cls_scores, bbox_preds, bbox_preds_refine, img_metas, cfg=None, rescale=None, with_nms=True):
-        """vfnet_head.py:465-597 -> list (per image) of (dets (k, 5), labels (k,)) from the refined boxes.  GPU fp32 maps with
-        hard NMS take the batched form; everything else the per-image loop."""
-        cfg = self.test_cfg if cfg is None else cfg
-        assert len(cls_scores) == len(bbox_preds) == len(bbox_preds_refine)
-        featmap_sizes = [c.shape[-2:] for c in cls_scores]
-        dev = cls_scores[0].device
-        nms_pre = cfg.get('nms_pre', -1)
-        Ns = [int(h * w) for h, w in featmap_sizes]
-        batched = with_nms and cls_scores[0].is_cuda and len(cls_scores) <= 8 and \
-            all(t.dtype == torch.float32 for t in list(cls_scores) + list(bbox_preds_refine)) and \
-            cfg.nms.get('type', 'nms') == 'nms' and (nms_pre <= 0 or nms_pre <= M.TOPK_KMAX) and \
-            getattr(self, 'batched_get_bboxes', True) and (nms_pre > 0 or max(Ns) <= M.TOPK_KMAX)
-        if batched:
-            return self._get_bboxes_batched(cls_scores, bbox_preds_refine, img_metas, cfg, rescale)
-        mlvl_points = self.get_points(featmap_sizes, bbox_preds[0].dtype, dev)
-        return [self._get_bboxes_single([c[b].detach() for c in cls_scores], [r[b].detach() for r in bbox_preds_refine],
-                                        mlvl_points, meta['img_shape'], meta['scale_factor'], cfg, rescale, with_nms)
-                for b, meta in enumerate(img_metas)]
-
-    def _level_keys(self, cls_scores):
-        """per level (n_l,) max_c sigmoid(score) of one image: htd_retina_keys on the GPU (the launch form of the batched path,
-        so the two rank identically), tensor operations elsewhere."""
-        if cls_scores[0].is_cuda and cls_scores[0].dtype == torch.float32 and len(cls_scores) <= 8:
-            maps = [c[None] for c in cls_scores]
-            maps = [c.contiguous(memory_format=torch.channels_last) if M.nhwc_channel_stride(c) is None else c for c in maps]
-            keys = M.retina_keys(maps, 1, self.cls_out_channels)[0]
-            return list(keys.split([int(c.shape[1] * c.shape[2]) for c in cls_scores]))
-        return [c.permute(1, 2, 0).reshape(-1, self.cls_out_channels).sigmoid().max(dim=1)[0] for c in cls_scores]
-
-    def _get_bboxes_single(self, cls_scores, bbox_preds, mlvl_points, img_shape, scale_factor, cfg, rescale=False, with_nms=True):
-        """vfnet_head.py:524-597 for one image."""
-        from ..core.post_processing import multiclass_nms
-        cfg = self.test_cfg if cfg is None else cfg
-        assert len(cls_scores) == len(bbox_preds) == len(mlvl_points)
-        nms_pre = cfg.get('nms_pre', -1)
-        keys = self._level_keys(cls_scores) if nms_pre > 0 and any(p.size(0) > nms_pre for p in mlvl_points) else None
-        mlvl_bboxes, mlvl_scores = [], []
-        for lvl, (cls_score, bbox_pred, points) in enumerate(zip(cls_scores, bbox_preds, mlvl_points)):
-            assert cls_score.size()[-2:] == bbox_pred.size()[-2:]
-            scores = cls_score.permute(1, 2, 0).reshape(-1, self.cls_out_channels).contiguous().sigmoid()
-            bbox_pred = bbox_pred.permute(1, 2, 0).reshape(-1, 4).contiguous()
-            if 0 < nms_pre < scores.shape[0]:
-                # the first nms_pre of the stable descending order (equal keys: lower location index first)
-                topk_inds = keys[lvl].sort(descending=True, stable=True)[1][:nms_pre]
-                points, bbox_pred, scores = points[topk_inds, :], bbox_pred[topk_inds, :], scores[topk_inds, :]
-            mlvl_bboxes.append(distance2bbox(points, bbox_pred, max_shape=img_shape))
-            mlvl_scores.append(scores)
-        mlvl_bboxes = torch.cat(mlvl_bboxes)
-        if rescale:
-            mlvl_bboxes = mlvl_bboxes / mlvl_bboxes.new_tensor(scale_factor)
-        mlvl_scores = torch.cat(mlvl_scores)
-        mlvl_scores = torch.cat([mlvl_scores, mlvl_scores.new_zeros(mlvl_scores.shape[0], 1)], dim=1)
-        if with_nms:
-            return multiclass_nms(mlvl_bboxes, mlvl_scores, cfg.score_thr, cfg.nms, cfg.max_per_img)
-        return mlvl_bboxes, mlvl_scores
-
-    def _get_bboxes_batched(self, cls_scores, bbox_preds, img_metas, cfg, rescale):
-        """The whole batch on the GPU: one key launch (htd_retina_keys) and one segmented top-k give every (image, level) cut to
-        nms_pre, one gather, one multiclass NMS over all images without score factors; distance2bbox stays the tensor operation,
-        image by image, so the result is bit-identical to the per-image loop."""
-        from ..core.post_processing import multiclass_nms_images
-        B, L = cls_scores[0].size(0), len(cls_scores)
-        dev = cls_scores[0].device
-        C = self.cls_out_channels
-        featmap_sizes = [c.shape[-2:] for c in cls_scores]
-        nms_pre = cfg.get('nms_pre', -1)
-        Ns = [int(h * w) for h, w in featmap_sizes]
-        ks = [n if nms_pre <= 0 else min(nms_pre, n) for n in Ns]
-        offs = [sum(Ns[:l]) for l in range(L)]
-        total = sum(Ns)
-        cls_scores = [c.detach() for c in cls_scores]
-        points = self._cached('_points_cache', 32, (self._shape_key(featmap_sizes), str(dev), self.use_atss),
-                              lambda: torch.cat(self.get_points(featmap_sizes, torch.float32, dev)))
-        cut = [l for l in range(L) if ks[l] < Ns[l]]
-        pieces = [torch.arange(offs[l], offs[l] + Ns[l], device=dev)[None].expand(B, Ns[l]) for l in range(L)]
-        if cut:
-            keys = M.retina_keys([c.contiguous(memory_format=torch.channels_last) if M.nhwc_channel_stride(c) is None else c
-                                  for c in cls_scores], 1, C)                        # (B, total)
-            top_idx, _ = M.segmented_topk(keys, [(b * total + offs[l], Ns[l], ks[l]) for b in range(B) for l in cut])
-            top_idx, at = top_idx.view(B, -1), 0
-            for l in cut:
-                pieces[l] = top_idx[:, at:at + ks[l]] + offs[l]
-                at += ks[l]
-        gidx = torch.cat(pieces, 1)
-        K = gidx.size(1)
-        logits = torch.cat([c.permute(0, 2, 3, 1).reshape(B, -1, C) for c in cls_scores], 1)
-        dists = torch.cat([r.detach().permute(0, 2, 3, 1).reshape(B, -1, 4) for r in bbox_preds], 1)
-        scores = torch.gather(logits, 1, gidx[..., None].expand(B, K, C)).sigmoid()
-        dists = torch.gather(dists, 1, gidx[..., None].expand(B, K, 4))
-        boxes = torch.stack([distance2bbox(points[gidx[b]], dists[b], max_shape=img_metas[b]['img_shape']) for b in range(B)])
-        if rescale:
-            boxes = torch.stack([boxes[b] / boxes.new_tensor(img_metas[b]['scale_factor']) for b in range(B)])
-        scores = torch.cat([scores, scores.new_zeros(B, K, 1)], dim=2)
-        img_of = torch.arange(B, device=dev).repeat_interleave(K)
-        dets, labels = multiclass_nms_images(boxes.reshape(B * K, 4), scores.reshape(B * K, C + 1), img_of, B, cfg.score_thr,
-                                             cfg.nms, cfg.max_per_img)
-        return list(zip(dets, labels))
+        """vfnet_head.py:465-597 -> list (per image) of (dets (k, 5), labels (k,)) from the refined boxes, ranked by max_c
+        sigmoid(cls) without a score factor."""
+        assert len(bbox_preds) == len(bbox_preds_refine)
+        return self._get_bboxes(cls_scores, bbox_preds_refine, None, img_metas, cfg, rescale, with_nms)

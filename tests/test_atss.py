@@ -274,14 +274,21 @@ def test_per_image_get_bboxes_on_the_cpu_matches_the_reference(golden):
 
 def test_dispatch_rule_and_shared_get_bboxes_code():
     from htd_amd.detector.anchor_free_heads import FCOSHead
-    from htd_amd.detector.anchor_heads import ATSSHead
+    from htd_amd.detector.anchor_heads import ATSSHead, GFLHead, RetinaHead
     from htd_amd.detector.base_dense_head import BaseDenseHead
+    from htd_amd.detector.fovea_head import FoveaHead
+    from htd_amd.detector.vfnet_head import VFNetHead
     metas, gts, labels = inputs()
     head = build_head('giou')
     assert not head._fused_loss_ok(*U.head_maps(), labels, None, metas)            # CPU maps
-    for cls in (ATSSHead, FCOSHead):
-        assert cls._ctr_bboxes_batched is BaseDenseHead._ctr_bboxes_batched and cls._ctr_bboxes_single is BaseDenseHead._ctr_bboxes_single
-        assert '_get_bboxes_batched' not in vars(cls)              # no copy of the batched form beside the shared one
+    shared = ('_get_bboxes', '_get_bboxes_single', '_get_bboxes_batched')
+    assert all(name in vars(BaseDenseHead) for name in shared)
+    for cls in (RetinaHead, FCOSHead, ATSSHead, GFLHead, VFNetHead, FoveaHead):
+        # the dispatch, the per-image loop and the batched form are BaseDenseHead's own objects, and no class between the head
+        # and BaseDenseHead has a copy of them, or of the former key helpers, beside the shared ones
+        assert all(getattr(cls, name) is getattr(BaseDenseHead, name) for name in shared)
+        for klass in cls.__mro__[:cls.__mro__.index(BaseDenseHead)]:
+            assert not [n for n in vars(klass) if n in shared or n.startswith(('_level_keys', '_ctr_'))], klass
     three = build_head('giou', anchor_generator=dict(type='AnchorGenerator', ratios=[0.5, 1.0, 2.0], octave_base_scale=8,
                                                      scales_per_octave=1, strides=list(U.STRIDES)))
     assert three.num_anchors == 3 and three.atss_centerness.weight.size(0) == 3

@@ -526,7 +526,8 @@ def test_towers_on_the_smallest_levels_equal_torch_group_norm(det):
 def test_batched_get_bboxes_equals_the_per_image_loop(det, golden, scale, nms_pre):
     """get_bboxes of the whole batch -- one key launch, one segmented top-k, one NMS with the centerness as score factor -- agrees
     BIT FOR BIT with the per-image loop: B = 2 and B = 5, images of different shapes and scale factors, a blank image, the cuts to
-    nms_pre (and none: nms_pre <= 0) and max_per_img active."""
+    nms_pre (and none: nms_pre <= 0) and max_per_img active.  NCHW-contiguous copies of the maps give, in both forms, exactly
+    what the head's own channels_last maps give."""
     img, _, _, _ = inputs(torch.device(DEV))
     H, W = img.shape[-2:]
     img5 = torch.cat([img, img.flip(0) * 0.5, img[:1] * 0.0])
@@ -545,14 +546,20 @@ def test_batched_get_bboxes_equals_the_per_image_loop(det, golden, scale, nms_pr
         for im, ms in ((img, metas[:2]), (img5, metas)):
             with torch.no_grad():
                 outs = head(det.extract_feat(im))
-                res = {}
+                nchw = [[t.contiguous() for t in maps] for maps in outs]
+                assert not any(maps[0].is_contiguous(memory_format=torch.channels_last) for maps in nchw[:2])
+                res, res_nchw = {}, {}
                 for mode in (True, False):
                     head.batched_get_bboxes = mode
                     res[mode] = head.get_bboxes(*outs, ms, rescale=scale is not None)
+                    res_nchw[mode] = head.get_bboxes(*nchw, ms, rescale=scale is not None)
             counts = [int(d.shape[0]) for d, _ in res[False]]
             assert max(counts) == 9 and sum(counts) >= 18, counts
             for (d1, l1), (d2, l2) in zip(res[True], res[False]):
                 assert torch.equal(d1, d2) and torch.equal(l1, l2)
+            for mode in (True, False):          # NCHW-contiguous copies of the maps: the same detections in both forms
+                for (d1, l1), (d2, l2) in zip(res_nchw[mode], res[mode]):
+                    assert torch.equal(d1, d2) and torch.equal(l1, l2)
     finally:
         head.batched_get_bboxes = True
         head.test_cfg = old_cfg
@@ -606,7 +613,7 @@ def test_transposed_batch_after_a_batch_gives_the_result_of_a_fresh_head(det):
         return out
     fresh = copy.deepcopy(det)
     for m in (det, fresh):
-        m.bbox_head.__dict__.pop('_points_cache', None)
+        m.bbox_head.__dict__.pop('_prior_cache', None)
     a, b = run(det, True), run(fresh, False)
     assert torch.isfinite(a[0]).item() and all(torch.equal(x, y) for x, y in zip(a[:4], b[:4]))
     assert all(np.array_equal(x, y) for x, y in zip(a[4], b[4])) and sum(len(x) for x in a[4]) > 0

@@ -352,7 +352,8 @@ def test_fused_head_loss_matches_tensor_path_bitwise_repeatable_and_reads_nothin
 @pytest.mark.parametrize('scale', ['array', None])
 def test_batched_get_bboxes_equals_the_per_image_loop(det, scale):
     """get_bboxes of the whole batch -- one key launch, one segmented top-k, one NMS -- agrees BIT FOR BIT with the per-image loop:
-    images of different shapes and scale factors, a blank image, the cuts to nms_pre and max_per_img active."""
+    images of different shapes and scale factors, a blank image, the cuts to nms_pre and max_per_img active.  NCHW-contiguous copies
+    of the maps give, in both forms, exactly what the head's own channels_last maps give."""
     img, _, _, _ = inputs(torch.device(DEV))
     H, W = img.shape[-2:]
     img = torch.cat([img, img.flip(0) * 0.5, img[:1] * 0.0])
@@ -368,10 +369,13 @@ def test_batched_get_bboxes_equals_the_per_image_loop(det, scale):
         head.test_cfg.max_per_img = 37
         with torch.no_grad():
             outs = head(det.extract_feat(img))
-            res = {}
+            nchw = [[t.contiguous() for t in maps] for maps in outs]
+            assert not any(maps[0].is_contiguous(memory_format=torch.channels_last) for maps in nchw)
+            res, res_nchw = {}, {}
             for mode in (True, False):
                 head.batched_get_bboxes = mode
                 res[mode] = head.get_bboxes(*outs, metas, rescale=scale is not None)
+                res_nchw[mode] = head.get_bboxes(*nchw, metas, rescale=scale is not None)
     finally:
         head.batched_get_bboxes = True
         head.test_cfg = old_cfg
@@ -379,6 +383,9 @@ def test_batched_get_bboxes_equals_the_per_image_loop(det, scale):
     assert max(counts) == 37 and sum(counts) > 60, counts
     for (d1, l1), (d2, l2) in zip(res[True], res[False]):
         assert torch.equal(d1, d2) and torch.equal(l1, l2)
+    for mode in (True, False):                  # NCHW-contiguous copies of the maps: the same detections in both forms
+        for (d1, l1), (d2, l2) in zip(res_nchw[mode], res[mode]):
+            assert torch.equal(d1, d2) and torch.equal(l1, l2)
 
 
 def test_reference_format_checkpoint_round_trip(golden, tmp_path):
@@ -442,7 +449,7 @@ def test_transposed_batch_after_a_batch_gives_the_result_of_a_fresh_head(det):
     fresh = copy.deepcopy(det)
     for m in (det, fresh):
         m.bbox_head.__dict__.pop('_inside_cache', None)
-        m.bbox_head.__dict__.pop('_bbox_cache', None)
+        m.bbox_head.__dict__.pop('_prior_cache', None)
     a, b = run(det, True), run(fresh, False)
     assert torch.isfinite(a[0]).item() and torch.equal(a[0], b[0]) and torch.equal(a[1], b[1]) and torch.equal(a[2], b[2])
     assert all(np.array_equal(x, y) for x, y in zip(a[3], b[3])) and sum(len(x) for x in a[3]) > 0
