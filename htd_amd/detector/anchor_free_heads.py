@@ -3,8 +3,8 @@
 Reference: dense_heads/anchor_free_head.py:14-340 (towers, predictors, the pre-2.0 key rename, get_points),
 dense_heads/fcos_head.py:14-576 (forward_single, loss, get_bboxes, get_targets, centerness_target), mmcv.cnn.Scale.  Same registry
 names, constructor kwargs, state_dict keys (cls_convs.N.conv/gn, reg_convs.N..., conv_cls, conv_reg, conv_centerness,
-scales.N.scale) and return structures.  forward_train, simple_test and the shape-keyed caches come from BaseDenseHead, which the
-anchor heads extend too.
+scales.N.scale) and return structures.  forward_train, simple_test, the towers (built tower by tower: `_build_towers`), the
+fused losses' rule on the maps and the shape-keyed caches come from BaseDenseHead, which the anchor heads extend too.
 
 `FCOSHead.loss` has two forms, like AnchorHead.loss, and `_fused_loss_ok` is the one rule between them.  `loss_tensor` is the
 reference's order of operations (get_points, get_targets / _get_target_single, centerness_target, distance2bbox, the three loss
@@ -28,7 +28,7 @@ from .. import mmcv_ops as M
 from ..registry import HEADS, build_loss
 from .anchor_heads import bias_init_with_prob
 from .base_dense_head import BaseDenseHead
-from .bricks import Conv2d, ConvModule, normal_init
+from .bricks import Conv2d, normal_init
 
 FCOS_FUSED = os.environ.get('HTD_FCOS_FUSED', '1') != '0'           # 0: the tensor-path loss (A/B runs)
 INF = 1e8
@@ -67,32 +67,12 @@ class AnchorFreeHead(BaseDenseHead):
         self._init_layers()
 
     def _init_layers(self):
-        self.cls_convs = self._tower()
-        self.reg_convs = self._tower()
+        self._build_towers('cls_convs', 'reg_convs')
         self.conv_cls = Conv2d(self.feat_channels, self.cls_out_channels, 3, padding=1)
         self.conv_reg = Conv2d(self.feat_channels, 4, 3, padding=1)
 
-    def _tower(self):
-        """anchor_free_head.py:85-123: stacked_convs ConvModules, the last one a DCNv2 under dcn_on_last_conv."""
-        convs = nn.ModuleList()
-        for i in range(self.stacked_convs):
-            chn = self.in_channels if i == 0 else self.feat_channels
-            dcn = self.dcn_on_last_conv and i == self.stacked_convs - 1
-            try:
-                convs.append(ConvModule(chn, self.feat_channels, 3, stride=1, padding=1,
-                                        conv_cfg=dict(type='DCNv2') if dcn else self.conv_cfg, norm_cfg=self.norm_cfg,
-                                        bias=self.conv_bias))
-            except (KeyError, TypeError) as e:
-                if not dcn:
-                    raise
-                raise NotImplementedError(f"dcn_on_last_conv: a ConvModule with conv_cfg=dict(type='DCNv2') does not build "
-                                          f'({e})') from e
-        return convs
-
     def init_weights(self):
-        for m in list(self.cls_convs) + list(self.reg_convs):
-            if isinstance(m.conv, nn.Conv2d):
-                normal_init(m.conv, std=0.01)
+        self._init_towers()
         normal_init(self.conv_cls, std=0.01, bias=bias_init_with_prob(0.01))
         normal_init(self.conv_reg, std=0.01)
 
@@ -118,13 +98,7 @@ class AnchorFreeHead(BaseDenseHead):
 
     def forward_single(self, x):
         """-> cls_score, bbox_pred and the two tower outputs (FCOS puts the centerness on one of them)."""
-        if x.dtype != torch.float32:             # a bf16 pyramid: the towers and all box / loss arithmetic stay fp32
-            x = x.float()
-        cls_feat = reg_feat = x
-        for layer in self.cls_convs:
-            cls_feat = layer(cls_feat)
-        for layer in self.reg_convs:
-            reg_feat = layer(reg_feat)
+        cls_feat, reg_feat = self._run_towers(x)
         return self.conv_cls(cls_feat), self.conv_reg(reg_feat), cls_feat, reg_feat
 
     def loss(self, cls_scores, bbox_preds, gt_bboxes, gt_labels, img_metas, gt_bboxes_ignore=None):
@@ -266,15 +240,13 @@ class FCOSHead(AnchorFreeHead):
 
     def _fused_loss_ok(self, cls_scores, bbox_preds, centernesses):
         """htd_fcos_loss covers FocalLoss + IoULoss / GIoULoss + sigmoid CrossEntropyLoss without class weight, all with mean
-        reduction, on fp32 channels_last GPU maps of at most 8 levels."""
+        reduction, on maps that `_fused_maps_ok` takes."""
         lc, lb, lt = self.loss_cls, self.loss_bbox, self.loss_centerness
         return getattr(self, 'fused_loss', FCOS_FUSED) and \
             type(lc).__name__ == 'FocalLoss' and lc.reduction == 'mean' and \
             type(lb).__name__ in M.FCOS_BOX_KINDS and lb.reduction == 'mean' and \
             type(lt).__name__ == 'CrossEntropyLoss' and lt.use_sigmoid and lt.reduction == 'mean' and lt.class_weight is None and \
-            len(cls_scores) <= 8 and \
-            all(t.is_cuda and t.dtype == torch.float32 and M.nhwc_channel_stride(t) is not None
-                for t in list(cls_scores) + list(bbox_preds) + list(centernesses))
+            self._fused_maps_ok(cls_scores, bbox_preds, centernesses)
 
     def loss_tensor(self, cls_scores, bbox_preds, centernesses, gt_bboxes, gt_labels, img_metas, gt_bboxes_ignore=None):
         """fcos_head.py:159-253, in the reference's order of operations."""

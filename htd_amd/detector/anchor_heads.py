@@ -5,10 +5,19 @@ base_dense_head.py:22-59 (forward_train), retina_head.py:8-114 (RetinaHead), ats
 (Integral, GFLHead).  Same registry names, constructor kwargs, state_dict keys (cls_convs / reg_convs / retina_cls / retina_reg;
 atss_cls / atss_reg / atss_centerness / scales.N.scale; gfl_cls / gfl_reg / integral.project) and return structures.  AnchorHead is also the base of RPNHead
 (detector/rpn_head.py), as in the reference: anchors, per-image targets (gt_labels None: foreground is class 0), the
-reference-order loss are written once, here; forward_train, simple_test and the cache of constants of the pyramid's map shapes
-(`_shape_key` makes their key, `_cached` fetches them) come from BaseDenseHead (detector/base_dense_head.py), which the
+reference-order loss are written once, here; forward_train, simple_test, the two convolution towers (`_build_towers`,
+`_init_towers`, `_run_towers`), the fused losses' rule on the maps (`_fused_maps_ok`) and the cache of constants of the pyramid's
+map shapes (`_shape_key` makes their key, `_cached` fetches them) come from BaseDenseHead (detector/base_dense_head.py), which the
 anchor-free heads share: `_anchors_inside`, the RPN's proposal constants and the level-concatenated priors of `_get_bboxes` all go
 through the two.
+
+The anchors and their targets live in two mixins, so that the FCOS-shaped VFNetHead inherits them like the anchor heads do.
+`AnchorTargets` (AnchorHead's first base) has `get_anchors`, `_anchors_inside`, the per-image routine `_anchor_targets_single`,
+the batch routine `_anchor_targets` (both with the ATSS family's returns: the anchors first) and `_loss_targets`, the head of
+every `loss_tensor`; its hooks are `_assign` (the assigner's call) and `_pos_bbox_targets`.  `ATSSTargets`, on top of it, is what
+ATSSHead, GFLHead and VFNetHead add: ATSSAssigner's call with the per-level inside counts, `_atss_consts`, the assigner's half of
+the fused-loss rule (`_atss_fused_ok`) and the head of their fused losses (`_atss_fused_targets`).  `get_targets` keeps the
+reference's return structure in every class: six entries in AnchorHead, seven in ATSSHead and GFLHead.
 
 `loss` has two forms, like RPNHead.loss.  The tensor form follows the reference's order of operations (per image targets, per
 level losses) and works with any loss modules, `reg_decoded_bbox`, ignore boxes and on the CPU.  The fused form -- FocalLoss with
@@ -33,7 +42,7 @@ from ..core.misc import const_tensor
 from .. import mmcv_ops as M
 from ..registry import HEADS, build_anchor_generator, build_assigner, build_bbox_coder, build_loss, build_sampler
 from .base_dense_head import BaseDenseHead
-from .bricks import Conv2d, ConvModule, normal_init
+from .bricks import Conv2d, normal_init
 from .losses import GHM_KERNEL_BINS, GHMC, GHMR
 
 RETINA_FUSED = os.environ.get('HTD_RETINA_FUSED', '1') != '0'       # 0: the tensor-path loss (A/B runs)
@@ -48,8 +57,172 @@ def bias_init_with_prob(prior_prob):
     return float(-math.log((1 - prior_prob) / prior_prob))
 
 
+class AnchorTargets:
+    """The anchors of a pyramid and their per-image targets (anchor_head.py:142-371, atss_head.py:471-643), for any head with
+    an `anchor_generator`, `assigner`, `sampler`, `train_cfg`, `num_classes`, `cls_out_channels` and `use_sigmoid_cls`: AnchorHead
+    and, through ATSSTargets, the FCOS-shaped VFNetHead.  Two hooks: `_assign` and `_pos_bbox_targets`."""
+
+    def get_anchors(self, featmap_sizes, img_metas, device='cuda'):
+        mlvl = self.anchor_generator.grid_anchors(featmap_sizes, device)
+        anchor_list = [mlvl for _ in img_metas]
+        valid_flag_list = [self.anchor_generator.valid_flags(featmap_sizes, m['pad_shape'], device) for m in img_metas]
+        return anchor_list, valid_flag_list
+
+    def _anchors_inside(self, featmap_sizes, img_metas, dev):
+        """(A, 4) level-concatenated anchors and the (B, A) mask of anchors that are valid and inside their image
+        (anchor_head.py:200-207, core/anchor/utils.py:20-46): constants of (feature-map sizes, image shapes), cached under
+        exactly those."""
+        border = self.train_cfg.allowed_border
+
+        def make():
+            anchor_list, valid_flag_list = self.get_anchors(featmap_sizes, img_metas, device=dev)
+            flat_anchors = torch.cat(anchor_list[0])
+            valid = torch.stack([torch.cat(v) for v in valid_flag_list])
+            if border >= 0:
+                lim = const_tensor([[m['img_shape'][1], m['img_shape'][0]] for m in img_metas], dev, flat_anchors.dtype)
+                valid = valid & (flat_anchors[None, :, 0] >= -border) & (flat_anchors[None, :, 1] >= -border) & \
+                    (flat_anchors[None, :, 2] < lim[:, 0:1] + border) & (flat_anchors[None, :, 3] < lim[:, 1:2] + border)
+            return flat_anchors, valid
+        key = (self._shape_key(featmap_sizes), tuple((tuple(m['img_shape'][:2]), tuple(m['pad_shape'][:2])) for m in img_metas),
+               str(dev), border)
+        return self._cached('_inside_cache', 64, key, make)
+
+    def _assign(self, anchors, num_level_anchors, inside, gt_bboxes, gt_bboxes_ignore, gt_labels):
+        """MaxIoUAssigner and its kin; a sampling head assigns without labels (anchor_head.py:209-211)."""
+        return self.assigner.assign(anchors, gt_bboxes, gt_bboxes_ignore, None if self.sampling else gt_labels)
+
+    def _pos_bbox_targets(self, sr):
+        """The regression targets of the positives of a sampling result: the coder's deltas, the gt boxes under
+        reg_decoded_bbox (GFLHead and VFNetHead: always the gt boxes)."""
+        return sr.pos_gt_bboxes if self.reg_decoded_bbox else self.bbox_coder.encode(sr.pos_bboxes, sr.pos_gt_bboxes)
+
+    def _anchor_targets_single(self, flat_anchors, valid_flags, num_level_anchors, gt_bboxes, gt_bboxes_ignore, gt_labels,
+                               img_meta, label_channels=1, unmap_outputs=True):
+        """anchor_head.py:172-269 and atss_head.py:535-643 (gfl_head.py:521-625) for one image -> (anchors, labels,
+        label_weights, bbox_targets, bbox_weights, pos_inds, neg_inds).  Only the RPN gives gt_labels as None: foreground is
+        class 0."""
+        inside = anchor_inside_flags(flat_anchors, valid_flags, img_meta['img_shape'][:2], self.train_cfg.allowed_border)
+        if not inside.any():
+            return (None, ) * 7
+        anchors = flat_anchors[inside, :]
+        assign_result = self._assign(anchors, num_level_anchors, inside, gt_bboxes, gt_bboxes_ignore, gt_labels)
+        sr = self.sampler.sample(assign_result, anchors, gt_bboxes)
+        n = anchors.shape[0]
+        bbox_targets = torch.zeros_like(anchors)
+        bbox_weights = torch.zeros_like(anchors)
+        labels = anchors.new_full((n, ), self.num_classes, dtype=torch.long)
+        label_weights = anchors.new_zeros(n, dtype=torch.float)
+        pos_inds, neg_inds = sr.pos_inds, sr.neg_inds
+        if len(pos_inds) > 0:
+            bbox_targets[pos_inds, :] = self._pos_bbox_targets(sr)
+            bbox_weights[pos_inds, :] = 1.0
+            labels[pos_inds] = 0 if gt_labels is None else gt_labels[sr.pos_assigned_gt_inds]
+            label_weights[pos_inds] = 1.0 if self.train_cfg.pos_weight <= 0 else self.train_cfg.pos_weight
+        if len(neg_inds) > 0:
+            label_weights[neg_inds] = 1.0
+        if unmap_outputs:
+            total = flat_anchors.size(0)
+            anchors = unmap(anchors, total, inside)
+            labels = unmap(labels, total, inside, fill=self.num_classes)
+            label_weights = unmap(label_weights, total, inside)
+            bbox_targets = unmap(bbox_targets, total, inside)
+            bbox_weights = unmap(bbox_weights, total, inside)
+        return anchors, labels, label_weights, bbox_targets, bbox_weights, pos_inds, neg_inds
+
+    def _anchor_targets(self, anchor_list, valid_flag_list, gt_bboxes_list, img_metas, gt_bboxes_ignore_list=None,
+                        gt_labels_list=None, label_channels=1, unmap_outputs=True):
+        """anchor_head.py:271-371 and atss_head.py:471-533 -> (anchors, labels, label_weights, bbox_targets, bbox_weights per
+        level, num_total_pos, num_total_neg), or None when an image has no anchor inside."""
+        num_imgs = len(img_metas)
+        assert len(anchor_list) == len(valid_flag_list) == num_imgs
+        num_level_anchors = [a.size(0) for a in anchor_list[0]]
+        concat_anchors = [torch.cat(a) for a in anchor_list]
+        concat_valid = [torch.cat(v) for v in valid_flag_list]
+        if gt_bboxes_ignore_list is None:
+            gt_bboxes_ignore_list = [None] * num_imgs
+        if gt_labels_list is None:
+            gt_labels_list = [None] * num_imgs
+        res = [self._anchor_targets_single(concat_anchors[i], concat_valid[i], num_level_anchors, gt_bboxes_list[i],
+                                           gt_bboxes_ignore_list[i], gt_labels_list[i], img_metas[i], label_channels,
+                                           unmap_outputs) for i in range(num_imgs)]
+        if any(r[0] is None for r in res):
+            return None
+        num_total_pos = sum(max(r[5].numel(), 1) for r in res)
+        num_total_neg = sum(max(r[6].numel(), 1) for r in res)
+        lv = [images_to_levels([r[k] for r in res], num_level_anchors) for k in range(5)]
+        return lv[0], lv[1], lv[2], lv[3], lv[4], num_total_pos, num_total_neg
+
+    def _loss_targets(self, cls_scores, gt_bboxes, gt_labels, img_metas, gt_bboxes_ignore):
+        """The head of every tensor-form loss (anchor_head.py:450-466): the anchors of the maps and the targets of the batch
+        -> (anchor_list, what `_anchor_targets` returns)."""
+        featmap_sizes = [f.size()[-2:] for f in cls_scores]
+        assert len(featmap_sizes) == self.anchor_generator.num_levels
+        anchor_list, valid_flag_list = self.get_anchors(featmap_sizes, img_metas, device=cls_scores[0].device)
+        label_channels = self.cls_out_channels if self.use_sigmoid_cls else 1
+        return anchor_list, self._anchor_targets(anchor_list, valid_flag_list, gt_bboxes, img_metas,
+                                                 gt_bboxes_ignore_list=gt_bboxes_ignore, gt_labels_list=gt_labels,
+                                                 label_channels=label_channels)
+
+
+class ATSSTargets(AnchorTargets):
+    """What ATSSHead, GFLHead and VFNetHead share beyond AnchorTargets: ATSSAssigner's call, the constants, the assigner's half
+    of the fused-loss rule and the head of the fused loss (htd_atss_targets)."""
+
+    def get_num_level_anchors_inside(self, num_level_anchors, inside_flags):
+        return [int(flags.sum()) for flags in torch.split(inside_flags, num_level_anchors)]
+
+    def _assign(self, anchors, num_level_anchors, inside, gt_bboxes, gt_bboxes_ignore, gt_labels):
+        return self.assigner.assign(anchors, self.get_num_level_anchors_inside(num_level_anchors, inside), gt_bboxes,
+                                    gt_bboxes_ignore, gt_labels)
+
+    def _get_target_single(self, *args, **kwargs):
+        """The per-image routine under the reference's name (atss_head.py:535, gfl_head.py:521)."""
+        return self._anchor_targets_single(*args, **kwargs)
+
+    def get_targets(self, *args, **kwargs):
+        """atss_head.py:471-533, gfl_head.py:455-519 -> (anchors, labels, label_weights, bbox_targets, bbox_weights per level,
+        num_total_pos, num_total_neg)."""
+        return self._anchor_targets(*args, **kwargs)
+
+    def _atss_consts(self, featmap_sizes, img_metas, dev):
+        """-> (A, 4) level-concatenated anchors and whether every anchor of every image is valid and inside (a host bool, read
+        once per (map sizes, image shapes))."""
+        def make():
+            flat_anchors, inside = self._anchors_inside(featmap_sizes, img_metas, dev)
+            return flat_anchors.float().contiguous(), bool(inside.all())
+        key = (self._shape_key(featmap_sizes), tuple((tuple(m['img_shape'][:2]), tuple(m['pad_shape'][:2])) for m in img_metas),
+               str(dev), self.train_cfg.allowed_border)
+        return self._cached('_atss_cache', 64, key, make)
+
+    def _atss_fused_ok(self, cls_scores, gt_labels, gt_bboxes_ignore, img_metas):
+        """htd_atss_targets covers one anchor per location (several tie in distance), ATSSAssigner with topk <= 16 and no ignore
+        threshold, no ignore boxes, label weight 1 on positives (pos_weight <= 0: the kernels have no other) and -- last, a host
+        read on a cache miss -- every anchor valid and inside."""
+        a = getattr(self, 'assigner', None)
+        return gt_labels is not None and gt_bboxes_ignore is None and self.num_anchors == 1 and \
+            type(a).__name__ == 'ATSSAssigner' and a.ignore_iof_thr <= 0 and a.topk <= 16 and self.train_cfg.pos_weight <= 0 and \
+            self._atss_consts([f.size()[-2:] for f in cls_scores], img_metas, cls_scores[0].device)[1]
+
+    def _atss_fused_targets(self, cls_scores, gt_bboxes, gt_labels, img_metas, means_stds=(), reduce_norm=True):
+        """The head of every fused ATSS-family loss: the batch assigned in one launch, nothing read back -> flat anchors, padded
+        gts and labels, assigned, ctr_targets (of the coder given by `means_stds`: ATSSHead alone), num_pos, norm."""
+        import torch.distributed as dist
+        from ..core.bbox import pad_gt_batch
+        featmap_sizes = [f.size()[-2:] for f in cls_scores]
+        assert len(featmap_sizes) == self.anchor_generator.num_levels
+        flat_anchors, _ = self._atss_consts(featmap_sizes, img_metas, cls_scores[0].device)
+        gts, gt_valid, labels = pad_gt_batch(gt_bboxes, gt_labels)
+        assigned, ctr_targets, num_pos, norm = M.atss_targets(flat_anchors, [int(h * w) for h, w in featmap_sizes], gts, gt_valid,
+                                                              self.assigner.topk, *means_stds)
+        if reduce_norm and dist.is_available() and dist.is_initialized():
+            # atss_head.py:271-273,288, gfl_head.py:347-350: both factors averaged over the processes, the sample count at least 1
+            norm = reduce_mean(norm)
+            norm = torch.cat([norm[:2].clamp(min=1.0), norm[2:]])
+        return flat_anchors, gts, labels, assigned, ctr_targets, num_pos, norm
+
+
 @HEADS.register_module()
-class AnchorHead(BaseDenseHead):
+class AnchorHead(AnchorTargets, BaseDenseHead):
     def __init__(self, num_classes, in_channels, feat_channels=256,
                  anchor_generator=dict(type='AnchorGenerator', scales=[8, 16, 32], ratios=[0.5, 1.0, 2.0],
                                        strides=[4, 8, 16, 32, 64]),
@@ -98,70 +271,11 @@ class AnchorHead(BaseDenseHead):
         return multi_apply(self.forward_single, feats)
 
     # ------------------------------------------------------------------ targets
-    def get_anchors(self, featmap_sizes, img_metas, device='cuda'):
-        mlvl = self.anchor_generator.grid_anchors(featmap_sizes, device)
-        anchor_list = [mlvl for _ in img_metas]
-        valid_flag_list = [self.anchor_generator.valid_flags(featmap_sizes, m['pad_shape'], device) for m in img_metas]
-        return anchor_list, valid_flag_list
-
-    def _get_targets_single(self, flat_anchors, valid_flags, gt_bboxes, gt_bboxes_ignore, gt_labels, img_meta,
-                            label_channels=1, unmap_outputs=True):
-        """anchor_head.py:172-269."""
-        inside = anchor_inside_flags(flat_anchors, valid_flags, img_meta['img_shape'][:2], self.train_cfg.allowed_border)
-        if not inside.any():
-            return (None, ) * 7
-        anchors = flat_anchors[inside, :]
-        assign_result = self.assigner.assign(anchors, gt_bboxes, gt_bboxes_ignore, None if self.sampling else gt_labels)
-        sr = self.sampler.sample(assign_result, anchors, gt_bboxes)
-        n = anchors.shape[0]
-        bbox_targets = torch.zeros_like(anchors)
-        bbox_weights = torch.zeros_like(anchors)
-        labels = anchors.new_full((n, ), self.num_classes, dtype=torch.long)
-        label_weights = anchors.new_zeros(n, dtype=torch.float)
-        pos_inds, neg_inds = sr.pos_inds, sr.neg_inds
-        if len(pos_inds) > 0:
-            if not self.reg_decoded_bbox:
-                pos_bbox_targets = self.bbox_coder.encode(sr.pos_bboxes, sr.pos_gt_bboxes)
-            else:
-                pos_bbox_targets = sr.pos_gt_bboxes
-            bbox_targets[pos_inds, :] = pos_bbox_targets
-            bbox_weights[pos_inds, :] = 1.0
-            if gt_labels is None:
-                labels[pos_inds] = 0        # only the RPN gives gt_labels as None: foreground is class 0
-            else:
-                labels[pos_inds] = gt_labels[sr.pos_assigned_gt_inds]
-            label_weights[pos_inds] = 1.0 if self.train_cfg.pos_weight <= 0 else self.train_cfg.pos_weight
-        if len(neg_inds) > 0:
-            label_weights[neg_inds] = 1.0
-        if unmap_outputs:
-            total = flat_anchors.size(0)
-            labels = unmap(labels, total, inside, fill=self.num_classes)
-            label_weights = unmap(label_weights, total, inside)
-            bbox_targets = unmap(bbox_targets, total, inside)
-            bbox_weights = unmap(bbox_weights, total, inside)
-        return labels, label_weights, bbox_targets, bbox_weights, pos_inds, neg_inds, sr
-
-    def get_targets(self, anchor_list, valid_flag_list, gt_bboxes_list, img_metas, gt_bboxes_ignore_list=None,
-                    gt_labels_list=None, label_channels=1, unmap_outputs=True):
+    def get_targets(self, *args, **kwargs):
         """anchor_head.py:271-371 -> (labels, label_weights, bbox_targets, bbox_weights per level, num_total_pos,
-        num_total_neg)."""
-        num_imgs = len(img_metas)
-        assert len(anchor_list) == len(valid_flag_list) == num_imgs
-        num_level_anchors = [a.size(0) for a in anchor_list[0]]
-        concat_anchors = [torch.cat(a) for a in anchor_list]
-        concat_valid = [torch.cat(v) for v in valid_flag_list]
-        if gt_bboxes_ignore_list is None:
-            gt_bboxes_ignore_list = [None] * num_imgs
-        if gt_labels_list is None:
-            gt_labels_list = [None] * num_imgs
-        res = [self._get_targets_single(concat_anchors[i], concat_valid[i], gt_bboxes_list[i], gt_bboxes_ignore_list[i],
-                                        gt_labels_list[i], img_metas[i], label_channels, unmap_outputs) for i in range(num_imgs)]
-        if any(r[0] is None for r in res):
-            return None
-        num_total_pos = sum(max(r[4].numel(), 1) for r in res)
-        num_total_neg = sum(max(r[5].numel(), 1) for r in res)
-        lv = [images_to_levels([r[k] for r in res], num_level_anchors) for k in range(4)]
-        return lv[0], lv[1], lv[2], lv[3], num_total_pos, num_total_neg
+        num_total_neg): `_anchor_targets` without the anchors."""
+        targets = self._anchor_targets(*args, **kwargs)
+        return None if targets is None else targets[1:]
 
     # ------------------------------------------------------------------ loss
     def loss_single(self, cls_score, bbox_pred, anchors, labels, label_weights, bbox_targets, bbox_weights, num_total_samples):
@@ -185,16 +299,10 @@ class AnchorHead(BaseDenseHead):
 
     def loss_tensor(self, cls_scores, bbox_preds, gt_bboxes, gt_labels, img_metas, gt_bboxes_ignore=None):
         """anchor_head.py:420-488, in the reference's order of operations."""
-        featmap_sizes = [f.size()[-2:] for f in cls_scores]
-        assert len(featmap_sizes) == self.anchor_generator.num_levels
-        device = cls_scores[0].device
-        anchor_list, valid_flag_list = self.get_anchors(featmap_sizes, img_metas, device=device)
-        label_channels = self.cls_out_channels if self.use_sigmoid_cls else 1
-        targets = self.get_targets(anchor_list, valid_flag_list, gt_bboxes, img_metas, gt_bboxes_ignore_list=gt_bboxes_ignore,
-                                   gt_labels_list=gt_labels, label_channels=label_channels)
+        anchor_list, targets = self._loss_targets(cls_scores, gt_bboxes, gt_labels, img_metas, gt_bboxes_ignore)
         if targets is None:
             return None
-        labels, label_weights, bbox_targets, bbox_weights, num_total_pos, num_total_neg = targets
+        _, labels, label_weights, bbox_targets, bbox_weights, num_total_pos, num_total_neg = targets
         num_total_samples = num_total_pos + num_total_neg if self.sampling else num_total_pos
         num_level_anchors = [a.size(0) for a in anchor_list[0]]
         all_anchors = images_to_levels([torch.cat(a) for a in anchor_list], num_level_anchors)
@@ -213,34 +321,12 @@ class AnchorHead(BaseDenseHead):
         return getattr(self, 'fused_loss', RETINA_FUSED) and gt_labels is not None and gt_bboxes_ignore is None and \
             (focal or self._ghm_pair()) and not self.reg_decoded_bbox and \
             type(a).__name__ == 'MaxIoUAssigner' and a.ignore_iof_thr <= 0 and isinstance(a.neg_iou_thr, float) and \
-            (a.gt_max_assign_all or not a.match_low_quality) and len(cls_scores) <= 8 and \
-            all(t.is_cuda and t.dtype == torch.float32 and M.nhwc_channel_stride(t) is not None
-                for t in list(cls_scores) + list(bbox_preds))       # (other layouts, e.g. NCHW-contiguous maps: the tensor path)
+            (a.gt_max_assign_all or not a.match_low_quality) and self._fused_maps_ok(cls_scores, bbox_preds)
 
     def _ghm_pair(self):
         lc, lb = self.loss_cls, self.loss_bbox
         return type(lc) is GHMC and type(lb) is GHMR and lc.bins <= GHM_KERNEL_BINS and lb.bins <= GHM_KERNEL_BINS and \
             lc.edges.is_cuda and lb.edges.is_cuda
-
-    # ------------------------------------------------------------------ constants of the map shapes
-    def _anchors_inside(self, featmap_sizes, img_metas, dev):
-        """(A, 4) level-concatenated anchors and the (B, A) mask of anchors that are valid and inside their image
-        (anchor_head.py:200-207, core/anchor/utils.py:20-46): constants of (feature-map sizes, image shapes), cached under
-        exactly those."""
-        border = self.train_cfg.allowed_border
-
-        def make():
-            anchor_list, valid_flag_list = self.get_anchors(featmap_sizes, img_metas, device=dev)
-            flat_anchors = torch.cat(anchor_list[0])
-            valid = torch.stack([torch.cat(v) for v in valid_flag_list])
-            if border >= 0:
-                lim = const_tensor([[m['img_shape'][1], m['img_shape'][0]] for m in img_metas], dev, flat_anchors.dtype)
-                valid = valid & (flat_anchors[None, :, 0] >= -border) & (flat_anchors[None, :, 1] >= -border) & \
-                    (flat_anchors[None, :, 2] < lim[:, 0:1] + border) & (flat_anchors[None, :, 3] < lim[:, 1:2] + border)
-            return flat_anchors, valid
-        key = (self._shape_key(featmap_sizes), tuple((tuple(m['img_shape'][:2]), tuple(m['pad_shape'][:2])) for m in img_metas),
-               str(dev), border)
-        return self._cached('_inside_cache', 64, key, make)
 
     def loss_fused(self, cls_scores, bbox_preds, gt_bboxes, gt_labels, img_metas):
         from ..core.bbox import batched_max_iou_assign, pad_gt_batch
@@ -295,38 +381,22 @@ class RetinaHead(AnchorHead):
 
     def _init_layers(self):
         self.relu = nn.ReLU(inplace=True)
-        self.cls_convs = nn.ModuleList()
-        self.reg_convs = nn.ModuleList()
-        for i in range(self.stacked_convs):
-            chn = self.in_channels if i == 0 else self.feat_channels
-            self.cls_convs.append(ConvModule(chn, self.feat_channels, 3, stride=1, padding=1, conv_cfg=self.conv_cfg,
-                                             norm_cfg=self.norm_cfg))
-            self.reg_convs.append(ConvModule(chn, self.feat_channels, 3, stride=1, padding=1, conv_cfg=self.conv_cfg,
-                                             norm_cfg=self.norm_cfg))
+        self._build_towers('cls_convs', 'reg_convs', interleaved=True)
         self.retina_cls = Conv2d(self.feat_channels, self.num_anchors * self.cls_out_channels, 3, padding=1)
         self.retina_reg = Conv2d(self.feat_channels, self.num_anchors * 4, 3, padding=1)
 
     def init_weights(self):
-        for m in self.cls_convs:
-            normal_init(m.conv, std=0.01)
-        for m in self.reg_convs:
-            normal_init(m.conv, std=0.01)
+        self._init_towers()
         normal_init(self.retina_cls, std=0.01, bias=bias_init_with_prob(0.01))
         normal_init(self.retina_reg, std=0.01)
 
     def forward_single(self, x):
-        if x.dtype != torch.float32:             # a bf16 pyramid: the towers and all box / loss arithmetic stay fp32
-            x = x.float()
-        cls_feat = reg_feat = x
-        for cls_conv in self.cls_convs:
-            cls_feat = cls_conv(cls_feat)
-        for reg_conv in self.reg_convs:
-            reg_feat = reg_conv(reg_feat)
+        cls_feat, reg_feat = self._run_towers(x)
         return self.retina_cls(cls_feat), self.retina_reg(reg_feat)
 
 
 @HEADS.register_module()
-class ATSSHead(AnchorHead):
+class ATSSHead(ATSSTargets, AnchorHead):
     """dense_heads/atss_head.py:15-650: the towers of RetinaHead under GroupNorm, a centerness branch on the regression tower,
     one learnable scale per level, ATSSAssigner in place of MaxIoUAssigner and a centerness-weighted IoU-family box loss on
     decoded boxes.
@@ -354,22 +424,14 @@ class ATSSHead(AnchorHead):
     def _init_layers(self):
         from .anchor_free_heads import Scale
         self.relu = nn.ReLU(inplace=True)
-        self.cls_convs = nn.ModuleList()
-        self.reg_convs = nn.ModuleList()
-        for i in range(self.stacked_convs):
-            chn = self.in_channels if i == 0 else self.feat_channels
-            self.cls_convs.append(ConvModule(chn, self.feat_channels, 3, stride=1, padding=1, conv_cfg=self.conv_cfg,
-                                             norm_cfg=self.norm_cfg))
-            self.reg_convs.append(ConvModule(chn, self.feat_channels, 3, stride=1, padding=1, conv_cfg=self.conv_cfg,
-                                             norm_cfg=self.norm_cfg))
+        self._build_towers('cls_convs', 'reg_convs', interleaved=True)
         self.atss_cls = Conv2d(self.feat_channels, self.num_anchors * self.cls_out_channels, 3, padding=1)
         self.atss_reg = Conv2d(self.feat_channels, self.num_anchors * 4, 3, padding=1)
         self.atss_centerness = Conv2d(self.feat_channels, self.num_anchors * 1, 3, padding=1)
         self.scales = nn.ModuleList([Scale(1.0) for _ in self.anchor_generator.strides])
 
     def init_weights(self):
-        for m in list(self.cls_convs) + list(self.reg_convs):
-            normal_init(m.conv, std=0.01)
+        self._init_towers()
         normal_init(self.atss_cls, std=0.01, bias=bias_init_with_prob(0.01))
         normal_init(self.atss_reg, std=0.01)
         normal_init(self.atss_centerness, std=0.01)
@@ -380,13 +442,7 @@ class ATSSHead(AnchorHead):
 
     def forward_single(self, x, scale):
         """atss_head.py:116-143 -> cls_score, bbox_pred (scaled, no exp), centerness (on the regression tower)."""
-        if x.dtype != torch.float32:             # a bf16 pyramid: the towers and all box / loss arithmetic stay fp32
-            x = x.float()
-        cls_feat = reg_feat = x
-        for cls_conv in self.cls_convs:
-            cls_feat = cls_conv(cls_feat)
-        for reg_conv in self.reg_convs:
-            reg_feat = reg_conv(reg_feat)
+        cls_feat, reg_feat = self._run_towers(x)
         return self.atss_cls(cls_feat), scale(self.atss_reg(reg_feat)).float(), self.atss_centerness(reg_feat)
 
     # ------------------------------------------------------------------ targets
@@ -399,67 +455,9 @@ class ATSSHead(AnchorHead):
         return torch.sqrt((left_right.min(dim=-1)[0] / left_right.max(dim=-1)[0]) *
                           (top_bottom.min(dim=-1)[0] / top_bottom.max(dim=-1)[0]))
 
-    def get_num_level_anchors_inside(self, num_level_anchors, inside_flags):
-        return [int(flags.sum()) for flags in torch.split(inside_flags, num_level_anchors)]
-
     def _pos_bbox_targets(self, sr):
-        """The regression targets of the positives of a sampling result: the coder's deltas (GFLHead: the gt boxes)."""
+        """The coder's deltas, whatever reg_decoded_bbox says (atss_head.py:606-611): centerness_target decodes them."""
         return self.bbox_coder.encode(sr.pos_bboxes, sr.pos_gt_bboxes)
-
-    def _get_target_single(self, flat_anchors, valid_flags, num_level_anchors, gt_bboxes, gt_bboxes_ignore, gt_labels, img_meta,
-                           label_channels=1, unmap_outputs=True):
-        """atss_head.py:535-643 for one image (gfl_head.py:521-625 with GFLHead's _pos_bbox_targets)."""
-        inside = anchor_inside_flags(flat_anchors, valid_flags, img_meta['img_shape'][:2], self.train_cfg.allowed_border)
-        if not inside.any():
-            return (None, ) * 7
-        anchors = flat_anchors[inside, :]
-        num_level_anchors_inside = self.get_num_level_anchors_inside(num_level_anchors, inside)
-        assign_result = self.assigner.assign(anchors, num_level_anchors_inside, gt_bboxes, gt_bboxes_ignore, gt_labels)
-        sr = self.sampler.sample(assign_result, anchors, gt_bboxes)
-        n = anchors.shape[0]
-        bbox_targets = torch.zeros_like(anchors)
-        bbox_weights = torch.zeros_like(anchors)
-        labels = anchors.new_full((n, ), self.num_classes, dtype=torch.long)
-        label_weights = anchors.new_zeros(n, dtype=torch.float)
-        pos_inds, neg_inds = sr.pos_inds, sr.neg_inds
-        if len(pos_inds) > 0:
-            bbox_targets[pos_inds, :] = self._pos_bbox_targets(sr)
-            bbox_weights[pos_inds, :] = 1.0
-            labels[pos_inds] = 0 if gt_labels is None else gt_labels[sr.pos_assigned_gt_inds]
-            label_weights[pos_inds] = 1.0 if self.train_cfg.pos_weight <= 0 else self.train_cfg.pos_weight
-        if len(neg_inds) > 0:
-            label_weights[neg_inds] = 1.0
-        if unmap_outputs:
-            total = flat_anchors.size(0)
-            anchors = unmap(anchors, total, inside)
-            labels = unmap(labels, total, inside, fill=self.num_classes)
-            label_weights = unmap(label_weights, total, inside)
-            bbox_targets = unmap(bbox_targets, total, inside)
-            bbox_weights = unmap(bbox_weights, total, inside)
-        return anchors, labels, label_weights, bbox_targets, bbox_weights, pos_inds, neg_inds
-
-    def get_targets(self, anchor_list, valid_flag_list, gt_bboxes_list, img_metas, gt_bboxes_ignore_list=None,
-                    gt_labels_list=None, label_channels=1, unmap_outputs=True):
-        """atss_head.py:471-533 -> (anchors, labels, label_weights, bbox_targets, bbox_weights per level, num_total_pos,
-        num_total_neg)."""
-        num_imgs = len(img_metas)
-        assert len(anchor_list) == len(valid_flag_list) == num_imgs
-        num_level_anchors = [a.size(0) for a in anchor_list[0]]
-        concat_anchors = [torch.cat(a) for a in anchor_list]
-        concat_valid = [torch.cat(v) for v in valid_flag_list]
-        if gt_bboxes_ignore_list is None:
-            gt_bboxes_ignore_list = [None] * num_imgs
-        if gt_labels_list is None:
-            gt_labels_list = [None] * num_imgs
-        res = [self._get_target_single(concat_anchors[i], concat_valid[i], num_level_anchors, gt_bboxes_list[i],
-                                       gt_bboxes_ignore_list[i], gt_labels_list[i], img_metas[i], label_channels, unmap_outputs)
-               for i in range(num_imgs)]
-        if any(r[1] is None for r in res):
-            return None
-        num_total_pos = sum(max(r[5].numel(), 1) for r in res)
-        num_total_neg = sum(max(r[6].numel(), 1) for r in res)
-        lv = [images_to_levels([r[k] for r in res], num_level_anchors) for k in range(5)]
-        return lv[0], lv[1], lv[2], lv[3], lv[4], num_total_pos, num_total_neg
 
     # ------------------------------------------------------------------ loss
     def loss_single(self, anchors, cls_score, bbox_pred, centerness, labels, label_weights, bbox_targets, num_total_samples):
@@ -494,17 +492,11 @@ class ATSSHead(AnchorHead):
 
     def loss_tensor(self, cls_scores, bbox_preds, centernesses, gt_bboxes, gt_labels, img_metas, gt_bboxes_ignore=None):
         """atss_head.py:220-295, in the reference's order of operations."""
-        featmap_sizes = [f.size()[-2:] for f in cls_scores]
-        assert len(featmap_sizes) == self.anchor_generator.num_levels
-        device = cls_scores[0].device
-        anchor_list, valid_flag_list = self.get_anchors(featmap_sizes, img_metas, device=device)
-        label_channels = self.cls_out_channels if self.use_sigmoid_cls else 1
-        targets = self.get_targets(anchor_list, valid_flag_list, gt_bboxes, img_metas, gt_bboxes_ignore_list=gt_bboxes_ignore,
-                                   gt_labels_list=gt_labels, label_channels=label_channels)
+        _, targets = self._loss_targets(cls_scores, gt_bboxes, gt_labels, img_metas, gt_bboxes_ignore)
         if targets is None:
             return None
         anchors, labels, label_weights, bbox_targets, _, num_total_pos, _ = targets
-        num_total_samples = float(reduce_mean(torch.tensor(float(num_total_pos), device=device)))
+        num_total_samples = float(reduce_mean(torch.tensor(float(num_total_pos), device=cls_scores[0].device)))
         num_total_samples = max(num_total_samples, 1.0)
         losses_cls, losses_bbox, loss_centerness, bbox_avg_factor = multi_apply(
             self.loss_single, anchors, cls_scores, bbox_preds, centernesses, labels, label_weights, bbox_targets,
@@ -515,51 +507,24 @@ class ATSSHead(AnchorHead):
         losses_bbox = [x / bbox_avg_factor for x in losses_bbox]
         return dict(loss_cls=losses_cls, loss_bbox=losses_bbox, loss_centerness=loss_centerness)
 
-    def _atss_consts(self, featmap_sizes, img_metas, dev):
-        """-> (A, 4) level-concatenated anchors and whether every anchor of every image is valid and inside (a host bool, read
-        once per (map sizes, image shapes))."""
-        def make():
-            flat_anchors, inside = self._anchors_inside(featmap_sizes, img_metas, dev)
-            return flat_anchors.float().contiguous(), bool(inside.all())
-        key = (self._shape_key(featmap_sizes), tuple((tuple(m['img_shape'][:2]), tuple(m['pad_shape'][:2])) for m in img_metas),
-               str(dev), self.train_cfg.allowed_border)
-        return self._cached('_atss_cache', 64, key, make)
-
     def _fused_loss_ok(self, cls_scores, bbox_preds, centernesses, gt_labels, gt_bboxes_ignore, img_metas):
-        """htd_atss_targets / htd_atss_loss cover one anchor per location (several tie in distance), every anchor valid and
-        inside, no ignore boxes, label weight 1 on positives (pos_weight <= 0: the kernel has no other), sigmoid FocalLoss +
-        IoULoss / GIoULoss + sigmoid CrossEntropyLoss without class weight, all with mean reduction, a DeltaXYWHBBoxCoder and fp32 channels_last GPU maps of at most 8 levels."""
+        """htd_atss_targets / htd_atss_loss cover sigmoid FocalLoss + IoULoss / GIoULoss + sigmoid CrossEntropyLoss without class
+        weight, all with mean reduction, and a DeltaXYWHBBoxCoder, on maps that `_fused_maps_ok` takes, under the assigner's
+        conditions (`_atss_fused_ok`)."""
         lc, lb, lt = self.loss_cls, self.loss_bbox, self.loss_centerness
-        a = getattr(self, 'assigner', None)
-        ok = getattr(self, 'fused_loss', ATSS_FUSED) and gt_labels is not None and gt_bboxes_ignore is None and \
-            self.num_anchors == 1 and type(a).__name__ == 'ATSSAssigner' and a.ignore_iof_thr <= 0 and a.topk <= 16 and \
+        return getattr(self, 'fused_loss', ATSS_FUSED) and \
             type(lc).__name__ == 'FocalLoss' and lc.use_sigmoid and lc.reduction == 'mean' and \
-            self.train_cfg.pos_weight <= 0 and \
             type(lb).__name__ in M.FCOS_BOX_KINDS and lb.reduction == 'mean' and \
             type(lt).__name__ == 'CrossEntropyLoss' and lt.use_sigmoid and lt.reduction == 'mean' and lt.class_weight is None and \
-            type(self.bbox_coder).__name__ == 'DeltaXYWHBBoxCoder' and not self.reg_decoded_bbox and len(cls_scores) <= 8 and \
-            all(t.is_cuda and t.dtype == torch.float32 and M.nhwc_channel_stride(t) is not None
-                for t in list(cls_scores) + list(bbox_preds) + list(centernesses))
-        if not ok:
-            return False
-        return self._atss_consts([f.size()[-2:] for f in cls_scores], img_metas, cls_scores[0].device)[1]
+            type(self.bbox_coder).__name__ == 'DeltaXYWHBBoxCoder' and not self.reg_decoded_bbox and \
+            self._fused_maps_ok(cls_scores, bbox_preds, centernesses) and \
+            self._atss_fused_ok(cls_scores, gt_labels, gt_bboxes_ignore, img_metas)
 
     def loss_fused(self, cls_scores, bbox_preds, centernesses, gt_bboxes, gt_labels, img_metas):
-        import torch.distributed as dist
-        from ..core.bbox import pad_gt_batch
-        featmap_sizes = [f.size()[-2:] for f in cls_scores]
-        assert len(featmap_sizes) == self.anchor_generator.num_levels
-        flat_anchors, _ = self._atss_consts(featmap_sizes, img_metas, cls_scores[0].device)
-        gts, gt_valid, labels = pad_gt_batch(gt_bboxes, gt_labels)
         means, stds = tuple(self.bbox_coder.means), tuple(self.bbox_coder.stds)
-        targets = M.atss_targets(flat_anchors, [int(h * w) for h, w in featmap_sizes], gts, gt_valid, self.assigner.topk, means, stds)
-        assigned, ctr_targets, num_pos, norm = targets
-        if dist.is_available() and dist.is_initialized():
-            # atss_head.py:271-273,288: both factors averaged over the processes, the sample count at least 1
-            norm = reduce_mean(norm)
-            norm = torch.cat([norm[:2].clamp(min=1.0), norm[2:]])
-            targets = (assigned, ctr_targets, num_pos, norm)
-        self._last_targets = targets            # exposed for tests
+        flat_anchors, gts, labels, assigned, ctr_targets, num_pos, norm = self._atss_fused_targets(
+            cls_scores, gt_bboxes, gt_labels, img_metas, (means, stds))
+        self._last_targets = (assigned, ctr_targets, num_pos, norm)            # exposed for tests
         lc, lb = self.loss_cls, self.loss_bbox
         loss_cls, loss_bbox, loss_centerness = M.atss_loss(
             cls_scores, bbox_preds, centernesses, self.anchor_generator.strides, flat_anchors, gts, labels, assigned, ctr_targets,
@@ -590,7 +555,7 @@ class Integral(nn.Module):
 
 
 @HEADS.register_module()
-class GFLHead(AnchorHead):
+class GFLHead(ATSSTargets, AnchorHead):
     """dense_heads/gfl_head.py:51-632: ATSSHead's towers, assigner and one-anchor pyramid with a joint class / quality score
     under QualityFocalLoss in place of the centerness branch, and a discrete distribution of reg_max + 1 bins per side under
     DistributionFocalLoss, plus an IoU-family loss on its integral, in place of the four deltas.  The targets are the gt boxes.
@@ -621,22 +586,14 @@ class GFLHead(AnchorHead):
     def _init_layers(self):
         from .anchor_free_heads import Scale
         self.relu = nn.ReLU(inplace=True)
-        self.cls_convs = nn.ModuleList()
-        self.reg_convs = nn.ModuleList()
-        for i in range(self.stacked_convs):
-            chn = self.in_channels if i == 0 else self.feat_channels
-            self.cls_convs.append(ConvModule(chn, self.feat_channels, 3, stride=1, padding=1, conv_cfg=self.conv_cfg,
-                                             norm_cfg=self.norm_cfg))
-            self.reg_convs.append(ConvModule(chn, self.feat_channels, 3, stride=1, padding=1, conv_cfg=self.conv_cfg,
-                                             norm_cfg=self.norm_cfg))
+        self._build_towers('cls_convs', 'reg_convs', interleaved=True)
         assert self.num_anchors == 1, 'anchor free version'
         self.gfl_cls = Conv2d(self.feat_channels, self.cls_out_channels, 3, padding=1)
         self.gfl_reg = Conv2d(self.feat_channels, 4 * (self.reg_max + 1), 3, padding=1)
         self.scales = nn.ModuleList([Scale(1.0) for _ in self.anchor_generator.strides])
 
     def init_weights(self):
-        for m in list(self.cls_convs) + list(self.reg_convs):
-            normal_init(m.conv, std=0.01)
+        self._init_towers()
         normal_init(self.gfl_cls, std=0.01, bias=bias_init_with_prob(0.01))
         normal_init(self.gfl_reg, std=0.01)
 
@@ -646,27 +603,16 @@ class GFLHead(AnchorHead):
 
     def forward_single(self, x, scale):
         """gfl_head.py:170-194 -> cls_score (class / quality logits), bbox_pred (scaled distribution logits)."""
-        if x.dtype != torch.float32:             # a bf16 pyramid: the towers and all box / loss arithmetic stay fp32
-            x = x.float()
-        cls_feat = reg_feat = x
-        for cls_conv in self.cls_convs:
-            cls_feat = cls_conv(cls_feat)
-        for reg_conv in self.reg_convs:
-            reg_feat = reg_conv(reg_feat)
+        cls_feat, reg_feat = self._run_towers(x)
         return self.gfl_cls(cls_feat), scale(self.gfl_reg(reg_feat)).float()
 
     def anchor_center(self, anchors):
         """gfl_head.py:196-207: (N, 4) anchors -> (N, 2) centres."""
         return torch.stack([(anchors[:, 2] + anchors[:, 0]) / 2, (anchors[:, 3] + anchors[:, 1]) / 2], dim=-1)
 
-    # ------------------------------------------------------------------ targets (ATSSHead's, with the gt boxes as targets)
+    # ------------------------------------------------------------------ targets (ATSSTargets', with the gt boxes as targets)
     def _pos_bbox_targets(self, sr):
         return sr.pos_gt_bboxes
-
-    get_num_level_anchors_inside = ATSSHead.get_num_level_anchors_inside
-    _get_target_single = ATSSHead._get_target_single
-    get_targets = ATSSHead.get_targets
-    _atss_consts = ATSSHead._atss_consts
 
     # ------------------------------------------------------------------ loss
     def loss_single(self, anchors, cls_score, bbox_pred, labels, label_weights, bbox_targets, stride, num_total_samples):
@@ -709,17 +655,11 @@ class GFLHead(AnchorHead):
 
     def loss_tensor(self, cls_scores, bbox_preds, gt_bboxes, gt_labels, img_metas, gt_bboxes_ignore=None):
         """gfl_head.py:297-369, in the reference's order of operations; the averaging factor is not clamped."""
-        featmap_sizes = [f.size()[-2:] for f in cls_scores]
-        assert len(featmap_sizes) == self.anchor_generator.num_levels
-        device = cls_scores[0].device
-        anchor_list, valid_flag_list = self.get_anchors(featmap_sizes, img_metas, device=device)
-        label_channels = self.cls_out_channels if self.use_sigmoid_cls else 1
-        targets = self.get_targets(anchor_list, valid_flag_list, gt_bboxes, img_metas, gt_bboxes_ignore_list=gt_bboxes_ignore,
-                                   gt_labels_list=gt_labels, label_channels=label_channels)
+        _, targets = self._loss_targets(cls_scores, gt_bboxes, gt_labels, img_metas, gt_bboxes_ignore)
         if targets is None:
             return None
         anchors, labels, label_weights, bbox_targets, _, num_total_pos, _ = targets
-        num_total_samples = float(reduce_mean(torch.tensor(float(num_total_pos), device=device)))
+        num_total_samples = float(reduce_mean(torch.tensor(float(num_total_pos), device=cls_scores[0].device)))
         num_total_samples = max(num_total_samples, 1.0)
         losses_cls, losses_bbox, losses_dfl, avg_factor = multi_apply(
             self.loss_single, anchors, cls_scores, bbox_preds, labels, label_weights, bbox_targets, self.anchor_generator.strides,
@@ -730,42 +670,24 @@ class GFLHead(AnchorHead):
         return dict(loss_cls=losses_cls, loss_bbox=losses_bbox, loss_dfl=losses_dfl)
 
     def _fused_loss_ok(self, cls_scores, bbox_preds, gt_labels, gt_bboxes_ignore, img_metas):
-        """htd_atss_targets / htd_gfl_quality / htd_gfl_loss cover one anchor per location, every anchor valid and inside, no
-        ignore boxes, label weight 1 on positives (pos_weight <= 0), ATSSAssigner with topk <= 16, QualityFocalLoss +
-        DistributionFocalLoss + IoULoss / GIoULoss all with mean reduction, reg_max <= 31 and fp32 channels_last GPU maps of at
-        most 8 levels."""
+        """htd_atss_targets / htd_gfl_quality / htd_gfl_loss cover QualityFocalLoss + DistributionFocalLoss + IoULoss / GIoULoss
+        all with mean reduction and reg_max <= 31, on maps that `_fused_maps_ok` takes, under the assigner's conditions
+        (`_atss_fused_ok`)."""
         lc, lb, ld = self.loss_cls, self.loss_bbox, self.loss_dfl
-        a = getattr(self, 'assigner', None)
-        ok = getattr(self, 'fused_loss', GFL_FUSED) and gt_labels is not None and gt_bboxes_ignore is None and \
-            self.num_anchors == 1 and type(a).__name__ == 'ATSSAssigner' and a.ignore_iof_thr <= 0 and a.topk <= 16 and \
+        return getattr(self, 'fused_loss', GFL_FUSED) and \
             type(lc).__name__ == 'QualityFocalLoss' and lc.use_sigmoid and lc.reduction == 'mean' and \
-            self.train_cfg.pos_weight <= 0 and \
             type(lb).__name__ in M.FCOS_BOX_KINDS and lb.reduction == 'mean' and \
-            type(ld).__name__ == 'DistributionFocalLoss' and ld.reduction == 'mean' and \
-            1 <= self.reg_max <= 31 and len(cls_scores) <= 8 and \
-            all(t.is_cuda and t.dtype == torch.float32 and M.nhwc_channel_stride(t) is not None
-                for t in list(cls_scores) + list(bbox_preds))
-        if not ok:
-            return False
-        return self._atss_consts([f.size()[-2:] for f in cls_scores], img_metas, cls_scores[0].device)[1]
+            type(ld).__name__ == 'DistributionFocalLoss' and ld.reduction == 'mean' and 1 <= self.reg_max <= 31 and \
+            self._fused_maps_ok(cls_scores, bbox_preds) and self._atss_fused_ok(cls_scores, gt_labels, gt_bboxes_ignore, img_metas)
 
     def loss_fused(self, cls_scores, bbox_preds, gt_bboxes, gt_labels, img_metas):
         import torch.distributed as dist
-        from ..core.bbox import pad_gt_batch
-        featmap_sizes = [f.size()[-2:] for f in cls_scores]
-        assert len(featmap_sizes) == self.anchor_generator.num_levels
-        flat_anchors, _ = self._atss_consts(featmap_sizes, img_metas, cls_scores[0].device)
-        gts, gt_valid, labels = pad_gt_batch(gt_bboxes, gt_labels)
+        flat_anchors, gts, labels, assigned, _, num_pos, norm = self._atss_fused_targets(cls_scores, gt_bboxes, gt_labels, img_metas)
         strides = self.anchor_generator.strides
-        assigned, _, num_pos, norm = M.atss_targets(flat_anchors, [int(h * w) for h, w in featmap_sizes], gts, gt_valid,
-                                                    self.assigner.topk)
         weight, score, wsum = M.gfl_quality([c.detach() for c in cls_scores], [r.detach() for r in bbox_preds], strides,
                                             self.reg_max, flat_anchors, gts, assigned)
         if dist.is_available() and dist.is_initialized():
-            # gfl_head.py:347-350,364-365: both factors averaged over the processes, the sample count at least 1
-            norm = reduce_mean(norm)
-            norm = torch.cat([norm[:2].clamp(min=1.0), norm[2:]])
-            wsum = reduce_mean(wsum)
+            wsum = reduce_mean(wsum)            # gfl_head.py:364-365
         self._last_targets = (assigned, num_pos, norm)          # exposed for tests
         self._last_quality = (weight, score, wsum)
         lc, lb = self.loss_cls, self.loss_bbox

@@ -3,8 +3,13 @@ heads share.
 
 Reference: dense_heads/base_dense_head.py:22-59 (forward_train), dense_test_mixins.py (simple_test), and the get_bboxes /
 _get_bboxes_single pair that anchor_head.py, fcos_head.py, atss_head.py, gfl_head.py, vfnet_head.py and fovea_head.py each
-restate.  A head gives `forward`, `loss` and `get_bboxes`; the step plumbing, the cache of constants of the pyramid's map shapes
-and get_bboxes are written once, here.
+restate.  A head gives `forward`, `loss` and `get_bboxes`; the step plumbing, the cache of constants of the pyramid's map shapes,
+the two convolution towers and get_bboxes are written once, here.
+
+The towers of RetinaHead, ATSSHead, GFLHead, AnchorFreeHead / FCOSHead and VFNetHead are built by `_build_towers` (in each head's
+own seeded order), initialised by `_init_towers` and run by `_run_towers`; FoveaHead builds its plain towers with the first and
+keeps its own forward order.  `_fused_maps_ok` is the one statement of what the fused loss kernels ask of the maps; a head's
+`_fused_loss_ok` is its own loss modules' conditions beside one call of it.
 
 `_get_bboxes` is the whole inference path of RetinaHead, FCOSHead, ATSSHead, GFLHead, VFNetHead and FoveaHead: the dispatch, the
 reference's per-image loop (`_get_bboxes_single`) and the batched form (`_get_bboxes_batched`: one key launch and one segmented
@@ -18,6 +23,7 @@ import torch
 import torch.nn as nn
 
 from .. import mmcv_ops as M
+from .bricks import ConvModule, normal_init
 
 
 def _channels_last(maps):
@@ -58,6 +64,55 @@ class BaseDenseHead(nn.Module):
                 cache.clear()
             cache[key] = make()
         return cache[key]
+
+    # ------------------------------------------------------------------ towers
+    conv_bias = 'auto'                  # what ConvModule takes when no bias is passed (AnchorFreeHead: a constructor kwarg)
+    dcn_on_last_conv = False            # (AnchorFreeHead: a constructor kwarg)
+
+    def _build_towers(self, *names, interleaved=False):
+        """self.<name> for every name: a ModuleList of stacked_convs ConvModules, the last one a DCNv2 under dcn_on_last_conv
+        (anchor_free_head.py:85-123, retina_head.py:61-84).  A ConvModule draws from the RNG when it is built, so the order is
+        part of a seeded head: tower by tower (the anchor-free heads), or `interleaved` layer by layer (the anchor heads)."""
+        towers = [nn.ModuleList() for _ in names]
+        layers = range(self.stacked_convs)
+        for tower, i in ([(t, i) for i in layers for t in towers] if interleaved else [(t, i) for t in towers for i in layers]):
+            chn = self.in_channels if i == 0 else self.feat_channels
+            dcn = self.dcn_on_last_conv and i == self.stacked_convs - 1
+            try:
+                tower.append(ConvModule(chn, self.feat_channels, 3, stride=1, padding=1,
+                                        conv_cfg=dict(type='DCNv2') if dcn else self.conv_cfg, norm_cfg=self.norm_cfg,
+                                        bias=self.conv_bias))
+            except (KeyError, TypeError) as e:
+                if not dcn:
+                    raise
+                raise NotImplementedError(f"dcn_on_last_conv: a ConvModule with conv_cfg=dict(type='DCNv2') does not build "
+                                          f'({e})') from e
+        for name, tower in zip(names, towers):
+            setattr(self, name, tower)
+
+    def _init_towers(self):
+        for m in list(self.cls_convs) + list(self.reg_convs):
+            if isinstance(m.conv, nn.Conv2d):
+                normal_init(m.conv, std=0.01)
+
+    def _run_towers(self, x):
+        """One level's map through cls_convs and through reg_convs -> (cls_feat, reg_feat)."""
+        if x.dtype != torch.float32:             # a bf16 pyramid: the towers and all box / loss arithmetic stay fp32
+            x = x.float()
+        cls_feat = reg_feat = x
+        for layer in self.cls_convs:
+            cls_feat = layer(cls_feat)
+        for layer in self.reg_convs:
+            reg_feat = layer(reg_feat)
+        return cls_feat, reg_feat
+
+    # ------------------------------------------------------------------ the fused losses' rule on the maps
+    @staticmethod
+    def _fused_maps_ok(*groups):
+        """The fused loss kernels of every dense head read fp32 channels_last GPU maps (or channel slices of them) of at most 8
+        levels where they are; any other layout, NCHW-contiguous maps included, takes the tensor path."""
+        return len(groups[0]) <= 8 and \
+            all(t.is_cuda and t.dtype == torch.float32 and M.nhwc_channel_stride(t) is not None for g in groups for t in g)
 
     # ------------------------------------------------------------------ boxes
     num_anchors = 1                     # predictions per location (AnchorHead: its generator's base anchors)

@@ -83,10 +83,10 @@ class FoveaHead(AnchorFreeHead):
 
     def _init_layers(self):
         """fovea_head.py:65-103."""
-        self.reg_convs = self._tower()
+        self._build_towers('reg_convs')
         self.conv_reg = Conv2d(self.feat_channels, 4, 3, padding=1)
         if not self.with_deform:
-            self.cls_convs = self._tower()
+            self._build_towers('cls_convs')
             self.conv_cls = Conv2d(self.feat_channels, self.cls_out_channels, 3, padding=1)
         else:
             wide = self.feat_channels * 4
@@ -182,15 +182,12 @@ class FoveaHead(AnchorFreeHead):
         return self.loss_tensor(cls_scores, bbox_preds, gt_bbox_list, gt_label_list, img_metas, gt_bboxes_ignore)
 
     def _fused_loss_ok(self, cls_scores, bbox_preds):
-        """htd_fovea_loss covers FocalLoss + SmoothL1Loss, both with mean reduction, on fp32 channels_last GPU maps of at most 8
-        levels."""
+        """htd_fovea_loss covers FocalLoss + SmoothL1Loss, both with mean reduction, on maps that `_fused_maps_ok` takes."""
         lc, lb = self.loss_cls, self.loss_bbox
         return getattr(self, 'fused_loss', FOVEA_FUSED) and \
             type(lc).__name__ == 'FocalLoss' and lc.reduction == 'mean' and \
             type(lb).__name__ == 'SmoothL1Loss' and lb.reduction == 'mean' and lb.beta > 0 and \
-            0 <= self.sigma <= 1 and len(cls_scores) <= 8 and \
-            all(t.is_cuda and t.dtype == torch.float32 and M.nhwc_channel_stride(t) is not None
-                for t in list(cls_scores) + list(bbox_preds))
+            0 <= self.sigma <= 1 and self._fused_maps_ok(cls_scores, bbox_preds)
 
     def loss_tensor(self, cls_scores, bbox_preds, gt_bbox_list, gt_label_list, img_metas, gt_bboxes_ignore=None):
         """fovea_head.py:127-175, in the reference's order of operations."""

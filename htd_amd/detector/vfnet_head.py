@@ -6,8 +6,9 @@ registry name, constructor kwargs and defaults, `reg_denoms`, `dcn_base_offset`,
 reg_convs.N..., vfnet_reg_conv.conv/gn, vfnet_reg, scales.N.scale, vfnet_reg_refine_dconv.weight, vfnet_reg_refine,
 scales_refine.N.scale, vfnet_cls_dconv.weight, vfnet_cls) and return structures.
 
-The head is FCOS-shaped (AnchorFreeHead's towers, one Scale per level, points) and borrows ATSSHead's target routines for its
-positives; the targets of the positives are the gt boxes themselves (no coder).  Its two deformable convolutions
+The head is FCOS-shaped (the towers, one Scale per level, points) and inherits the anchors, their targets and the ATSS half of
+the fused loss from the mixin ATSSHead and GFLHead take them from (`VFNetHead(ATSSTargets, FCOSHead)`); the targets of the
+positives are the gt boxes themselves (no coder).  Its two deformable convolutions
 (htd_amd.dcn.deform_conv2d with the ReLU in the epilogue) share one offset tensor that is not predicted but built from the
 initial box: on fp32 GPU maps one autograd function around htd_vfnet_star_fwd / _bwd turns the scaled regression logits into
 `bbox_pred` and `dcn_offset` together; `star_dcn_offset` is the reference's tensor form (CPU, fp64).
@@ -34,14 +35,14 @@ from .. import mmcv_ops as M
 from ..dcn import DeformConv2d, deform_conv2d
 from ..registry import HEADS, build_anchor_generator, build_assigner, build_loss, build_sampler
 from .anchor_free_heads import INF, AnchorFreeHead, FCOSHead, Scale
-from .anchor_heads import AnchorHead, ATSSHead, bias_init_with_prob
+from .anchor_heads import ATSSTargets, bias_init_with_prob
 from .bricks import Conv2d, ConvModule, normal_init
 
 VFNET_FUSED = os.environ.get('HTD_VFNET_FUSED', '1') != '0'         # 0: the tensor-path loss and star offsets (A/B runs)
 
 
 @HEADS.register_module()
-class VFNetHead(FCOSHead):
+class VFNetHead(ATSSTargets, FCOSHead):
     def __init__(self, num_classes, in_channels, regress_ranges=((-1, 64), (64, 128), (128, 256), (256, 512), (512, INF)),
                  center_sampling=False, center_sample_radius=1.5, sync_num_pos=True, gradient_mul=0.1, bbox_norm_type='reg_denom',
                  loss_cls_fl=dict(type='FocalLoss', use_sigmoid=True, gamma=2.0, alpha=0.25, loss_weight=1.0), use_vfl=True,
@@ -84,8 +85,7 @@ class VFNetHead(FCOSHead):
             self.sampler = build_sampler(dict(type='PseudoSampler'), context=self)
 
     def _init_layers(self):
-        self.cls_convs = self._tower()
-        self.reg_convs = self._tower()
+        self._build_towers('cls_convs', 'reg_convs')
         self.relu = nn.ReLU(inplace=True)
         self.vfnet_reg_conv = ConvModule(self.feat_channels, self.feat_channels, 3, stride=1, padding=1, conv_cfg=self.conv_cfg,
                                          norm_cfg=self.norm_cfg, bias=self.conv_bias)
@@ -98,9 +98,7 @@ class VFNetHead(FCOSHead):
         self.vfnet_cls = Conv2d(self.feat_channels, self.cls_out_channels, 3, padding=1)
 
     def init_weights(self):
-        for m in list(self.cls_convs) + list(self.reg_convs):
-            if isinstance(m.conv, nn.Conv2d):
-                normal_init(m.conv, std=0.01)
+        self._init_towers()
         normal_init(self.vfnet_reg_conv.conv, std=0.01)
         normal_init(self.vfnet_reg, std=0.01)
         normal_init(self.vfnet_reg_refine_dconv, std=0.01)
@@ -122,13 +120,7 @@ class VFNetHead(FCOSHead):
 
     def forward_single(self, x, scale, scale_refine, stride, reg_denom):
         """vfnet_head.py:217-273 -> cls_score, bbox_pred, bbox_pred_refine (both distances in image units)."""
-        if x.dtype != torch.float32:             # a bf16 pyramid: the towers and all box / loss arithmetic stay fp32
-            x = x.float()
-        cls_feat = reg_feat = x
-        for cls_layer in self.cls_convs:
-            cls_feat = cls_layer(cls_feat)
-        for reg_layer in self.reg_convs:
-            reg_feat = reg_layer(reg_feat)
+        cls_feat, reg_feat = self._run_towers(x)
         # predict the bbox_pred of different level
         reg_feat_init = self.vfnet_reg_conv(reg_feat)
         denom = reg_denom if self.bbox_norm_type == 'reg_denom' else stride
@@ -185,17 +177,14 @@ class VFNetHead(FCOSHead):
         points = torch.stack((x.reshape(-1), y.reshape(-1)), dim=-1)
         return points + (stride * self.anchor_center_offset if self.use_atss else stride // 2)
 
-    get_anchors = AnchorHead.get_anchors
-    _anchors_inside = AnchorHead._anchors_inside
-    _atss_consts = ATSSHead._atss_consts
-    get_num_level_anchors_inside = ATSSHead.get_num_level_anchors_inside
-
     def _pos_bbox_targets(self, sr):
         return sr.pos_gt_bboxes
 
     def _get_target_single(self, *args, **kwargs):
+        """vfnet_head.py:657-662: ATSSTargets' per-image routine under use_atss, FCOSHead's (which its get_targets calls)
+        otherwise."""
         if self.use_atss:
-            return ATSSHead._get_target_single(self, *args, **kwargs)
+            return super()._get_target_single(*args, **kwargs)
         return FCOSHead._get_target_single(self, *args, **kwargs)
 
     def get_targets(self, cls_scores, mlvl_points, gt_bboxes, gt_labels, img_metas, gt_bboxes_ignore):
@@ -212,14 +201,7 @@ class VFNetHead(FCOSHead):
 
     def get_atss_targets(self, cls_scores, mlvl_points, gt_bboxes, gt_labels, img_metas, gt_bboxes_ignore=None):
         """vfnet_head.py:690-763."""
-        featmap_sizes = [featmap.size()[-2:] for featmap in cls_scores]
-        assert len(featmap_sizes) == self.anchor_generator.num_levels
-        device = cls_scores[0].device
-        anchor_list, valid_flag_list = self.get_anchors(featmap_sizes, img_metas, device=device)
-        label_channels = self.cls_out_channels if self.use_sigmoid_cls else 1
-        targets = ATSSHead.get_targets(self, anchor_list, valid_flag_list, gt_bboxes, img_metas,
-                                       gt_bboxes_ignore_list=gt_bboxes_ignore, gt_labels_list=gt_labels,
-                                       label_channels=label_channels, unmap_outputs=True)
+        _, targets = self._loss_targets(cls_scores, gt_bboxes, gt_labels, img_metas, gt_bboxes_ignore)
         if targets is None:
             return None
         _, labels_list, label_weights_list, bbox_targets_list, bbox_weights_list, _, _ = targets
@@ -293,35 +275,23 @@ class VFNetHead(FCOSHead):
         return dict(loss_cls=loss_cls, loss_bbox=loss_bbox, loss_bbox_rf=loss_bbox_refine)
 
     def _fused_loss_ok(self, cls_scores, bbox_preds, bbox_preds_refine, gt_labels, gt_bboxes_ignore, img_metas):
-        """htd_atss_targets / htd_vfnet_quality / htd_vfnet_loss cover ATSS targets under VarifocalLoss: one anchor per location,
-        every anchor valid and inside, no ignore boxes, label weight 1 on positives (pos_weight <= 0), ATSSAssigner with topk <=
-        16 and no ignore threshold, sigmoid VarifocalLoss and two IoULoss / GIoULoss all with mean reduction, the number of
-        positives synchronised (its clamp to 1 is part of the kernel) and fp32 channels_last GPU maps of at most 8 levels."""
+        """htd_atss_targets / htd_vfnet_quality / htd_vfnet_loss cover ATSS targets under sigmoid VarifocalLoss and two IoULoss /
+        GIoULoss, all with mean reduction, the number of positives synchronised (its clamp to 1 is part of the kernel), on maps
+        that `_fused_maps_ok` takes, under the assigner's conditions (`_atss_fused_ok`)."""
         lc, lb, lr = self.loss_cls, self.loss_bbox, self.loss_bbox_refine
-        a = getattr(self, 'assigner', None)
-        ok = getattr(self, 'fused_loss', VFNET_FUSED) and self.use_atss and self.use_vfl and self.sync_num_pos and \
-            gt_labels is not None and gt_bboxes_ignore is None and \
-            self.num_anchors == 1 and type(a).__name__ == 'ATSSAssigner' and a.ignore_iof_thr <= 0 and a.topk <= 16 and \
+        return getattr(self, 'fused_loss', VFNET_FUSED) and self.use_atss and self.use_vfl and self.sync_num_pos and \
             type(lc).__name__ == 'VarifocalLoss' and lc.use_sigmoid and lc.reduction == 'mean' and \
-            self.train_cfg.pos_weight <= 0 and \
             type(lb).__name__ in M.FCOS_BOX_KINDS and lb.reduction == 'mean' and \
-            type(lr).__name__ in M.FCOS_BOX_KINDS and lr.reduction == 'mean' and len(cls_scores) <= 8 and \
-            all(t.is_cuda and t.dtype == torch.float32 and M.nhwc_channel_stride(t) is not None
-                for t in list(cls_scores) + list(bbox_preds) + list(bbox_preds_refine))
-        if not ok:
-            return False
-        return self._atss_consts([f.size()[-2:] for f in cls_scores], img_metas, cls_scores[0].device)[1]
+            type(lr).__name__ in M.FCOS_BOX_KINDS and lr.reduction == 'mean' and \
+            self._fused_maps_ok(cls_scores, bbox_preds, bbox_preds_refine) and \
+            self._atss_fused_ok(cls_scores, gt_labels, gt_bboxes_ignore, img_metas)
 
     def loss_fused(self, cls_scores, bbox_preds, bbox_preds_refine, gt_bboxes, gt_labels, img_metas):
         import torch.distributed as dist
-        from ..core.bbox import pad_gt_batch
         assert len(cls_scores) == len(bbox_preds) == len(bbox_preds_refine)
-        featmap_sizes = [f.size()[-2:] for f in cls_scores]
-        assert len(featmap_sizes) == self.anchor_generator.num_levels
-        flat_anchors, _ = self._atss_consts(featmap_sizes, img_metas, cls_scores[0].device)
-        gts, gt_valid, labels = pad_gt_batch(gt_bboxes, gt_labels)
-        assigned, _, num_pos, norm = M.atss_targets(flat_anchors, [int(h * w) for h, w in featmap_sizes], gts, gt_valid,
-                                                    self.assigner.topk)
+        # `norm` stays this process's own: the head takes none of it, it averages the sums of its quality pass below
+        flat_anchors, gts, labels, assigned, _, num_pos, norm = self._atss_fused_targets(cls_scores, gt_bboxes, gt_labels, img_metas,
+                                                                                        reduce_norm=False)
         iou_ini, iou_rf, sums = M.vfnet_quality([r.detach() for r in bbox_preds], [r.detach() for r in bbox_preds_refine],
                                                 flat_anchors, gts, assigned)
         if dist.is_available() and dist.is_initialized():

@@ -294,6 +294,51 @@ def test_dispatch_rule_and_shared_get_bboxes_code():
     assert three.num_anchors == 3 and three.atss_centerness.weight.size(0) == 3
 
 
+def test_towers_anchor_targets_and_fused_gate_are_written_once():
+    import inspect
+    from htd_amd.detector import anchor_free_heads, anchor_heads, fovea_head, vfnet_head
+    from htd_amd.detector.anchor_free_heads import FCOSHead
+    from htd_amd.detector.anchor_heads import AnchorHead, AnchorTargets, ATSSHead, ATSSTargets, GFLHead, RetinaHead
+    from htd_amd.detector.base_dense_head import BaseDenseHead
+    from htd_amd.detector.fovea_head import FoveaHead
+    from htd_amd.detector.rpn_head import RPNHead
+    from htd_amd.detector.vfnet_head import VFNetHead
+
+    def written_once(owner, names, heads):
+        assert all(name in vars(owner) for name in names)
+        for cls in heads:
+            # the owner's own objects, and no class between the head and the owner has a copy
+            assert all(getattr(cls, name) is getattr(owner, name) for name in names), cls
+            for klass in cls.__mro__[:cls.__mro__.index(owner)]:
+                assert not [n for n in vars(klass) if n in names], klass
+    six = (RetinaHead, FCOSHead, ATSSHead, GFLHead, VFNetHead, FoveaHead)
+    written_once(BaseDenseHead, ('_build_towers', '_init_towers', '_run_towers', '_fused_maps_ok'), six + (RPNHead, ))
+    anchor_based = (AnchorHead, RPNHead, RetinaHead, ATSSHead, GFLHead, VFNetHead)
+    written_once(AnchorTargets, ('get_anchors', '_anchors_inside', '_anchor_targets_single', '_anchor_targets', '_loss_targets'),
+                 anchor_based)
+    written_once(ATSSTargets, ('_atss_consts', '_atss_fused_ok', '_atss_fused_targets', 'get_num_level_anchors_inside', '_assign'),
+                 (ATSSHead, GFLHead, VFNetHead))
+    assert AnchorHead._assign is AnchorTargets._assign is RPNHead._assign is RetinaHead._assign
+    assert GFLHead.__bases__ == (ATSSTargets, AnchorHead) == ATSSHead.__bases__ and VFNetHead.__bases__ == (ATSSTargets, FCOSHead)
+    # the map rule is stated once, and nothing is borrowed by assignment
+    text = ''.join(inspect.getsource(m) for m in (anchor_heads, anchor_free_heads, vfnet_head, fovea_head)) + \
+        inspect.getsource(BaseDenseHead)
+    assert text.count('t.is_cuda and t.dtype == torch.float32 and M.nhwc_channel_stride(t)') == 1
+    assert not [line for line in text.splitlines() if line.startswith('    ') and ' = ' in line and
+                line.split(' = ')[1].startswith(('ATSSHead.', 'AnchorHead.')) and line.split(' = ')[0].strip().isidentifier()]
+    # the anchor heads have neither tower kwarg: ConvModule's own default bias, no deformable last layer
+    assert RetinaHead.conv_bias == 'auto' and RetinaHead.dcn_on_last_conv is False
+    # the public return structures are the reference's: 6 of AnchorHead, 7 (the anchors first) of ATSSHead
+    metas, gts, labels = inputs()
+    head = build_head('giou')
+    anchor_list, valid = head.get_anchors(U.LEVEL_SIZES, metas, device='cpu')
+    seven = head.get_targets(anchor_list, valid, gts, metas, gt_labels_list=labels, label_channels=80)
+    six_ = AnchorHead.get_targets(head, anchor_list, valid, gts, metas, gt_labels_list=labels, label_channels=80)
+    assert len(seven) == 7 and len(six_) == 6 and seven[5:] == six_[4:]
+    assert all(torch.equal(a, b) for s, t in zip(seven[1:5], six_[:4]) for a, b in zip(s, t))
+    assert all(torch.equal(a, torch.stack([x, x])) for a, x in zip(seven[0], anchor_list[0]))      # every anchor is inside
+
+
 def test_new_abi_symbols_are_declared_and_exported():
     from htd_amd import capi
     names = {n for n, _, _ in capi.declared_functions()}

@@ -130,8 +130,15 @@ def test_state_dict_keys_and_shapes_equal_the_fixture(golden):
 
 def test_targets_are_shared_with_atss_and_hold_the_gt_boxes():
     from htd_amd.detector.anchor_heads import ATSSHead, GFLHead
+    from htd_amd.detector.vfnet_head import VFNetHead
     assert GFLHead.get_targets is ATSSHead.get_targets and GFLHead._get_target_single is ATSSHead._get_target_single
     assert GFLHead.get_num_level_anchors_inside is ATSSHead.get_num_level_anchors_inside
+    # VFNetHead keeps the reference's own get_targets / _get_target_single (they choose between ATSS and FCOS targets); what
+    # they call is the same
+    assert VFNetHead.get_num_level_anchors_inside is ATSSHead.get_num_level_anchors_inside
+    assert VFNetHead._anchor_targets is ATSSHead._anchor_targets is GFLHead._anchor_targets
+    assert VFNetHead._anchor_targets_single is ATSSHead._anchor_targets_single is GFLHead._anchor_targets_single
+    assert VFNetHead._pos_bbox_targets is not ATSSHead._pos_bbox_targets                # the gt boxes, as GFLHead's
     metas, gts, labels = inputs()
     head = build_head()
     anchor_list, valid = head.get_anchors(U.LEVEL_SIZES, metas, device='cpu')
