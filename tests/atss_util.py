@@ -4,18 +4,17 @@ reference's centerness arithmetic restated in fp32 for the checks of the kernel'
 import numpy as np
 import torch
 
-from golden_util import load_seeded_, seeded_tensor
+import dense_fixture_util as D
+from dense_fixture_util import CFG_KEYS, LEVEL_SIZES, STRIDES, levels_to_images, maps_to_rows, pad_gts  # noqa: F401
+from golden_util import seeded_tensor
 
 CONFIGS = dict(r50='configs/atss/atss_r50_fpn_1x_coco.py', r101='configs/atss/atss_r101_fpn_1x_coco.py')
-CFG_KEYS = ('model', 'train_cfg', 'test_cfg', 'evaluation', 'optimizer', 'optimizer_config', 'lr_config', 'total_epochs')
 EXTRA_GRAD_KEYS = ('neck.fpn_convs.3.conv.weight', 'neck.fpn_convs.4.conv.weight', 'bbox_head.cls_convs.0.conv.weight',
                    'bbox_head.reg_convs.3.conv.weight', 'bbox_head.atss_cls.weight', 'bbox_head.atss_cls.bias',
                    'bbox_head.atss_reg.weight', 'bbox_head.atss_reg.bias', 'bbox_head.atss_centerness.weight',
                    'bbox_head.atss_centerness.bias', 'bbox_head.scales.0.scale', 'bbox_head.scales.1.scale',
                    'bbox_head.scales.2.scale', 'bbox_head.scales.3.scale', 'bbox_head.scales.4.scale',
                    'bbox_head.cls_convs.1.gn.weight')
-STRIDES = (8, 16, 32, 64, 128)
-LEVEL_SIZES = ((16, 20), (8, 10), (4, 5), (2, 3), (1, 2))                  # of a 128 x 160 batch at strides 8 .. 128
 LEVEL_ANCHORS = tuple(h * w for h, w in LEVEL_SIZES)                       # 320, 80, 20, 6, 2: the last two hold fewer than topk
 TOPK = 9
 MEANS, STDS = (0., 0., 0., 0.), (0.1, 0.1, 0.2, 0.2)
@@ -51,52 +50,25 @@ def head_cfg(variant, num_classes=80, **extra):
     return d
 
 
+# the fixture's weights (dense_fixture_util): the level scales at 1 + a quarter of a seeded normal, the classification and centerness
+# layers scaled and the classification bias lowered by the two figures the fixture records (plainly seeded, the logits saturate
+# the sigmoid, the ranking keys crowd and thousands of scores lie around the score threshold), the regression layer by REG_SCALE
+FIXTURE = dict(scales=('scales', ),
+               edits=(('bbox_head.atss_cls.weight', 'mul', 'scale'), ('bbox_head.atss_centerness.weight', 'mul', 'scale'),
+                      ('bbox_head.atss_cls.bias', 'sub', 'bias_shift'), ('bbox_head.atss_reg.weight', 'mul', REG_SCALE),
+                      ('bbox_head.atss_reg.bias', 'mul', REG_SCALE)))
+
+
 def load_fixture_weights_(det, scale, bias_shift):
-    """The values of load_seeded_(det, 'det.') with the level scales at 1 + a quarter of a seeded normal, the classification and
-    centerness layers scaled and the classification bias lowered by the two figures the fixture records (plainly seeded, the
-    logits saturate the sigmoid, the ranking keys crowd and thousands of scores lie around the score threshold), and the
-    regression layer scaled by REG_SCALE."""
-    from golden_util import seeded_array
-    load_seeded_(det.backbone, 'det.backbone.')
-    load_seeded_(det.neck, 'det.neck.')
-    for name, child in det.bbox_head.named_children():
-        if name != 'scales' and len(list(child.state_dict())) > 0:      # (zero-dimensional parameters: seeded by hand below)
-            load_seeded_(child, f'det.bbox_head.{name}.')
-    with torch.no_grad():
-        for l, s in enumerate(det.bbox_head.scales):
-            s.scale.fill_(1.0 + 0.25 * float(seeded_array(f'det.bbox_head.scales.{l}.scale', (1, ))[0]))
-        det.bbox_head.atss_cls.weight.mul_(float(scale))
-        det.bbox_head.atss_centerness.weight.mul_(float(scale))
-        det.bbox_head.atss_cls.bias.sub_(float(bias_shift))
-        det.bbox_head.atss_reg.weight.mul_(REG_SCALE)
-        det.bbox_head.atss_reg.bias.mul_(REG_SCALE)
-    return det
+    return D.load_fixture_weights(det, **FIXTURE, scale=scale, bias_shift=bias_shift)
 
 
 def fixture_state(keys, shapes, scale, bias_shift):
-    """The state dict load_fixture_weights_ leaves, from the fixture's key and shape lists (shapes padded to 4 dims with 0)."""
-    from golden_util import seeded_array, seeded_state_value
-    out = {}
-    for k, shape in zip(keys, shapes):
-        k, shape = str(k), [int(s) for s in shape if s]
-        if k.endswith('num_batches_tracked'):
-            out[k] = torch.zeros((), dtype=torch.int64)
-        elif k.startswith('bbox_head.scales.'):
-            out[k] = torch.tensor(1.0 + 0.25 * float(seeded_array('det.' + k, (1, ))[0]))
-        else:
-            out[k] = torch.from_numpy(np.asarray(seeded_state_value('det.' + k, shape)))
-    out['bbox_head.atss_cls.weight'] = out['bbox_head.atss_cls.weight'] * float(scale)
-    out['bbox_head.atss_centerness.weight'] = out['bbox_head.atss_centerness.weight'] * float(scale)
-    out['bbox_head.atss_cls.bias'] = out['bbox_head.atss_cls.bias'] - float(bias_shift)
-    out['bbox_head.atss_reg.weight'] = out['bbox_head.atss_reg.weight'] * REG_SCALE
-    out['bbox_head.atss_reg.bias'] = out['bbox_head.atss_reg.bias'] * REG_SCALE
-    return out
+    return D.fixture_state(keys, shapes, **FIXTURE, scale=scale, bias_shift=bias_shift)
 
 
 def grad_keys(det):
-    from baselines_util import GRAD_KEYS
-    names = dict(det.named_parameters())
-    return [k for k in GRAD_KEYS + EXTRA_GRAD_KEYS if k in names and names[k].requires_grad]
+    return D.grad_keys(det, EXTRA_GRAD_KEYS)
 
 
 def head_maps(variant=None, B=2, C=80, sizes=LEVEL_SIZES, tag='atss.head'):
@@ -161,18 +133,6 @@ EXTRA_CASES = dict(equal=(((1, 2), ), (128, ), torch.tensor([[-40., -30., 168., 
                    std=(((1, 3), ), (64, ), torch.tensor([[-224.7, -233.9, 245.7, 256.9]])))
 
 
-def pad_gts(gts_list, labels_list=None, K=None):
-    """-> (B, K, 4) boxes, (B, K) validity, (B, K) labels, zero-padded like core.bbox.pad_gt_batch (K = max(1, longest list))."""
-    B = len(gts_list)
-    K = max(1, max(len(g) for g in gts_list)) if K is None else K
-    gts, valid, labels = torch.zeros(B, K, 4), torch.zeros(B, K, dtype=torch.bool), torch.zeros(B, K, dtype=torch.long)
-    for b, g in enumerate(gts_list):
-        gts[b, :len(g)], valid[b, :len(g)] = g, True
-        if labels_list is not None:
-            labels[b, :len(g)] = labels_list[b]
-    return gts, valid, labels
-
-
 def _rounded(fn, x):
     """fn in fp64 rounded to fp32: the correctly rounded fp32 function (the kernel's logarithm and exponential)."""
     return fn(x.double()).float()
@@ -211,14 +171,3 @@ def batch_ltrb(anchors, padded_gts, assigned, rounded=False):
 def centerness_of(ltrb):
     lr, tb = ltrb[..., [0, 2]], ltrb[..., [1, 3]]
     return torch.sqrt((lr.min(-1)[0] / lr.max(-1)[0]) * (tb.min(-1)[0] / tb.max(-1)[0]))
-
-
-def levels_to_images(per_level, B):
-    """The reference's per-level tensors (rows: image after image) -> (B, A, ...) level-major per image."""
-    return torch.cat([t.reshape(B, t.size(0) // B, *t.shape[1:]) for t in per_level], 1)
-
-
-def maps_to_rows(maps):
-    """(B, c, h, w) per level -> (B, A, c)."""
-    B = maps[0].size(0)
-    return torch.cat([m.permute(0, 2, 3, 1).reshape(B, -1, m.size(1)) for m in maps], 1)

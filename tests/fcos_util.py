@@ -2,24 +2,22 @@
 (tests/golden/fcos.npz), re-created from seeds so the fixture holds results only, and restatements of the reference's target
 assignment and loss in a chosen precision (pinned against the fixture by tests/test_fcos.py) for the cases of the GPU tests that
 the fixture does not hold."""
-import numpy as np
 import torch
 
-from golden_util import load_seeded_, seeded_tensor
+import dense_fixture_util as D
+from dense_fixture_util import CFG_KEYS, LEVEL_SIZES, STRIDES, levels_to_images, maps_to_rows, pad_gts  # noqa: F401
+from golden_util import seeded_tensor
 
 CONFIGS = dict(gn_head='configs/fcos/fcos_r50_caffe_fpn_gn-head_4x4_1x_coco.py',
                center='configs/fcos/fcos_center-normbbox-centeronreg-giou_r50_caffe_fpn_gn-head_4x4_1x_coco.py')
 VARIANT_OF = dict(gn_head='gn-head', center='center-normbbox-centeronreg-giou')
-CFG_KEYS = ('model', 'train_cfg', 'test_cfg', 'evaluation', 'optimizer', 'optimizer_config', 'lr_config', 'total_epochs')
 EXTRA_GRAD_KEYS = ('neck.fpn_convs.3.conv.weight', 'neck.fpn_convs.4.conv.weight', 'bbox_head.cls_convs.0.conv.weight',
                    'bbox_head.reg_convs.3.conv.weight', 'bbox_head.conv_cls.weight', 'bbox_head.conv_cls.bias',
                    'bbox_head.conv_reg.weight', 'bbox_head.conv_reg.bias', 'bbox_head.conv_centerness.weight',
                    'bbox_head.conv_centerness.bias', 'bbox_head.scales.0.scale', 'bbox_head.scales.1.scale',
                    'bbox_head.scales.2.scale', 'bbox_head.scales.3.scale', 'bbox_head.scales.4.scale',
                    'bbox_head.cls_convs.1.gn.weight')
-STRIDES = (8, 16, 32, 64, 128)
 REG_BIAS_SHIFT = 2.5      # distances around exp(2.5) = 12 pixels: plainly seeded, the boxes of neighbouring points never overlap
-LEVEL_SIZES = ((16, 20), (8, 10), (4, 5), (2, 3), (1, 2))                  # of a 128 x 160 batch at strides 8 .. 128
 INF = 1e8
 RANGES = ((-1, 64), (64, 128), (128, 256), (256, 512), (512, INF))         # the head's default
 SMALL_RANGES = ((-1, 16), (16, 32), (32, 64), (64, 128), (128, INF))       # scaled to the 128 x 160 pyramid
@@ -41,49 +39,24 @@ def head_cfg(variant, num_classes=80, **extra):
     return d
 
 
+# the fixture's weights (dense_fixture_util): the level scales at 1 + a quarter of a seeded normal, the classification and centerness
+# layers scaled and the classification bias lowered by the two figures the fixture records (plainly seeded, the logits saturate
+# the sigmoid, the ranking keys crowd and thousands of scores lie around the score threshold)
+FIXTURE = dict(scales=('scales', ),
+               edits=(('bbox_head.conv_cls.weight', 'mul', 'scale'), ('bbox_head.conv_centerness.weight', 'mul', 'scale'),
+                      ('bbox_head.conv_cls.bias', 'sub', 'bias_shift'), ('bbox_head.conv_reg.bias', 'add', REG_BIAS_SHIFT)))
+
+
 def load_fixture_weights_(det, scale, bias_shift):
-    """The values of load_seeded_(det, 'det.') with the level scales at 1 + a quarter of a seeded normal, the classification and
-    centerness layers scaled and the classification bias lowered by the two figures the fixture records (plainly seeded, the
-    logits saturate the sigmoid, the ranking keys crowd and thousands of scores lie around the score threshold)."""
-    from golden_util import seeded_array
-    load_seeded_(det.backbone, 'det.backbone.')
-    load_seeded_(det.neck, 'det.neck.')
-    for name, child in det.bbox_head.named_children():
-        if name != 'scales':                    # (zero-dimensional parameters: seeded by hand below)
-            load_seeded_(child, f'det.bbox_head.{name}.')
-    with torch.no_grad():
-        for l, s in enumerate(det.bbox_head.scales):
-            s.scale.fill_(1.0 + 0.25 * float(seeded_array(f'det.bbox_head.scales.{l}.scale', (1, ))[0]))
-        det.bbox_head.conv_cls.weight.mul_(float(scale))
-        det.bbox_head.conv_centerness.weight.mul_(float(scale))
-        det.bbox_head.conv_cls.bias.sub_(float(bias_shift))
-        det.bbox_head.conv_reg.bias.add_(REG_BIAS_SHIFT)
-    return det
+    return D.load_fixture_weights(det, **FIXTURE, scale=scale, bias_shift=bias_shift)
 
 
 def fixture_state(keys, shapes, scale, bias_shift):
-    """The state dict load_fixture_weights_ leaves, from the fixture's key and shape lists (shapes padded to 4 dims with 0)."""
-    from golden_util import seeded_array, seeded_state_value
-    out = {}
-    for k, shape in zip(keys, shapes):
-        k, shape = str(k), [int(s) for s in shape if s]
-        if k.endswith('num_batches_tracked'):
-            out[k] = torch.zeros((), dtype=torch.int64)
-        elif k.startswith('bbox_head.scales.'):
-            out[k] = torch.tensor(1.0 + 0.25 * float(seeded_array('det.' + k, (1, ))[0]))
-        else:
-            out[k] = torch.from_numpy(np.asarray(seeded_state_value('det.' + k, shape)))
-    out['bbox_head.conv_cls.weight'] = out['bbox_head.conv_cls.weight'] * float(scale)
-    out['bbox_head.conv_centerness.weight'] = out['bbox_head.conv_centerness.weight'] * float(scale)
-    out['bbox_head.conv_cls.bias'] = out['bbox_head.conv_cls.bias'] - float(bias_shift)
-    out['bbox_head.conv_reg.bias'] = out['bbox_head.conv_reg.bias'] + REG_BIAS_SHIFT
-    return out
+    return D.fixture_state(keys, shapes, **FIXTURE, scale=scale, bias_shift=bias_shift)
 
 
 def grad_keys(det):
-    from baselines_util import GRAD_KEYS
-    names = dict(det.named_parameters())
-    return [k for k in GRAD_KEYS + EXTRA_GRAD_KEYS if k in names and names[k].requires_grad]
+    return D.grad_keys(det, EXTRA_GRAD_KEYS)
 
 
 def head_maps(variant, B=2, C=80, sizes=LEVEL_SIZES, strides=STRIDES, tag='fcos.head'):
@@ -122,18 +95,6 @@ def points_of(sizes, strides, dtype=torch.float32):
     return torch.cat(pts), torch.cat(lvl)
 
 
-def pad_gts(gts_list, labels_list=None, K=None):
-    """-> (B, K, 4) boxes, (B, K) validity, (B, K) labels, zero-padded like core.bbox.pad_gt_batch (K = max(1, longest list))."""
-    B = len(gts_list)
-    K = max(1, max(len(g) for g in gts_list)) if K is None else K
-    gts, valid, labels = torch.zeros(B, K, 4), torch.zeros(B, K, dtype=torch.bool), torch.zeros(B, K, dtype=torch.long)
-    for b, g in enumerate(gts_list):
-        gts[b, :len(g)], valid[b, :len(g)] = g, True
-        if labels_list is not None:
-            labels[b, :len(g)] = labels_list[b]
-    return gts, valid, labels
-
-
 def targets_ref(sizes, strides, ranges, gts, valid, center_sampling=False, radius=1.5, norm_on_bbox=False, dtype=torch.float32):
     """fcos_head.py:476-576 restated on padded gts (B, K, 4) / valid (B, K) in `dtype`, one rounded operation at a time as the
     reference's tensors take them -> assigned (B, P) int32 (0 background, k + 1 = gt k), bbox_targets (B, P, 4), ctr_targets
@@ -170,17 +131,6 @@ def targets_ref(sizes, strides, ranges, gts, valid, center_sampling=False, radiu
     ctr = torch.sqrt((lr.min(-1)[0] / lr.max(-1)[0]) * (tb.min(-1)[0] / tb.max(-1)[0]))
     ctr = torch.where(pos, ctr, torch.zeros_like(ctr))
     return torch.where(pos, k + 1, torch.zeros_like(k)).to(torch.int32), bt, ctr
-
-
-def levels_to_images(per_level, B):
-    """The reference's per-level tensors (rows: image after image) -> (B, P, ...) level-major per image."""
-    return torch.cat([t.reshape(B, t.size(0) // B, *t.shape[1:]) for t in per_level], 1)
-
-
-def maps_to_rows(maps):
-    """(B, c, h, w) per level -> (B, P, c)."""
-    B = maps[0].size(0)
-    return torch.cat([m.permute(0, 2, 3, 1).reshape(B, -1, m.size(1)) for m in maps], 1)
 
 
 def loss_ref(cls, reg, ctr, strides, gt_labels, assigned, bbox_targets, ctr_targets, kind='iou', gamma=2.0, alpha=0.25,

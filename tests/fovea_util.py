@@ -1,11 +1,11 @@
 """Shared by tests/golden/make_golden_fovea.py, tests/test_fovea.py and tests/test_gpu_fovea.py: the inputs of the FoveaBox fixture
 (tests/golden/fovea.npz), re-created from seeds so the fixture holds results only, and the fp64 formulas of the loss and of the
 FeatureAlign offsets that the GPU tests measure the kernels against."""
-import numpy as np
 import torch
 
-from fcos_util import levels_to_images, maps_to_rows, pad_gts  # noqa: F401
-from golden_util import load_seeded_, seeded_tensor
+import dense_fixture_util as D
+from dense_fixture_util import CFG_KEYS, LEVEL_SIZES, STRIDES, levels_to_images, maps_to_rows, pad_gts  # noqa: F401
+from golden_util import seeded_tensor
 
 CONFIGS = dict(plain='configs/foveabox/fovea_r50_fpn_4x4_1x_coco.py',
                align='configs/foveabox/fovea_align_r50_fpn_gn-head_4x4_2x_coco.py',
@@ -13,16 +13,13 @@ CONFIGS = dict(plain='configs/foveabox/fovea_r50_fpn_4x4_1x_coco.py',
 CONFIG_ARGS = dict(plain=dict(depth=50), align=dict(depth=50, align=True, schedule='2x'),
                    align_r101_mstrain=dict(depth=101, align=True, mstrain=True, schedule='2x'))
 DETECTOR_CONFIGS = ('plain', 'align')           # the two the fixture runs
-CFG_KEYS = ('model', 'train_cfg', 'test_cfg', 'evaluation', 'optimizer', 'optimizer_config', 'lr_config', 'total_epochs')
-# (and 'train_pipeline' = data.train.pipeline)
+# (CFG_KEYS and 'train_pipeline' = data.train.pipeline)
 EXTRA_GRAD_KEYS = ('neck.fpn_convs.3.conv.weight', 'neck.fpn_convs.4.conv.weight', 'bbox_head.cls_convs.0.conv.weight',
                    'bbox_head.cls_convs.1.conv.weight', 'bbox_head.reg_convs.3.conv.weight', 'bbox_head.conv_cls.weight',
                    'bbox_head.conv_cls.bias', 'bbox_head.conv_reg.weight', 'bbox_head.conv_reg.bias',
                    'bbox_head.feature_adaption.conv_offset.weight', 'bbox_head.feature_adaption.conv_adaption.weight',
                    'bbox_head.cls_convs.1.gn.weight')
-STRIDES = (8, 16, 32, 64, 128)
 BASE_EDGES = (16, 32, 64, 128, 256)
-LEVEL_SIZES = ((16, 20), (8, 10), (4, 5), (2, 3), (1, 2))                  # of a 128 x 160 batch at strides 8 .. 128
 LEVEL_POINTS = tuple(h * w for h, w in LEVEL_SIZES)
 CONFIG_RANGES = ((1, 64), (32, 128), (64, 256), (128, 512), (256, 2048))   # of the reference's configs
 DEFAULT_RANGES = ((8, 32), (16, 64), (32, 128), (64, 256), (128, 512))     # of the head's constructor: the targets case
@@ -41,38 +38,22 @@ def head_cfg(num_classes=80, **extra):
     return d
 
 
+# the fixture's weights (dense_fixture_util): the classification layer scaled and its bias lowered by the two figures the fixture
+# records (plainly seeded, the logits saturate the sigmoid and the ranking keys crowd), the regression layer scaled by REG_SCALE
+FIXTURE = dict(edits=(('bbox_head.conv_cls.weight', 'mul', 'scale'), ('bbox_head.conv_cls.bias', 'sub', 'bias_shift'),
+                      ('bbox_head.conv_reg.weight', 'mul', REG_SCALE)))
+
+
 def load_fixture_weights_(det, scale, bias_shift):
-    """The values of load_seeded_(det, 'det.') with the classification layer scaled and its bias lowered by the two figures the
-    fixture records (plainly seeded, the logits saturate the sigmoid and the ranking keys crowd) and the regression layer scaled
-    by REG_SCALE."""
-    load_seeded_(det, 'det.')
-    with torch.no_grad():
-        det.bbox_head.conv_cls.weight.mul_(float(scale))
-        det.bbox_head.conv_cls.bias.sub_(float(bias_shift))
-        det.bbox_head.conv_reg.weight.mul_(REG_SCALE)
-    return det
+    return D.load_fixture_weights(det, **FIXTURE, scale=scale, bias_shift=bias_shift)
 
 
 def fixture_state(keys, shapes, scale, bias_shift):
-    """The state dict load_fixture_weights_ leaves, from the fixture's key and shape lists (shapes padded to 4 dims with 0)."""
-    from golden_util import seeded_state_value
-    out = {}
-    for k, shape in zip(keys, shapes):
-        k, shape = str(k), [int(s) for s in shape if s]
-        if k.endswith('num_batches_tracked'):
-            out[k] = torch.zeros((), dtype=torch.int64)
-        else:
-            out[k] = torch.from_numpy(np.asarray(seeded_state_value('det.' + k, shape)))
-    out['bbox_head.conv_cls.weight'] = out['bbox_head.conv_cls.weight'] * float(scale)
-    out['bbox_head.conv_cls.bias'] = out['bbox_head.conv_cls.bias'] - float(bias_shift)
-    out['bbox_head.conv_reg.weight'] = out['bbox_head.conv_reg.weight'] * REG_SCALE
-    return out
+    return D.fixture_state(keys, shapes, **FIXTURE, scale=scale, bias_shift=bias_shift)
 
 
 def grad_keys(det):
-    from baselines_util import GRAD_KEYS
-    names = dict(det.named_parameters())
-    return [k for k in GRAD_KEYS + EXTRA_GRAD_KEYS if k in names and names[k].requires_grad]
+    return D.grad_keys(det, EXTRA_GRAD_KEYS)
 
 
 def head_maps(B=2, C=80, sizes=LEVEL_SIZES, tag='fovea.head'):

@@ -4,6 +4,7 @@
 import numpy as np
 import torch
 
+import dense_fixture_util as D
 from golden_util import seeded_tensor
 import retina_util as RU
 
@@ -47,15 +48,20 @@ def edges_of(bins, kind):
     return e
 
 
+# the fixture's weights (dense_fixture_util): retina_util's, with the four buffers of the loss modules (STATE_KEYS) as the modules
+# make them: their own edges, acc_sum = 0
+FIXTURE = dict(RU.FIXTURE, constants={'bbox_head.loss_cls.edges': lambda shape: edges_of(shape[0] - 1, 'c'),
+                                      'bbox_head.loss_bbox.edges': lambda shape: edges_of(shape[0] - 1, 'r'),
+                                      'bbox_head.loss_cls.acc_sum': torch.zeros, 'bbox_head.loss_bbox.acc_sum': torch.zeros})
+assert set(FIXTURE['constants']) == set(STATE_KEYS)
+
+
 def load_fixture_weights_(det, cls_scale):
-    """retina_util.load_fixture_weights_, after which the four buffers of the loss modules (STATE_KEYS, seeded like every other
-    state entry by it) are put back: the modules' own edges, acc_sum = 0."""
-    RU.load_fixture_weights_(det, cls_scale)
-    with torch.no_grad():
-        for mod, kind in ((det.bbox_head.loss_cls, 'c'), (det.bbox_head.loss_bbox, 'r')):
-            mod.edges.copy_(edges_of(mod.bins, kind))
-            mod.acc_sum.zero_()
-    return det
+    return D.load_fixture_weights(det, **FIXTURE, cls_scale=cls_scale)
+
+
+def fixture_state(keys, shapes, cls_scale):
+    return D.fixture_state(keys, shapes, **FIXTURE, cls_scale=cls_scale)
 
 
 def ghmc_rows(n=64, C=80, tag='ghm.c'):

@@ -107,16 +107,20 @@ def aug_inputs():
     return imgs, metas
 
 
-def match_detections(mine, ref, tol=1e-2):
-    """One-to-one matching of (k, 6) [x1, y1, x2, y2, score, class] rows: detections with (nearly) equal scores may
-    swap ranks, so rows are matched instead of compared in order."""
+def match_detections(mine, ref, tol=1e-2, coord_rtol=1e-3):
+    """One-to-one matching of (k, 6) [x1, y1, x2, y2, score, class] rows within tol + coord_rtol * the row's largest coordinate:
+    detections with (nearly) equal scores may swap ranks, so rows are matched instead of compared in order.  -> the worst
+    distance in units of its bound."""
     assert mine.shape == ref.shape, (mine.shape, ref.shape)
     used = np.zeros(len(mine), dtype=bool)
+    worst = 0.0
     for r in ref:
         d = np.abs(mine[:, :5] - r[:5]).max(1) + 1e3 * (mine[:, 5] != r[5]) + 1e3 * used
         j = int(d.argmin())
-        assert d[j] <= tol + 1e-3 * np.abs(r[:4]).max(), (r, mine[j], d[j])
+        worst = max(worst, d[j] / (tol + coord_rtol * np.abs(r[:4]).max()))
+        assert d[j] <= tol + coord_rtol * np.abs(r[:4]).max(), (r, mine[j], d[j])
         used[j] = True
+    return worst
 
 
 def pipeline_samples():

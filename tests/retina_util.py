@@ -1,36 +1,36 @@
 """Shared by tests/golden/make_golden_retinanet.py, tests/test_retinanet.py and tests/test_gpu_retinanet.py: the inputs of the
 RetinaNet fixture (tests/golden/retinanet.npz), re-created from seeds so the fixture holds results only."""
-import numpy as np
 import torch
 
-from golden_util import load_seeded_, seeded_tensor
+import dense_fixture_util as D
+from dense_fixture_util import CFG_KEYS, LEVEL_SIZES  # noqa: F401
+from golden_util import seeded_tensor
 
 CONFIG = 'configs/retinanet/retinanet_r50_fpn_1x_coco.py'
-CFG_KEYS = ('model', 'train_cfg', 'test_cfg', 'evaluation', 'optimizer', 'optimizer_config', 'lr_config', 'total_epochs')
 EXTRA_GRAD_KEYS = ('neck.fpn_convs.3.conv.weight', 'neck.fpn_convs.4.conv.weight', 'bbox_head.cls_convs.0.conv.weight',
                    'bbox_head.reg_convs.3.conv.weight', 'bbox_head.retina_cls.weight', 'bbox_head.retina_cls.bias',
                    'bbox_head.retina_reg.weight', 'bbox_head.retina_reg.bias')
 FOCAL_PARAMS = ((2.0, 0.25), (1.5, 0.25), (2.0, 0.5), (1.5, 0.5))          # (gamma, alpha)
 AVG = 37.0
 CLS_BIAS_SHIFT = 5.0
-LEVEL_SIZES = ((16, 20), (8, 10), (4, 5), (2, 3), (1, 2))                  # of a 128 x 160 batch at strides 8 .. 128
+
+
+# the fixture's weights (dense_fixture_util): the classification layer scaled by the factor the fixture records and its bias lowered
+# by CLS_BIAS_SHIFT (plainly seeded, its logits saturate the sigmoid: the ranking keys crowd at 1 and every score passes the
+# threshold; a RetinaNet starts from sigmoid(bias) = 0.01)
+FIXTURE = dict(edits=(('bbox_head.retina_cls.weight', 'mul', 'cls_scale'), ('bbox_head.retina_cls.bias', 'sub', CLS_BIAS_SHIFT)))
 
 
 def load_fixture_weights_(det, cls_scale):
-    """load_seeded_(det, 'det.') with the classification layer scaled by the factor the fixture records and its bias lowered by
-    CLS_BIAS_SHIFT (plainly seeded, its logits saturate the sigmoid: the ranking keys crowd at 1 and every score passes the
-    threshold; a RetinaNet starts from sigmoid(bias) = 0.01)."""
-    load_seeded_(det, 'det.')
-    with torch.no_grad():
-        det.bbox_head.retina_cls.weight.mul_(float(cls_scale))
-        det.bbox_head.retina_cls.bias.sub_(CLS_BIAS_SHIFT)
-    return det
+    return D.load_fixture_weights(det, **FIXTURE, cls_scale=cls_scale)
+
+
+def fixture_state(keys, shapes, cls_scale):
+    return D.fixture_state(keys, shapes, **FIXTURE, cls_scale=cls_scale)
 
 
 def grad_keys(det):
-    from baselines_util import GRAD_KEYS
-    names = dict(det.named_parameters())
-    return [k for k in GRAD_KEYS + EXTRA_GRAD_KEYS if k in names]
+    return D.grad_keys(det, EXTRA_GRAD_KEYS)
 
 
 def focal_rows(n=64, C=80):

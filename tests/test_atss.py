@@ -12,12 +12,10 @@ import torch
 
 import atss_util as U
 import baselines_util as BU
+import dense_fixture_util as D
+from dense_fixture_util import T
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
-
-
-def T(a):
-    return torch.from_numpy(np.asarray(a))
 
 
 def build_head(variant='giou', **extra):
@@ -29,8 +27,7 @@ def build_head(variant='giou', **extra):
 
 
 def inputs():
-    _, metas, gts, labels = U.detector_inputs()
-    return metas, [T(g) for g in gts], [T(l) for l in labels]
+    return D.inputs('cpu', U.detector_inputs)[1:]
 
 
 @pytest.mark.parametrize('which,depth', [('r50', 50), ('r101', 101)])

@@ -10,13 +10,11 @@ import pytest
 import torch
 
 import baselines_util as BU
+import dense_fixture_util as D
+from dense_fixture_util import T
 import fcos_util as U
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
-
-
-def T(a):
-    return torch.from_numpy(np.asarray(a))
 
 
 def build_head(variant='iou', **extra):
@@ -26,8 +24,7 @@ def build_head(variant='iou', **extra):
 
 
 def inputs():
-    _, metas, gts, labels = BU.detector_inputs()
-    return metas, [T(g) for g in gts], [T(l) for l in labels]
+    return D.inputs('cpu', BU.detector_inputs)[1:]
 
 
 @pytest.mark.parametrize('which', list(U.CONFIGS))

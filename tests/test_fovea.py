@@ -10,19 +10,11 @@ import pytest
 import torch
 
 import baselines_util as BU
+import dense_fixture_util as D
+from dense_fixture_util import EPS32, T, bound as _bound
 import fovea_util as U
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
-EPS32 = 2.0 ** -23
-
-
-def T(a):
-    return torch.from_numpy(np.asarray(a))
-
-
-def _bound(e32, ref):
-    """The project's rule: 4 x max(the reference's own fp32 error, one fp32 ulp of the largest entry)."""
-    return 4.0 * max(float(e32), EPS32 * float(torch.as_tensor(ref).abs().max()))
 
 
 LOG_TOL = 2.0 ** -22     # one fp32 ulp of a value in [2, 4) (|log target| <= log 16 = 2.77): what two CPU logarithms may differ by
@@ -63,8 +55,7 @@ def build_head(**extra):
 
 
 def inputs():
-    _, metas, gts, labels = BU.detector_inputs()
-    return metas, [T(g) for g in gts], [T(l) for l in labels]
+    return D.inputs('cpu', BU.detector_inputs)[1:]
 
 
 @pytest.mark.parametrize('which', list(U.CONFIGS))

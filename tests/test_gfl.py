@@ -15,14 +15,11 @@ import pytest
 import torch
 
 import baselines_util as BU
+import dense_fixture_util as D
+from dense_fixture_util import EPS32, T
 import gfl_util as U
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
-EPS32 = 2.0 ** -23
-
-
-def T(a):
-    return torch.from_numpy(np.asarray(a))
 
 
 def build_head(variant='giou', **extra):
@@ -34,8 +31,7 @@ def build_head(variant='giou', **extra):
 
 
 def inputs():
-    _, metas, gts, labels = U.detector_inputs()
-    return metas, [T(g) for g in gts], [T(l) for l in labels]
+    return D.inputs('cpu', U.detector_inputs)[1:]
 
 
 def head_losses(ls):

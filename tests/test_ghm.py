@@ -13,14 +13,11 @@ import pytest
 import torch
 
 import baselines_util as BU
+from dense_fixture_util import T
 import ghm_util as U
 import retina_util as RU
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
-
-
-def T(a):
-    return torch.from_numpy(np.asarray(a))
 
 
 def _module(kind, bins, mmt, **kw):

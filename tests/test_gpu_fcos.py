@@ -2,7 +2,7 @@
 (tests/golden/fcos.npz) and the restatements of fcos_util (pinned against that fixture by tests/test_fcos.py), the fused
 FCOSHead.loss against the reference's fp64 run, and the FCOS detector against the reference's.
 
-The bound of every value computed by a kernel is the project's rule (test_gpu_iou_losses.py, test_gpu_retinanet.py:_bound):
+The bound of every value computed by a kernel is the project's rule (dense_fixture_util.bound):
 4 x max(the reference's own fp32 error on that case, one fp32 ulp of the largest entry); the fp32 error comes from the fixture or
 from the fp32 run of the formula, never from the code under test.  Assignments and distances are compared bit for bit, the
 centerness targets under the rule of _check_ctr."""
@@ -14,28 +14,16 @@ import pytest
 import torch
 
 import baselines_util as BU
+import dense_fixture_util as D
+from dense_fixture_util import EPS32, T, bound as _bound, err as _err
 import fcos_util as U
-from golden_util import match_detections, seeded_tensor
+from golden_util import seeded_tensor
 
 pytestmark = pytest.mark.gpu
 
-EPS32 = float(np.finfo(np.float32).eps)
 DEV = 'cuda:0'
 CL = torch.channels_last
 PYRAMIDS = dict(five=(U.LEVEL_SIZES, U.STRIDES, U.SMALL_RANGES, 2), one=(((1, 1), ), (8, ), ((-1, U.INF), ), 1))
-
-
-def T(a):
-    return torch.from_numpy(np.asarray(a))
-
-
-def _err(a, ref):
-    return float((a.detach().cpu().double() - ref).abs().max())
-
-
-def _bound(e32, ref):
-    """The rule of test_gpu_iou_losses.py: 4 x max(the reference's own fp32 error, one fp32 ulp of the largest entry)."""
-    return 4.0 * max(float(e32), EPS32 * float(ref.abs().max()))
 
 
 # ---------------------------------------------------------------------------------------------------- the targets kernel
@@ -324,8 +312,7 @@ def _head_on_device(v):
 
 
 def inputs(dev):
-    imgs, metas, gts, labels = BU.detector_inputs()
-    return T(imgs).to(dev), metas, [T(x).to(dev) for x in gts], [T(x).to(dev) for x in labels]
+    return D.inputs(dev, BU.detector_inputs)
 
 
 @pytest.mark.parametrize('v', list(U.HEAD_VARIANTS))
@@ -426,83 +413,32 @@ def det(golden):
 
 
 def test_train_step_matches_reference_fixture(det, golden):
-    """Bounds of test_gpu_retinanet.py::test_train_step_matches_reference_fixture: losses rtol 5e-4 / atol 1e-4; gradient digests in
-    units of 2e-4 * max(1, max |ref|) + 1e-3 * |ref|: no element over 2 units, rms at most 0.2.  `assigned` equals the fixture's."""
-    from htd_amd import capi
+    """The bounds of dense_fixture_util.check_train_step; `assigned` equals the fixture's and the step takes one htd_fcos_targets
+    and one htd_fcos_loss."""
     g = golden('fcos')
     img, metas, gts, labels = inputs(torch.device(DEV))
     det.train()
-    calls, real = [], capi.call
-
-    def spy(name, *a, **k):
-        calls.append(name)
-        return real(name, *a, **k)
-    capi.call = spy
-    try:
-        losses = det.forward_train(img, metas, gts, labels)
-    finally:
-        capi.call = real
+    losses, calls = D.spied(lambda: det.forward_train(img, metas, gts, labels))
     assert calls.count('htd_fcos_loss') == 1 and calls.count('htd_fcos_targets') == 1
     assigned, _, _, num_pos, norm = det.bbox_head._last_targets
     assert torch.equal(assigned.cpu().long(), T(g['assigned']).long())
     assert num_pos.tolist() == g['num_pos'].tolist() and float(norm[0]) == float(g['num_pos'].sum()) + 2
-    loss, log_vars = det._parse_losses(losses)
-    assert set(log_vars.keys()) == {f[5:] for f in g.files if f.startswith('loss.')} == {'loss_cls', 'loss_bbox', 'loss_centerness', 'loss'}
-    det.zero_grad()
-    loss.backward()
-    params = dict(det.named_parameters())
     keys = U.grad_keys(det)
     assert len(keys) == 3 + len(U.EXTRA_GRAD_KEYS), keys        # (the backbone's BatchNorm parameters are frozen in this config)
-    worst, worst_rms, worst_loss = (0.0, ''), (0.0, ''), 0.0
-    for k, v in log_vars.items():
-        ref = float(g[f'loss.{k}'])
-        worst_loss = max(worst_loss, abs(v - ref) / (1e-4 + 5e-4 * abs(ref)))
-    for k in keys:
-        ref = g[f'grad.{k}.sample']
-        assert float(g[f'grad.{k}.sums'][1]) > 0 or '.scales.' in k, k          # (a level without positives: its scale gets exactly 0)
-        tol = 2e-4 * max(1.0, np.abs(ref).max()) + 1e-3 * np.abs(ref)
-        ratio = np.abs(BU.digest(params[k].grad.cpu())[1] - ref) / tol
-        worst, worst_rms = max(worst, (float(ratio.max()), k)), max(worst_rms, (float(np.sqrt(np.mean(ratio ** 2))), k))
-    print(f'fcos: worst loss ratio {worst_loss:.3f}; worst gradient element {worst[0]:.3f} units ({worst[1]}), '
-          f'worst rms {worst_rms[0]:.3f} ({worst_rms[1]})')
-    for k, v in log_vars.items():
-        np.testing.assert_allclose(v, float(g[f'loss.{k}']), rtol=5e-4, atol=1e-4, err_msg=k)
-    assert worst[0] <= 2.0 and worst_rms[0] <= 0.2, (worst, worst_rms)
+    D.check_train_step(det, g, '', 'fcos', losses, ('loss_cls', 'loss_bbox', 'loss_centerness'), keys, len(keys),
+                       zero_grad_ok=('.scales.', ))
 
 
 def test_outputs_and_detections_match_reference_fixture(det, golden):
-    """Per-level outputs of the training forward within 2.5e-4 of the fixture's strided samples (relative to max(1, |ref|): the
-    distances are exponentials); detections matched one to one within 1e-3 + 1e-5 * the largest coordinate, same class.  The
-    pyramid crosses the GroupNorm dispatch boundary (only 16 x 20 has more than 196 pixels), so both GroupNorm kernels are in it."""
+    """The bounds of dense_fixture_util.check_outputs (the distances are exponentials) and check_detections.  The pyramid crosses
+    the GroupNorm dispatch boundary (only 16 x 20 has more than 196 pixels), so both GroupNorm kernels are in it."""
     g = golden('fcos')
     img, metas, _, _ = inputs(torch.device(DEV))
-    det.train()
-    with torch.no_grad():
-        outs = det.bbox_head(det.extract_feat(img))
-    assert tuple(tuple(c.shape[-2:]) for c in outs[0]) == U.LEVEL_SIZES
-    worst = 0.0
-    for name, maps in zip(('cls', 'reg', 'ctr'), outs):
-        for l, t in enumerate(maps):
-            ref = g[f'{name}{l}.sample']
-            mine = BU.digest(t.cpu())[1]
-            tol = 2.5e-4 * np.maximum(1.0, np.abs(ref))
-            worst = max(worst, float((np.abs(mine - ref) / tol).max()))
-            assert (np.abs(mine - ref) <= tol).all(), f'{name}{l}'
+    worst = D.check_outputs(det, g, '', ('cls', 'reg', 'ctr'), U.LEVEL_SIZES, img)
     det.eval()
     with torch.no_grad():
         res = det.simple_test(img, metas)
-    worst_det = 0.0
-    for i in range(2):
-        mine, ref = BU.dets_array(res[i]), g[f'test_dets{i}']
-        assert mine.shape == ref.shape and len(ref) >= 10
-        used = np.zeros(len(mine), dtype=bool)
-        for r in ref:
-            d = np.abs(mine[:, :5] - r[:5]).max(1) + 1e3 * (mine[:, 5] != r[5]) + 1e3 * used
-            j = int(d.argmin())
-            worst_det = max(worst_det, d[j] / (1e-3 + 1e-5 * np.abs(r[:4]).max()))
-            assert d[j] <= 1e-3 + 1e-5 * np.abs(r[:4]).max(), (r, mine[j], d[j])
-            used[j] = True
-    print(f'fcos: worst output ratio {worst:.3f}, worst detection ratio {worst_det:.3f}')
+    print(f'fcos: worst output ratio {worst:.3f}, worst detection ratio {D.check_detections(res, g, ""):.3f}')
 
 
 def test_towers_on_the_smallest_levels_equal_torch_group_norm(det):
@@ -566,25 +502,13 @@ def test_batched_get_bboxes_equals_the_per_image_loop(det, golden, scale, nms_pr
 
 
 def test_reference_format_checkpoint_round_trip(golden, tmp_path):
-    """A `.pth` in the reference's wire format goes through load_checkpoint(strict=True) into a freshly built detector, which
-    reproduces the reference's detections."""
-    from htd_amd.checkpoint import load_checkpoint
+    """dense_fixture_util.check_checkpoint_round_trip on the FCOS fixture."""
     from htd_amd.configs import build_baseline_detector
     g = golden('fcos')
-    ref = U.fixture_state(g['state_keys'], g['state_shapes'], float(g['cls_scale']), float(g['cls_bias_shift']))
-    path = str(tmp_path / 'epoch_3.pth')
-    torch.save(dict(meta=dict(epoch=3, iter=100, mmdet_version='2.7.0', CLASSES=('person', )),
-                    state_dict={'module.' + k: v for k, v in ref.items()}), path)
-    torch.manual_seed(123)
-    model = build_baseline_detector(cfg=small_cfg(g))
-    ckpt = load_checkpoint(model, path, strict=True)
-    assert ckpt['meta']['epoch'] == 3
-    model = model.to(torch.device(DEV)).eval()
+    state = U.fixture_state(g['state_keys'], g['state_shapes'], float(g['cls_scale']), float(g['cls_bias_shift']))
     img, metas, _, _ = inputs(torch.device(DEV))
-    with torch.no_grad():
-        res = model.simple_test(img, metas)
-    for i in range(2):
-        match_detections(BU.dets_array(res[i]), g[f'test_dets{i}'])
+    ckpt = D.check_checkpoint_round_trip(lambda: build_baseline_detector(cfg=small_cfg(g)), state, g, '', img, metas, tmp_path, tol=1e-2)
+    assert ckpt['meta']['epoch'] == 3
 
 
 def test_transposed_batch_after_a_batch_gives_the_result_of_a_fresh_head(det):
@@ -623,7 +547,6 @@ def test_center_variant_trains_and_tests_through_the_fused_path():
     """The second reference config (centre sampling, stride-normalised distances, centerness on the regression tower, conv biases,
     GIoULoss): forward_train through the fused kernels with finite losses and gradients, simple_test with detections inside the
     images; its head-level arithmetic is held against the reference by test_fused_head_loss_against_the_reference_fp64_run."""
-    from htd_amd import capi
     from htd_amd.configs import build_baseline_detector, fcos_config
     cfg = fcos_config(50, U.VARIANT_OF['center'])
     cfg.test_cfg.score_thr = 1e-4
@@ -631,16 +554,7 @@ def test_center_variant_trains_and_tests_through_the_fused_path():
     model = U.load_fixture_weights_(model, 1.0, 5.0).to(torch.device(DEV))
     img, metas, gts, labels = inputs(torch.device(DEV))
     model.train()
-    calls, real = [], capi.call
-
-    def spy(name, *a, **k):
-        calls.append(name)
-        return real(name, *a, **k)
-    capi.call = spy
-    try:
-        loss, log_vars = model._parse_losses(model.forward_train(img, metas, gts, labels))
-    finally:
-        capi.call = real
+    (loss, log_vars), calls = D.spied(lambda: model._parse_losses(model.forward_train(img, metas, gts, labels)))
     assert calls.count('htd_fcos_loss') == 1
     loss.backward()
     assert np.isfinite(list(log_vars.values())).all() and log_vars['loss_bbox'] > 0 and log_vars['loss_centerness'] > 0

@@ -3,7 +3,7 @@ reference's own run (tests/golden/fovea.npz), the head's tensor path (pinned aga
 the fp64 formulas of fovea_util, the fused FoveaHead.loss against the reference's fp64 run, and both FOVEA detectors against the
 reference's.
 
-The bound of every value computed by a kernel is the project's rule (test_gpu_fcos.py:_bound): 4 x max(the reference's own fp32
+The bound of every value computed by a kernel is the project's rule (dense_fixture_util.bound): 4 x max(the reference's own fp32
 error on that case, one fp32 ulp of the largest entry); the fp32 error comes from the fixture or from the fp32 run of the formula
 on the CPU, never from the code under test.  Assignments are compared bit for bit.  The log targets are compared within
 LOG_TOL = 1.5 ulp of log 16: torch's CPU logarithm is good to one ulp (not correctly rounded), the kernel's is the rounding of
@@ -15,12 +15,13 @@ import pytest
 import torch
 
 import baselines_util as BU
+import dense_fixture_util as D
+from dense_fixture_util import EPS32, T, bound as _bound, err as _err, leave_the_allocator_as_found, spied as _spied  # noqa: F401
 import fovea_util as U
-from golden_util import match_detections, seeded_tensor
+from golden_util import seeded_tensor
 
 pytestmark = pytest.mark.gpu
 
-EPS32 = float(np.finfo(np.float32).eps)
 DEV = 'cuda:0'
 CL = torch.channels_last
 LOG_TOL = 1.5 * 2.0 ** -22              # 1.5 ulp of a value in [2, 4): log 16 = 2.77
@@ -29,55 +30,8 @@ PYRAMIDS = dict(five=(U.LEVEL_SIZES, U.STRIDES, U.BASE_EDGES, U.DEFAULT_RANGES),
                 one=(((1, 1), ), (8, ), (16, ), ((1, 2048), )))
 
 
-def T(a):
-    return torch.from_numpy(np.asarray(a))
-
-
-def _err(a, ref):
-    return float((a.detach().cpu().double() - ref).abs().max())
-
-
-def _bound(e32, ref):
-    """The rule of test_gpu_fcos.py: 4 x max(the reference's own fp32 error, one fp32 ulp of the largest entry)."""
-    return 4.0 * max(float(e32), EPS32 * float(ref.abs().max()))
-
-
-@pytest.fixture(scope='module', autouse=True)
-def _leave_the_allocator_as_found():
-    """The cached blocks of this module go back to the driver when it ends, and so do the small device tensors that its new shapes
-    added to the package's content-keyed caches (see test_gpu_gfl.py)."""
-    import gc
-    from htd_amd import capi, mmcv_ops as M
-    from htd_amd.core import bbox, misc
-    caches = (capi._TABLES, M._TOPK_PLANS, misc._CONSTS, misc._ARANGES, bbox._SAMPLE_PLANS)
-    before = [set(c) for c in caches]
-    yield
-    for c, keys in zip(caches, before):
-        for k in [k for k in c if k not in keys]:
-            del c[k]
-    bbox._PAD_GT_LAST.clear()
-    gc.collect()
-    torch.cuda.empty_cache()
-
-
 def inputs(dev):
-    imgs, metas, gts, labels = BU.detector_inputs()
-    return T(imgs).to(dev), metas, [T(x).to(dev) for x in gts], [T(x).to(dev) for x in labels]
-
-
-def _spied(fn):
-    """fn() with capi.call recorded -> (result, list of entry points)."""
-    from htd_amd import capi
-    calls, real = [], capi.call
-
-    def spy(name, *a, **k):
-        calls.append(name)
-        return real(name, *a, **k)
-    capi.call = spy
-    try:
-        return fn(), calls
-    finally:
-        capi.call = real
+    return D.inputs(dev, BU.detector_inputs)
 
 
 def _cpu_head(**extra):
@@ -481,9 +435,8 @@ def det(golden, request):
 
 
 def test_train_step_matches_reference_fixture(det, golden):
-    """Bounds of test_gpu_fcos.py::test_train_step_matches_reference_fixture: losses rtol 5e-4 / atol 1e-4; gradient digests in
-    units of 2e-4 * max(1, max |ref|) + 1e-3 * |ref|: no element over 2 units, rms at most 0.2.  `assigned` equals the fixture's.
-    The align config goes through the FeatureAlign kernels, once per level and direction."""
+    """The bounds of dense_fixture_util.check_train_step; `assigned` equals the fixture's.  The align config goes through the
+    FeatureAlign kernels, once per level and direction."""
     which, det = det
     g = golden('fovea')
     p = which + '.'
@@ -495,65 +448,22 @@ def test_train_step_matches_reference_fixture(det, golden):
     assigned, _, num_pos, norm = det.bbox_head._last_targets
     assert torch.equal(assigned.cpu().long(), T(g[p + 'assigned']).long())
     assert num_pos.tolist() == g[p + 'num_pos'].tolist() and float(norm[0]) == float(g[p + 'num_pos'].sum()) + 2
-    loss, log_vars = det._parse_losses(losses)
-    assert set(log_vars.keys()) == {f[len(p) + 5:] for f in g.files if f.startswith(p + 'loss.')} == {'loss_cls', 'loss_bbox', 'loss'}
-    det.zero_grad()
-    (_, calls) = _spied(lambda: loss.backward())
-    assert calls.count('htd_fovea_align_bwd') == (5 if which == 'align' else 0)
-    params = dict(det.named_parameters())
-    keys = U.grad_keys(det)
-    assert len(keys) >= 11, keys
-    worst, worst_rms, worst_loss = (0.0, ''), (0.0, ''), 0.0
-    for k, v in log_vars.items():
-        ref = float(g[f'{p}loss.{k}'])
-        worst_loss = max(worst_loss, abs(v - ref) / (1e-4 + 5e-4 * abs(ref)))
-    for k in keys:
-        ref = g[f'{p}grad.{k}.sample']
-        assert float(g[f'{p}grad.{k}.sums'][1]) > 0, k
-        tol = 2e-4 * max(1.0, np.abs(ref).max()) + 1e-3 * np.abs(ref)
-        ratio = np.abs(BU.digest(params[k].grad.cpu())[1] - ref) / tol
-        worst, worst_rms = max(worst, (float(ratio.max()), k)), max(worst_rms, (float(np.sqrt(np.mean(ratio ** 2))), k))
-    print(f'fovea {which}: worst loss ratio {worst_loss:.3f}; worst gradient element {worst[0]:.3f} units ({worst[1]}), '
-          f'worst rms {worst_rms[0]:.3f} ({worst_rms[1]})')
-    for k, v in log_vars.items():
-        np.testing.assert_allclose(v, float(g[f'{p}loss.{k}']), rtol=5e-4, atol=1e-4, err_msg=k)
-    assert worst[0] <= 2.0 and worst_rms[0] <= 0.2, (worst, worst_rms)
+    back = []
+    D.check_train_step(det, g, p, f'fovea {which}', losses, ('loss_cls', 'loss_bbox'), U.grad_keys(det), 11,
+                       backward=lambda loss: back.extend(_spied(loss.backward)[1]))
+    assert back.count('htd_fovea_align_bwd') == (5 if which == 'align' else 0)
 
 
 def test_outputs_and_detections_match_reference_fixture(det, golden):
-    """Per-level outputs of the training forward within 2.5e-4 of the fixture's strided samples (relative to max(1, |ref|));
-    detections matched one to one within 1e-3 + 1e-5 * the largest coordinate, same class."""
+    """The bounds of dense_fixture_util.check_outputs and check_detections."""
     which, det = det
     g = golden('fovea')
-    p = which + '.'
     img, metas, _, _ = inputs(torch.device(DEV))
-    det.train()
-    with torch.no_grad():
-        outs = det.bbox_head(det.extract_feat(img))
-    assert tuple(tuple(c.shape[-2:]) for c in outs[0]) == U.LEVEL_SIZES
-    worst = 0.0
-    for name, maps in zip(('cls', 'reg'), outs):
-        for l, t in enumerate(maps):
-            ref = g[f'{p}{name}{l}.sample']
-            mine = BU.digest(t.cpu())[1]
-            tol = 2.5e-4 * np.maximum(1.0, np.abs(ref))
-            worst = max(worst, float((np.abs(mine - ref) / tol).max()))
-            assert (np.abs(mine - ref) <= tol).all(), f'{name}{l}'
+    worst = D.check_outputs(det, g, which + '.', ('cls', 'reg'), U.LEVEL_SIZES, img)
     det.eval()
     with torch.no_grad():
         res = det.simple_test(img, metas)
-    worst_det = 0.0
-    for i in range(2):
-        mine, ref = BU.dets_array(res[i]), g[f'{p}test_dets{i}']
-        assert mine.shape == ref.shape and len(ref) >= 10
-        used = np.zeros(len(mine), dtype=bool)
-        for r in ref:
-            d = np.abs(mine[:, :5] - r[:5]).max(1) + 1e3 * (mine[:, 5] != r[5]) + 1e3 * used
-            j = int(d.argmin())
-            worst_det = max(worst_det, d[j] / (1e-3 + 1e-5 * np.abs(r[:4]).max()))
-            assert d[j] <= 1e-3 + 1e-5 * np.abs(r[:4]).max(), (r, mine[j], d[j])
-            used[j] = True
-    print(f'fovea {which}: worst output ratio {worst:.3f}, worst detection ratio {worst_det:.3f}')
+    print(f'fovea {which}: worst output ratio {worst:.3f}, worst detection ratio {D.check_detections(res, g, which + "."):.3f}')
 
 
 @pytest.mark.parametrize('nms_pre', ['fixture', -1])
@@ -597,24 +507,12 @@ def test_batched_get_bboxes_equals_the_per_image_loop(det, golden, nms_pre):
 
 
 def test_reference_format_checkpoint_round_trip(det, golden, tmp_path):
-    """A `.pth` in the reference's wire format goes through load_checkpoint(strict=True) into a freshly built detector, which
-    reproduces the reference's detections."""
-    from htd_amd.checkpoint import load_checkpoint
+    """dense_fixture_util.check_checkpoint_round_trip on both FoveaBox fixtures."""
     from htd_amd.configs import build_fovea_detector
     which, _ = det
     g = golden('fovea')
     p = which + '.'
-    ref = U.fixture_state(g[p + 'state_keys'], g[p + 'state_shapes'], float(g[p + 'cls_scale']), float(g[p + 'cls_bias_shift']))
-    path = str(tmp_path / 'epoch_3.pth')
-    torch.save(dict(meta=dict(epoch=3, iter=100, mmdet_version='2.7.0', CLASSES=('person', )),
-                    state_dict={'module.' + k: v for k, v in ref.items()}), path)
-    torch.manual_seed(123)
-    model = build_fovea_detector(cfg=small_cfg(g, which))
-    ckpt = load_checkpoint(model, path, strict=True)
-    assert ckpt['meta']['epoch'] == 3
-    model = model.to(torch.device(DEV)).eval()
+    state = U.fixture_state(g[p + 'state_keys'], g[p + 'state_shapes'], float(g[p + 'cls_scale']), float(g[p + 'cls_bias_shift']))
     img, metas, _, _ = inputs(torch.device(DEV))
-    with torch.no_grad():
-        res = model.simple_test(img, metas)
-    for i in range(2):
-        match_detections(BU.dets_array(res[i]), g[f'{p}test_dets{i}'], tol=1e-3)
+    ckpt = D.check_checkpoint_round_trip(lambda: build_fovea_detector(cfg=small_cfg(g, which)), state, g, p, img, metas, tmp_path, tol=1e-3)
+    assert ckpt['meta']['epoch'] == 3

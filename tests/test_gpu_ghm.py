@@ -18,25 +18,14 @@ import pytest
 import torch
 
 import baselines_util as BU
+import dense_fixture_util as D
+from dense_fixture_util import EPS32, T, bound as _bound, err as _err  # noqa: F401
 import ghm_util as U
 import retina_util as RU
 
 pytestmark = pytest.mark.gpu
 
-EPS32 = float(np.finfo(np.float32).eps)
 DEV = 'cuda:0'
-
-
-def T(a):
-    return torch.from_numpy(np.asarray(a))
-
-
-def _err(a, ref):
-    return float((torch.as_tensor(a).detach().cpu().double() - torch.as_tensor(ref).double()).abs().max())
-
-
-def _bound(e32, ref):
-    return 4.0 * max(float(e32), EPS32 * float(torch.as_tensor(ref).abs().max()))
 
 
 def _module(kind, bins, mmt, loss_weight=1.0):
@@ -359,8 +348,7 @@ def test_head_kernel_wraps_its_grid():
 
 # ---------------------------------------------------------------------------------------------------- the detector
 def inputs(dev):
-    imgs, metas, gts, labels = BU.detector_inputs()
-    return T(imgs).to(dev), metas, [T(x).to(dev) for x in gts], [T(x).to(dev) for x in labels]
+    return D.inputs(dev, BU.detector_inputs)
 
 
 @pytest.fixture(scope='module')
@@ -378,51 +366,22 @@ def _reset(det):
 
 
 def test_train_step_matches_reference_fixture(det, golden):
-    """Losses within rtol 5e-4 + atol 1e-4 (the RetinaNet fixture's bound; the fixture's flip bound of 1e-4, asserted by its
-    generator, fits inside), gradient digests in units of 2e-4 * max(1, max |ref|) + 1e-3 * |ref|: no element over 2 units, rms at
-    most 0.2; `assigned` equals the fixture's; acc_sum of both losses within rtol 1e-5; one htd_ghm_head_loss call."""
-    from htd_amd import capi
+    """The bounds of dense_fixture_util.check_train_step (the fixture's flip bound of 1e-4, asserted by its generator, fits inside
+    the bound of the losses); `assigned` equals the fixture's; acc_sum of both losses within rtol 1e-5; one htd_ghm_head_loss call."""
     g = golden('ghm')
     assert float(g['flip.loss'].max()) <= 1e-4 and float(g['flip.grad'].max()) <= 1e-4
     img, metas, gts, labels = inputs(torch.device(DEV))
     det.train()
     _reset(det)
-    calls, real = [], capi.call
-
-    def spy(name, *a, **k):
-        calls.append(name)
-        return real(name, *a, **k)
-    capi.call = spy
-    try:
-        losses = det.forward_train(img, metas, gts, labels)
-    finally:
-        capi.call = real
+    losses, calls = D.spied(lambda: det.forward_train(img, metas, gts, labels))
     assert calls.count('htd_ghm_head_loss') == 1 and 'htd_retina_loss' not in calls
     assert torch.equal(det.bbox_head._last_assigned[0].cpu(), T(g['assigned']).long())
-    loss, log_vars = det._parse_losses(losses)
-    assert set(log_vars.keys()) == {f[5:] for f in g.files if f.startswith('loss.')} == {'loss_cls', 'loss_bbox', 'loss'}
-    det.zero_grad()
-    loss.backward()
-    params = dict(det.named_parameters())
     keys = RU.grad_keys(det)
     assert len(keys) == 5 + len(RU.EXTRA_GRAD_KEYS), keys
-    worst, worst_rms, worst_loss = (0.0, ''), (0.0, ''), 0.0
-    for k, v in log_vars.items():
-        ref = float(g[f'loss.{k}'])
-        worst_loss = max(worst_loss, abs(v - ref) / (1e-4 + 5e-4 * abs(ref)))
-    for k in keys:
-        ref = g[f'grad.{k}.sample']
-        assert float(g[f'grad.{k}.sums'][1]) > 0, k
-        tol = 2e-4 * max(1.0, np.abs(ref).max()) + 1e-3 * np.abs(ref)
-        ratio = np.abs(BU.digest(params[k].grad.cpu())[1] - ref) / tol
-        worst, worst_rms = max(worst, (float(ratio.max()), k)), max(worst_rms, (float(np.sqrt(np.mean(ratio ** 2))), k))
+    D.check_train_step(det, g, '', 'retinanet-ghm', losses, ('loss_cls', 'loss_bbox'), keys, len(keys))
     acc_c, acc_r = det.bbox_head.loss_cls.acc_sum.cpu().numpy(), det.bbox_head.loss_bbox.acc_sum.cpu().numpy()
     rel = max(float(np.abs(a[r > 0] / r[r > 0] - 1).max()) for a, r in ((acc_c, g['acc_c']), (acc_r, g['acc_r'])))
-    print(f'retinanet-ghm: worst loss ratio {worst_loss:.3f}; worst gradient element {worst[0]:.3f} units ({worst[1]}), '
-          f'worst rms {worst_rms[0]:.3f} ({worst_rms[1]}); acc_sum worst relative {rel:.2e}')
-    for k, v in log_vars.items():
-        np.testing.assert_allclose(v, float(g[f'loss.{k}']), rtol=5e-4, atol=1e-4, err_msg=k)
-    assert worst[0] <= 2.0 and worst_rms[0] <= 0.2, (worst, worst_rms)
+    print(f'retinanet-ghm: acc_sum worst relative {rel:.2e}')
     np.testing.assert_allclose(acc_c, g['acc_c'], rtol=1e-5)
     np.testing.assert_allclose(acc_r, g['acc_r'], rtol=1e-5)
 

@@ -11,26 +11,13 @@ import pytest
 import torch
 
 import baselines_util as BU
+import dense_fixture_util as D
+from dense_fixture_util import EPS32, T, bound as _bound, err as _err  # noqa: F401
 import retina_util as U
-from golden_util import match_detections
 
 pytestmark = pytest.mark.gpu
 
-EPS32 = float(np.finfo(np.float32).eps)
 DEV = 'cuda:0'
-
-
-def T(a):
-    return torch.from_numpy(np.asarray(a))
-
-
-def _err(a, ref):
-    return float((a.detach().cpu().double() - ref).abs().max())
-
-
-def _bound(e32, ref):
-    """The rule of test_gpu_iou_losses.py: 4 x max(the reference's own fp32 error, one fp32 ulp of the largest entry)."""
-    return 4.0 * max(float(e32), EPS32 * float(ref.abs().max()))
 
 
 # ---------------------------------------------------------------------------------------------------- the matrix kernel
@@ -214,8 +201,7 @@ def small_cfg(g):
 
 
 def inputs(dev):
-    imgs, metas, gts, labels = BU.detector_inputs()
-    return T(imgs).to(dev), metas, [T(x).to(dev) for x in gts], [T(x).to(dev) for x in labels]
+    return D.inputs(dev, BU.detector_inputs)
 
 
 @pytest.fixture(scope='module')
@@ -227,53 +213,23 @@ def det(golden):
 
 
 def test_train_step_matches_reference_fixture(det, golden):
-    """Bounds of test_gpu_baselines.py::test_train_step_matches_reference_fixture: losses rtol 5e-4 / atol 1e-4; gradient digests in
-    units of 2e-4 * max(1, max |ref|) + 1e-3 * |ref|: no element over 2 units, rms at most 0.2.  `assigned` equals the fixture's."""
-    from htd_amd import capi
+    """The bounds of dense_fixture_util.check_train_step; `assigned` equals the fixture's and the step takes one htd_retina_loss."""
     g = golden('retinanet')
     img, metas, gts, labels = inputs(torch.device(DEV))
     det.train()
-    calls, real = [], capi.call
-
-    def spy(name, *a, **k):
-        calls.append(name)
-        return real(name, *a, **k)
-    capi.call = spy
-    try:
-        losses = det.forward_train(img, metas, gts, labels)
-    finally:
-        capi.call = real
+    losses, calls = D.spied(lambda: det.forward_train(img, metas, gts, labels))
     assert 'htd_retina_loss' in calls and calls.count('htd_retina_loss') == 1
     assigned, num_pos, avg = det.bbox_head._last_assigned
     assert torch.equal(assigned.cpu(), T(g['assigned']).long())
     assert num_pos.tolist() == g['num_pos'].tolist() and float(avg) == float(g['num_pos'].sum())
-    loss, log_vars = det._parse_losses(losses)
-    assert set(log_vars.keys()) == {f[5:] for f in g.files if f.startswith('loss.')} == {'loss_cls', 'loss_bbox', 'loss'}
-    det.zero_grad()
-    loss.backward()
-    params = dict(det.named_parameters())
     keys = U.grad_keys(det)
     assert len(keys) == 5 + len(U.EXTRA_GRAD_KEYS), keys
-    worst, worst_rms, worst_loss = (0.0, ''), (0.0, ''), 0.0
-    for k, v in log_vars.items():
-        ref = float(g[f'loss.{k}'])
-        worst_loss = max(worst_loss, abs(v - ref) / (1e-4 + 5e-4 * abs(ref)))
-    for k in keys:
-        ref = g[f'grad.{k}.sample']
-        assert float(g[f'grad.{k}.sums'][1]) > 0, k
-        tol = 2e-4 * max(1.0, np.abs(ref).max()) + 1e-3 * np.abs(ref)
-        ratio = np.abs(BU.digest(params[k].grad.cpu())[1] - ref) / tol
-        worst, worst_rms = max(worst, (float(ratio.max()), k)), max(worst_rms, (float(np.sqrt(np.mean(ratio ** 2))), k))
-    print(f'retinanet: worst loss ratio {worst_loss:.3f}; worst gradient element {worst[0]:.3f} units ({worst[1]}), '
-          f'worst rms {worst_rms[0]:.3f} ({worst_rms[1]})')
-    for k, v in log_vars.items():
-        np.testing.assert_allclose(v, float(g[f'loss.{k}']), rtol=5e-4, atol=1e-4, err_msg=k)
-    assert worst[0] <= 2.0 and worst_rms[0] <= 0.2, (worst, worst_rms)
+    D.check_train_step(det, g, '', 'retinanet', losses, ('loss_cls', 'loss_bbox'), keys, len(keys))
 
 
 def test_logits_and_detections_match_reference_fixture(det, golden):
-    """Per-level logits and deltas of the training forward within 2.5e-4 (the fixture's strided samples); detections matched one to
-    one within 1e-3 + 1e-5 * the largest coordinate, same class."""
+    """Per-level logits and deltas of the training forward within 2.5e-4 (the fixture's strided samples); detections under the
+    bounds of dense_fixture_util.check_detections."""
     g = golden('retinanet')
     img, metas, _, _ = inputs(torch.device(DEV))
     det.train()
@@ -290,18 +246,7 @@ def test_logits_and_detections_match_reference_fixture(det, golden):
     det.eval()
     with torch.no_grad():
         res = det.simple_test(img, metas)
-    worst_det = 0.0
-    for i in range(2):
-        mine, ref = BU.dets_array(res[i]), g[f'test_dets{i}']
-        assert mine.shape == ref.shape and len(ref) >= 10
-        used = np.zeros(len(mine), dtype=bool)
-        for r in ref:
-            d = np.abs(mine[:, :5] - r[:5]).max(1) + 1e3 * (mine[:, 5] != r[5]) + 1e3 * used
-            j = int(d.argmin())
-            worst_det = max(worst_det, d[j] / (1e-3 + 1e-5 * np.abs(r[:4]).max()))
-            assert d[j] <= 1e-3 + 1e-5 * np.abs(r[:4]).max(), (r, mine[j], d[j])
-            used[j] = True
-    print(f'retinanet: worst logit ratio {worst:.3f}, worst detection ratio {worst_det:.3f}')
+    print(f'retinanet: worst logit ratio {worst:.3f}, worst detection ratio {D.check_detections(res, g, ""):.3f}')
 
 
 def test_fused_head_loss_matches_tensor_path_bitwise_repeatable_and_reads_nothing(det, monkeypatch):
@@ -389,37 +334,13 @@ def test_batched_get_bboxes_equals_the_per_image_loop(det, scale):
 
 
 def test_reference_format_checkpoint_round_trip(golden, tmp_path):
-    """A `.pth` in the reference's wire format goes through load_checkpoint(strict=True) into a freshly built detector, which
-    reproduces the reference's detections."""
-    from golden_util import seeded_state_value
-    from htd_amd.checkpoint import load_checkpoint
+    """dense_fixture_util.check_checkpoint_round_trip on the RetinaNet fixture."""
     from htd_amd.configs import build_retinanet_detector
     g = golden('retinanet')
-    ref = {}
-    for k, shape in zip(g['state_keys'], g['state_shapes']):
-        k = str(k)
-        if k.endswith('num_batches_tracked'):
-            ref[k] = torch.zeros((), dtype=torch.int64)
-            continue
-        v = torch.from_numpy(np.asarray(seeded_state_value('det.' + k, [int(s) for s in shape if s])))
-        if k == 'bbox_head.retina_cls.weight':
-            v = v * float(g['cls_scale'])
-        if k == 'bbox_head.retina_cls.bias':
-            v = v - U.CLS_BIAS_SHIFT
-        ref[k] = v
-    path = str(tmp_path / 'epoch_3.pth')
-    torch.save(dict(meta=dict(epoch=3, iter=100, mmdet_version='2.7.0', CLASSES=('person', )),
-                    state_dict={'module.' + k: v for k, v in ref.items()}), path)
-    torch.manual_seed(123)
-    model = build_retinanet_detector(cfg=small_cfg(g))
-    ckpt = load_checkpoint(model, path, strict=True)
-    assert ckpt['meta']['epoch'] == 3
-    model = model.to(torch.device(DEV)).eval()
+    state = U.fixture_state(g['state_keys'], g['state_shapes'], float(g['cls_scale']))
     img, metas, _, _ = inputs(torch.device(DEV))
-    with torch.no_grad():
-        res = model.simple_test(img, metas)
-    for i in range(2):
-        match_detections(BU.dets_array(res[i]), g[f'test_dets{i}'])
+    ckpt = D.check_checkpoint_round_trip(lambda: build_retinanet_detector(cfg=small_cfg(g)), state, g, '', img, metas, tmp_path, tol=1e-2)
+    assert ckpt['meta']['epoch'] == 3
 
 
 def test_transposed_batch_after_a_batch_gives_the_result_of_a_fresh_head(det):

@@ -3,7 +3,7 @@
 the deformable convolution on star offsets, the dispatch rule, the batched get_bboxes, and the VFNet detector against the
 reference's.
 
-The bound of every value computed by a kernel is the project's rule (test_gpu_fcos.py:_bound): 4 x max(the reference's own fp32
+The bound of every value computed by a kernel is the project's rule (dense_fixture_util.bound): 4 x max(the reference's own fp32
 error on that case, one fp32 ulp of the largest entry); the fp32 error comes from the fixture or from the fp32 run of the tensor
 path on the CPU, never from the code under test.  Assignments are compared bit for bit.  No detector stays on the device between
 tests."""
@@ -13,68 +13,26 @@ import torch
 
 import baselines_util as BU
 import dcn_ref as R
-import vfnet_util as U
+import dense_fixture_util as D
+from dense_fixture_util import EPS32, bound as _bound, err as _err, leave_the_allocator_as_found, spied as _spied  # noqa: F401
 from golden_util import seeded_tensor
 from test_vfnet import E_GCLS, E_GCLSPOS, E_GREF, E_GREG, E_INI, E_RF, E_SUMS, KEYS, T
+import vfnet_util as U
 
 pytestmark = pytest.mark.gpu
 
-EPS32 = float(np.finfo(np.float32).eps)
 DEV = 'cuda:0'
 CL = torch.channels_last
 ENTRIES = ('htd_atss_targets', 'htd_vfnet_quality', 'htd_vfnet_loss')
 
 
-def _err(a, ref):
-    return float((a.detach().cpu().double() - ref).abs().max())
-
-
-def _bound(e32, ref):
-    """The rule of test_gpu_fcos.py: 4 x max(the reference's own fp32 error, one fp32 ulp of the largest entry)."""
-    return 4.0 * max(float(e32), EPS32 * float(ref.abs().max()))
-
-
-@pytest.fixture(scope='module', autouse=True)
-def _leave_the_allocator_as_found():
-    """The cached blocks of this module go back to the driver when it ends, and so do the small device tensors that its new shapes
-    added to the package's content-keyed caches (see test_gpu_gfl.py)."""
-    import gc
-    from htd_amd import capi, mmcv_ops as M
-    from htd_amd.core import bbox, misc
-    caches = (capi._TABLES, M._TOPK_PLANS, misc._CONSTS, misc._ARANGES, bbox._SAMPLE_PLANS)
-    before = [set(c) for c in caches]
-    yield
-    for c, keys in zip(caches, before):
-        for k in [k for k in c if k not in keys]:
-            del c[k]
-    bbox._PAD_GT_LAST.clear()
-    gc.collect()
-    torch.cuda.empty_cache()
-
-
 def inputs(dev):
-    imgs, metas, gts, labels = U.detector_inputs()
-    return T(imgs).to(dev), metas, [T(x).to(dev) for x in gts], [T(x).to(dev) for x in labels]
+    return D.inputs(dev, U.detector_inputs)
 
 
 def _head_on_device(v='giou', **extra):
     from test_vfnet import build_head
     return build_head(v, **extra).to(torch.device(DEV))
-
-
-def _spied(fn):
-    """fn() with capi.call recorded -> (result, list of entry points)."""
-    from htd_amd import capi
-    calls, real = [], capi.call
-
-    def spy(name, *a, **k):
-        calls.append(name)
-        return real(name, *a, **k)
-    capi.call = spy
-    try:
-        return fn(), calls
-    finally:
-        capi.call = real
 
 
 def _on_dev(ms, dev=None):
@@ -521,9 +479,8 @@ def det(golden):
 
 
 def test_train_step_matches_reference_fixture(det, golden):
-    """Bounds of test_gpu_gfl.py::test_train_step_matches_reference_fixture: losses rtol 5e-4 / atol 1e-4; gradient digests in
-    units of 2e-4 * max(1, max |ref|) + 1e-3 * |ref|: no element over 2 units, rms at most 0.2.  `assigned` equals the fixture's
-    and the step reaches the kernels: five htd_vfnet_star_fwd and _bwd, one htd_atss_targets, htd_vfnet_quality, htd_vfnet_loss."""
+    """The bounds of dense_fixture_util.check_train_step; `assigned` equals the fixture's and the step reaches the kernels: five
+    htd_vfnet_star_fwd and _bwd, one htd_atss_targets, htd_vfnet_quality, htd_vfnet_loss."""
     g = golden('vfnet')
     img, metas, gts, labels = inputs(torch.device(DEV))
     det.train()
@@ -532,57 +489,21 @@ def test_train_step_matches_reference_fixture(det, golden):
     assigned, num_pos, norm = det.bbox_head._last_targets
     assert torch.equal(assigned.cpu().long(), T(g['assigned']).long())
     assert num_pos.tolist() == g['num_pos'].tolist() and float(det.bbox_head._last_quality[2][0]) == float(g['num_pos'].sum())
-    loss, log_vars = det._parse_losses(losses)
-    assert set(log_vars.keys()) == {f[5:] for f in g.files if f.startswith('loss.')} == {'loss_cls', 'loss_bbox', 'loss_bbox_rf', 'loss'}
-    det.zero_grad()
-    _, calls = _spied(loss.backward)
-    assert calls.count('htd_vfnet_star_bwd') == 5
-    params = dict(det.named_parameters())
-    keys = U.grad_keys(det)
-    assert len(keys) >= 3 + len(U.EXTRA_GRAD_KEYS), keys
-    worst, worst_rms, worst_loss = (0.0, ''), (0.0, ''), 0.0
-    for k, v in log_vars.items():
-        ref = float(g[f'loss.{k}'])
-        worst_loss = max(worst_loss, abs(v - ref) / (1e-4 + 5e-4 * abs(ref)))
-    for k in keys:
-        ref = g[f'grad.{k}.sample']
-        tol = 2e-4 * max(1.0, np.abs(ref).max()) + 1e-3 * np.abs(ref)
-        ratio = np.abs(BU.digest(params[k].grad.cpu())[1] - ref) / tol
-        worst, worst_rms = max(worst, (float(ratio.max()), k)), max(worst_rms, (float(np.sqrt(np.mean(ratio ** 2))), k))
-    print(f'vfnet: worst loss ratio {worst_loss:.3f}; worst gradient element {worst[0]:.3f} units ({worst[1]}), '
-          f'worst rms {worst_rms[0]:.3f} ({worst_rms[1]})')
-    for k, v in log_vars.items():
-        np.testing.assert_allclose(v, float(g[f'loss.{k}']), rtol=5e-4, atol=1e-4, err_msg=k)
-    assert worst[0] <= 2.0 and worst_rms[0] <= 0.2, (worst, worst_rms)
+    back = []
+    D.check_train_step(det, g, '', 'vfnet', losses, ('loss_cls', 'loss_bbox', 'loss_bbox_rf'), U.grad_keys(det),
+                       3 + len(U.EXTRA_GRAD_KEYS), zero_grad_ok=('.scales.', ), backward=lambda loss: back.extend(_spied(loss.backward)[1]))
+    assert back.count('htd_vfnet_star_bwd') == 5
 
 
 def test_outputs_and_detections_match_reference_fixture(det, golden):
-    """Per-level outputs of the training forward within 2.5e-4 of the fixture's strided samples (relative to max(1, |ref|));
-    detections of simple_test matched one to one within 1e-3 + 1e-5 * the largest coordinate, same class (the bounds of
-    test_gpu_gfl.py)."""
+    """The bounds of dense_fixture_util.check_outputs and check_detections."""
     g = golden('vfnet')
     img, metas, _, _ = inputs(torch.device(DEV))
-    det.train()
-    with torch.no_grad():
-        outs = det.bbox_head(det.extract_feat(img))
-    assert tuple(tuple(c.shape[-2:]) for c in outs[0]) == U.LEVEL_SIZES
-    for name, maps in zip(('cls', 'reg', 'ref'), outs):
-        for l, t in enumerate(maps):
-            ref = g[f'{name}{l}.sample']
-            mine = BU.digest(t.cpu())[1]
-            assert (np.abs(mine - ref) <= 2.5e-4 * np.maximum(1.0, np.abs(ref))).all(), f'{name}{l}'
+    worst = D.check_outputs(det, g, '', ('cls', 'reg', 'ref'), U.LEVEL_SIZES, img)
     det.eval()
     with torch.no_grad():
         res = det.simple_test(img, metas)
-    for i in range(2):
-        mine, ref = BU.dets_array(res[i]), g[f'test_dets{i}']
-        assert mine.shape == ref.shape and len(ref) >= 10
-        used = np.zeros(len(mine), dtype=bool)
-        for r in ref:
-            d = np.abs(mine[:, :5] - r[:5]).max(1) + 1e3 * (mine[:, 5] != r[5]) + 1e3 * used
-            j = int(d.argmin())
-            assert d[j] <= 1e-3 + 1e-5 * np.abs(r[:4]).max(), (r, mine[j], d[j])
-            used[j] = True
+    print(f'vfnet: worst output ratio {worst:.3f}, worst detection ratio {D.check_detections(res, g, ""):.3f}')
 
 
 def test_fused_and_tensor_path_train_steps_agree(det, golden):
@@ -600,22 +521,9 @@ def test_fused_and_tensor_path_train_steps_agree(det, golden):
 
 
 def test_reference_format_checkpoint_round_trip(golden, tmp_path):
-    """A `.pth` in the reference's wire format goes through load_checkpoint(strict=True) into a freshly built detector, which
-    reproduces the reference's detections."""
-    from golden_util import match_detections
-    from htd_amd.checkpoint import load_checkpoint
+    """dense_fixture_util.check_checkpoint_round_trip on the VFNet fixture."""
     from htd_amd.configs import build_baseline_detector
     g = golden('vfnet')
-    ref = U.fixture_state(g['state_keys'], g['state_shapes'], float(g['cls_scale']), float(g['cls_bias_shift']))
-    path = str(tmp_path / 'epoch_3.pth')
-    torch.save(dict(meta=dict(epoch=3, iter=100, mmdet_version='2.7.0', CLASSES=('person', )),
-                    state_dict={'module.' + k: v for k, v in ref.items()}), path)
-    torch.manual_seed(123)
-    model = build_baseline_detector(cfg=small_cfg(g))
-    load_checkpoint(model, path, strict=True)
-    model = model.to(torch.device(DEV)).eval()
+    state = U.fixture_state(g['state_keys'], g['state_shapes'], float(g['cls_scale']), float(g['cls_bias_shift']))
     img, metas, _, _ = inputs(torch.device(DEV))
-    with torch.no_grad():
-        res = model.simple_test(img, metas)
-    for i in range(2):
-        match_detections(BU.dets_array(res[i]), g[f'test_dets{i}'])
+    D.check_checkpoint_round_trip(lambda: build_baseline_detector(cfg=small_cfg(g)), state, g, '', img, metas, tmp_path, tol=1e-2)

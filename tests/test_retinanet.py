@@ -9,13 +9,10 @@ import pytest
 import torch
 
 import baselines_util as BU
+from dense_fixture_util import T
 import retina_util as U
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
-
-
-def T(a):
-    return torch.from_numpy(np.asarray(a))
 
 
 def test_retinanet_config_equals_the_reference_merged_config():

@@ -14,18 +14,15 @@ import pytest
 import torch
 
 import baselines_util as BU
-import vfnet_util as U
+import dense_fixture_util as D
+from dense_fixture_util import EPS32, T
 from golden_util import seeded_tensor
+import vfnet_util as U
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
-EPS32 = 2.0 ** -23
 KEYS = ('loss_cls', 'loss_bbox', 'loss_bbox_rf')
 # head.{v}.err32: |fp32 - fp64| of [3 losses, gcls, greg, gref, iou_ini, iou_rf, gclspos, 3 sums]
 E_GCLS, E_GREG, E_GREF, E_INI, E_RF, E_GCLSPOS, E_SUMS = 3, 4, 5, 6, 7, 8, 9
-
-
-def T(a):
-    return torch.from_numpy(np.asarray(a))
 
 
 def build_head(variant='giou', **extra):
@@ -37,8 +34,7 @@ def build_head(variant='giou', **extra):
 
 
 def inputs():
-    _, metas, gts, labels = U.detector_inputs()
-    return metas, [T(g) for g in gts], [T(l) for l in labels]
+    return D.inputs('cpu', U.detector_inputs)[1:]
 
 
 def head_losses(ls):
@@ -128,9 +124,7 @@ def test_a_reference_format_checkpoint_loads_without_the_pre_2_0_rename(golden, 
     from htd_amd.configs import build_baseline_detector
     g = golden('vfnet')
     ref = U.fixture_state(g['state_keys'], g['state_shapes'], float(g['cls_scale']), float(g['cls_bias_shift']))
-    path = str(tmp_path / 'epoch_3.pth')
-    torch.save(dict(meta=dict(epoch=3, iter=100, mmdet_version='2.7.0', CLASSES=('person', )),
-                    state_dict={'module.' + k: v for k, v in ref.items()}), path)
+    path = D.save_reference_checkpoint(ref, tmp_path)
     torch.manual_seed(123)
     model = build_baseline_detector('vfnet')
     load_checkpoint(model, path, strict=True)

@@ -1,13 +1,13 @@
 """Shared by tests/golden/make_golden_vfnet.py, tests/test_vfnet.py and tests/test_gpu_vfnet.py: the inputs of the VFNet fixture
 (tests/golden/vfnet.npz), re-created from seeds so the fixture holds results only.  The images, boxes, level sizes and anchors
 are atss_util's (its anchors are centred on the grid nodes: centre offset 0, VFNet's)."""
-import numpy as np
 import torch
 
 import atss_util as AU
 from atss_util import (LEVEL_ANCHORS, LEVEL_SIZES, STRIDES, TOPK, TRAIN_CFG, anchors_of, detector_inputs, maps_to_rows,  # noqa: F401
                        pad_gts)
-from golden_util import load_seeded_, seeded_tensor
+import dense_fixture_util as D
+from golden_util import seeded_tensor
 
 CONFIGS = dict(r50='configs/vfnet/vfnet_r50_fpn_1x_coco.py', r101_mstrain='configs/vfnet/vfnet_r101_fpn_mstrain_2x_coco.py')
 CONFIG_ARGS = dict(r50=dict(depth=50), r101_mstrain=dict(depth=101, mstrain=True))
@@ -73,53 +73,25 @@ def head_maps(variant='giou', B=2, C=80, sizes=LEVEL_SIZES, strides=STRIDES, tag
     return cls, reg, ref
 
 
+# the fixture's weights (dense_fixture_util): the level scales of both groups at 1 + a quarter of a seeded normal, the
+# classification layer scaled and its bias lowered by the two figures the fixture records (plainly seeded, the logits saturate
+# the sigmoid and the ranking keys crowd), both regression layers scaled by REG_SCALE
+FIXTURE = dict(scales=('scales', 'scales_refine'),
+               edits=(('bbox_head.vfnet_cls.weight', 'mul', 'scale'), ('bbox_head.vfnet_cls.bias', 'sub', 'bias_shift'),
+                      ('bbox_head.vfnet_reg.weight', 'mul', REG_SCALE), ('bbox_head.vfnet_reg.bias', 'mul', REG_SCALE),
+                      ('bbox_head.vfnet_reg_refine.weight', 'mul', REG_SCALE), ('bbox_head.vfnet_reg_refine.bias', 'mul', REG_SCALE)))
+
+
 def load_fixture_weights_(det, scale, bias_shift):
-    """The values of load_seeded_(det, 'det.') with the level scales at 1 + a quarter of a seeded normal, the classification layer
-    scaled and its bias lowered by the two figures the fixture records (plainly seeded, the logits saturate the sigmoid and the
-    ranking keys crowd), and both regression layers scaled by REG_SCALE."""
-    from golden_util import seeded_array
-    load_seeded_(det.backbone, 'det.backbone.')
-    load_seeded_(det.neck, 'det.neck.')
-    head = det.bbox_head
-    for name, child in head.named_children():
-        if name not in ('scales', 'scales_refine') and len(list(child.state_dict())) > 0:
-            load_seeded_(child, f'det.bbox_head.{name}.')
-    with torch.no_grad():
-        for group in ('scales', 'scales_refine'):
-            for l, s in enumerate(getattr(head, group)):
-                s.scale.fill_(1.0 + 0.25 * float(seeded_array(f'det.bbox_head.{group}.{l}.scale', (1, ))[0]))
-        head.vfnet_cls.weight.mul_(float(scale))
-        head.vfnet_cls.bias.sub_(float(bias_shift))
-        for m in (head.vfnet_reg, head.vfnet_reg_refine):
-            m.weight.mul_(REG_SCALE)
-            m.bias.mul_(REG_SCALE)
-    return det
+    return D.load_fixture_weights(det, **FIXTURE, scale=scale, bias_shift=bias_shift)
 
 
 def fixture_state(keys, shapes, scale, bias_shift):
-    """The state dict load_fixture_weights_ leaves, from the fixture's key and shape lists (shapes padded to 4 dims with 0)."""
-    from golden_util import seeded_array, seeded_state_value
-    out = {}
-    for k, shape in zip(keys, shapes):
-        k, shape = str(k), [int(s) for s in shape if s]
-        if k.endswith('num_batches_tracked'):
-            out[k] = torch.zeros((), dtype=torch.int64)
-        elif k.startswith('bbox_head.scales'):
-            out[k] = torch.tensor(1.0 + 0.25 * float(seeded_array('det.' + k, (1, ))[0]))
-        else:
-            out[k] = torch.from_numpy(np.asarray(seeded_state_value('det.' + k, shape)))
-    out['bbox_head.vfnet_cls.weight'] = out['bbox_head.vfnet_cls.weight'] * float(scale)
-    out['bbox_head.vfnet_cls.bias'] = out['bbox_head.vfnet_cls.bias'] - float(bias_shift)
-    for name in ('vfnet_reg', 'vfnet_reg_refine'):
-        for p in ('weight', 'bias'):
-            out[f'bbox_head.{name}.{p}'] = out[f'bbox_head.{name}.{p}'] * REG_SCALE
-    return out
+    return D.fixture_state(keys, shapes, **FIXTURE, scale=scale, bias_shift=bias_shift)
 
 
 def grad_keys(det):
-    from baselines_util import GRAD_KEYS
-    names = dict(det.named_parameters())
-    return [k for k in GRAD_KEYS + EXTRA_GRAD_KEYS if k in names and names[k].requires_grad]
+    return D.grad_keys(det, EXTRA_GRAD_KEYS)
 
 
 def loss_module_case():

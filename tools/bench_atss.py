@@ -13,36 +13,21 @@
 
 Warm-up first, device events around every timed call, medians.  One JSON line per table.
 usage: bench_atss.py [kernel] [head] [step] [--steps K] [--warmup W] [--batch B]"""
-import argparse
-import json
 import os
-import statistics
 import sys
 
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from htd_amd import capi  # noqa: E402
-from bench_retinanet import HBM_COPY_TBS, SIZES, alternated, timed  # noqa: E402
+import bench_dense as D  # noqa: E402
+from bench_dense import SIZES, capi  # noqa: E402
 
 
 def head_and_inputs(dev, batch):
-    from htd_amd import detector  # noqa: F401
     from htd_amd.configs import atss_config
-    from htd_amd.registry import build_head
     from htd_amd.runner import synthetic_batch
-    cfg = atss_config()
-    spec = cfg.model.bbox_head.to_dict()
-    spec.update(train_cfg=cfg.train_cfg, test_cfg=cfg.test_cfg)
-    head = build_head(spec).to(dev)
-    data = synthetic_batch(batch, device=dev, seed=0)
-    g = torch.Generator().manual_seed(0)
-    cl = torch.channels_last
-    cls = [(torch.randn(batch, 80, h, w, generator=g) - 4.0).to(dev).contiguous(memory_format=cl) for h, w in SIZES]
-    reg = [torch.randn(batch, 4, h, w, generator=g).to(dev).contiguous(memory_format=cl) for h, w in SIZES]
-    ctr = [torch.randn(batch, 1, h, w, generator=g).to(dev).contiguous(memory_format=cl) for h, w in SIZES]
-    return head, data, cls, reg, ctr
+    head, data = D.head_from_config(atss_config, dev), synthetic_batch(batch, device=dev, seed=0)
+    return (head, data, *D.seeded_maps(((80, lambda t, l: t - 4.0), (4, lambda t, l: t), (1, lambda t, l: t)), batch, dev))
 
 
 def bench_kernel(dev, reps, warmup, batch):
@@ -79,86 +64,27 @@ def bench_kernel(dev, reps, warmup, batch):
     bytes_ = dict(htd_atss_targets=valid_gts * A * 16 + n * (3 * 8 + 4 + 4), htd_atss_loss=n * (2 * 80 * 4 + 2 * 4 * 4 + 2 * 4 + 4 + 4))
     out = dict(table='kernel', batch=B, anchors=A, classes=80, gts=K, valid_gts=valid_gts, positives=int(num_pos.sum()))
     for name, fn in (('htd_atss_targets', targets), ('htd_atss_loss', loss)):
-        r = timed(fn, reps, warmup)
-        floor = bytes_[name] / (HBM_COPY_TBS * 1e12) * 1e6
-        r.update(mandatory_MB=round(bytes_[name] / 1e6, 2), hbm_floor_us=round(floor, 2), fraction_of_floor=round(floor / r['median_us'], 3))
-        out[name] = r
+        out[name] = D.floor_row(D.timed(fn, reps, warmup), bytes_[name])
     return out
 
 
 def bench_head(dev, reps, warmup, batch):
     head, data, cls, reg, ctr = head_and_inputs(dev, batch)
 
-    def step(fused):
-        def run():
-            head.fused_loss = fused
-            maps = [[t.detach().requires_grad_() for t in ms] for ms in (cls, reg, ctr)]
-            ls = head.loss(*maps, data['gt_bboxes'], data['gt_labels'], data['img_metas'])
-            (sum(ls['loss_cls']) + sum(ls['loss_bbox']) + sum(ls['loss_centerness']) if isinstance(ls['loss_cls'], list)
-             else ls['loss_cls'] + ls['loss_bbox'] + ls['loss_centerness']).backward()
-        return run
+    def run_loss():
+        maps = [[t.detach().requires_grad_() for t in ms] for ms in (cls, reg, ctr)]
+        ls = head.loss(*maps, data['gt_bboxes'], data['gt_labels'], data['img_metas'])
+        (sum(ls['loss_cls']) + sum(ls['loss_bbox']) + sum(ls['loss_centerness']) if isinstance(ls['loss_cls'], list)
+         else ls['loss_cls'] + ls['loss_bbox'] + ls['loss_centerness']).backward()
     assert head._fused_loss_ok(cls, reg, ctr, data['gt_labels'], None, data['img_metas']), 'the fused path must take these maps'
-    out = dict(table='head', batch=batch, anchors=sum(h * w for h, w in SIZES))
-    out.update(alternated(dict(fused=step(True), tensor_path=step(False)), reps, warmup))
-    out['fused_no_slower'] = out['fused']['median_us'] <= out['tensor_path']['median_us']
-    head.fused_loss = True
-    return out
+    return D.head_table(head, run_loss, reps, warmup, batch=batch, anchors=sum(h * w for h, w in SIZES))
 
 
 def bench_step(dev, steps, warmup, batch):
-    from htd_amd.configs import build_baseline_detector, build_retinanet_detector
-    from htd_amd.runner import Trainer, synthetic_batch
-
-    def trainer(kind, fused):
-        torch.manual_seed(0)
-        model = build_retinanet_detector() if kind == 'retinanet' else build_baseline_detector(kind)
-        model.bbox_head.fused_loss = fused
-        return Trainer(model.to(dev).train(), lr=0.0)                # lr 0: every leg times the same weights throughout
-    data = synthetic_batch(batch, device=dev, seed=0)
-    legs = dict(atss_fused=trainer('atss', True), atss_tensor_path=trainer('atss', False), fcos_fused=trainer('fcos', True),
-                retinanet_fused=trainer('retinanet', True))
-    times = {k: [] for k in legs}
-    for tr in legs.values():
-        for _ in range(warmup):
-            tr.train_step(data)
-    torch.cuda.synchronize()
-    for _ in range(steps):
-        for k, tr in legs.items():
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            tr.train_step(data)
-            b.record()
-            b.synchronize()
-            times[k].append(a.elapsed_time(b))
-    out = dict(table='step', model='atss_r50_fpn', precision='fp32', batch=batch, image='1333x800', steps=steps, warmup=warmup)
-    for k, v in times.items():
-        med = statistics.median(v)
-        out[k] = dict(median_ms=round(med, 2), min_ms=round(min(v), 2), max_ms=round(max(v), 2), img_per_s=round(batch * 1e3 / med, 2))
-    out['fused_no_slower'] = out['atss_fused']['median_ms'] <= out['atss_tensor_path']['median_ms']
-    return out
-
-
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('tables', nargs='*', default=['kernel', 'head', 'step'])
-    ap.add_argument('--steps', type=int, default=20)
-    ap.add_argument('--warmup', type=int, default=5)
-    ap.add_argument('--reps', type=int, default=100)
-    ap.add_argument('--batch', type=int, default=4)
-    args = ap.parse_args()
-    assert torch.cuda.is_available(), 'bench_atss.py measures on the GPU only'
-    dev = torch.device('cuda:0')
-    capi.lib()
-    for t in args.tables or ['kernel', 'head', 'step']:
-        if t == 'kernel':
-            print(json.dumps(bench_kernel(dev, args.reps, 10, args.batch)), flush=True)
-        elif t == 'head':
-            print(json.dumps(bench_head(dev, max(10, args.reps // 5), 3, args.batch)), flush=True)
-        elif t == 'step':
-            print(json.dumps(bench_step(dev, args.steps, args.warmup, args.batch)), flush=True)
-        else:
-            raise SystemExit(f'unknown table {t}')
+    return D.step_table(dev, 'atss_r50_fpn', (('atss_fused', 'atss', True), ('atss_tensor_path', 'atss', False),
+                                              ('fcos_fused', 'fcos', True), ('retinanet_fused', 'retinanet', True)),
+                        (('atss_fused', 'atss_tensor_path'), ), steps, warmup, batch)
 
 
 if __name__ == '__main__':
-    main()
+    D.main('bench_atss.py', dict(kernel=(bench_kernel, D.KERNEL), head=(bench_head, D.HEAD), step=(bench_step, D.STEP)))

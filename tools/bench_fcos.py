@@ -12,39 +12,22 @@
 
 Warm-up first, device events around every timed call, medians.  One JSON line per table.
 usage: bench_fcos.py [kernel] [head] [step] [--steps K] [--warmup W] [--batch B]"""
-import argparse
-import json
 import os
-import statistics
 import sys
 
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from htd_amd import capi  # noqa: E402
-from bench_retinanet import HBM_COPY_TBS, SIZES, alternated, timed  # noqa: E402
-
-STRIDES = (8, 16, 32, 64, 128)
+import bench_dense as D  # noqa: E402
+from bench_dense import SIZES, STRIDES, capi  # noqa: E402
 
 
 def head_and_inputs(dev, batch):
-    from htd_amd import detector  # noqa: F401
     from htd_amd.configs import fcos_config
-    from htd_amd.registry import build_head
     from htd_amd.runner import synthetic_batch
-    cfg = fcos_config()
-    spec = cfg.model.bbox_head.to_dict()
-    spec.update(train_cfg=cfg.train_cfg, test_cfg=cfg.test_cfg)
-    head = build_head(spec).to(dev)
-    data = synthetic_batch(batch, device=dev, seed=0)
-    g = torch.Generator().manual_seed(0)
-    cl = torch.channels_last
-    cls = [(torch.randn(batch, 80, h, w, generator=g) - 4.0).to(dev).contiguous(memory_format=cl) for h, w in SIZES]
-    reg = [(0.5 * torch.randn(batch, 4, h, w, generator=g)).exp().mul(2.0 * s).to(dev).contiguous(memory_format=cl)
-           for (h, w), s in zip(SIZES, STRIDES)]
-    ctr = [torch.randn(batch, 1, h, w, generator=g).to(dev).contiguous(memory_format=cl) for h, w in SIZES]
-    return head, data, cls, reg, ctr
+    head, data = D.head_from_config(fcos_config, dev), synthetic_batch(batch, device=dev, seed=0)
+    return (head, data, *D.seeded_maps(((80, lambda t, l: t - 4.0), (4, lambda t, l: (0.5 * t).exp().mul(2.0 * STRIDES[l])),
+                                        (1, lambda t, l: t)), batch, dev))
 
 
 def bench_kernel(dev, reps, warmup, batch):
@@ -83,84 +66,25 @@ def bench_kernel(dev, reps, warmup, batch):
                   htd_fcos_keys=n * (80 * 4 + 4 + 4))
     out = dict(table='kernel', batch=B, points=P, classes=80, gts=K, positives=int(num_pos.sum()))
     for name, fn in (('htd_fcos_targets', targets), ('htd_fcos_loss', loss), ('htd_fcos_keys', keys_)):
-        r = timed(fn, reps, warmup)
-        floor = bytes_[name] / (HBM_COPY_TBS * 1e12) * 1e6
-        r.update(mandatory_MB=round(bytes_[name] / 1e6, 2), hbm_floor_us=round(floor, 2), fraction_of_floor=round(floor / r['median_us'], 3))
-        out[name] = r
+        out[name] = D.floor_row(D.timed(fn, reps, warmup), bytes_[name])
     return out
 
 
 def bench_head(dev, reps, warmup, batch):
     head, data, cls, reg, ctr = head_and_inputs(dev, batch)
 
-    def step(fused):
-        def run():
-            head.fused_loss = fused
-            maps = [[t.detach().requires_grad_() for t in ms] for ms in (cls, reg, ctr)]
-            ls = head.loss(*maps, data['gt_bboxes'], data['gt_labels'], data['img_metas'])
-            (ls['loss_cls'] + ls['loss_bbox'] + ls['loss_centerness']).backward()
-        return run
-    out = dict(table='head', batch=batch, points=sum(h * w for h, w in SIZES))
-    out.update(alternated(dict(fused=step(True), tensor_path=step(False)), reps, warmup))
-    out['fused_no_slower'] = out['fused']['median_us'] <= out['tensor_path']['median_us']
-    head.fused_loss = True
-    return out
+    def run_loss():
+        maps = [[t.detach().requires_grad_() for t in ms] for ms in (cls, reg, ctr)]
+        ls = head.loss(*maps, data['gt_bboxes'], data['gt_labels'], data['img_metas'])
+        (ls['loss_cls'] + ls['loss_bbox'] + ls['loss_centerness']).backward()
+    return D.head_table(head, run_loss, reps, warmup, batch=batch, points=sum(h * w for h, w in SIZES))
 
 
 def bench_step(dev, steps, warmup, batch):
-    from htd_amd.configs import build_baseline_detector, build_retinanet_detector
-    from htd_amd.runner import Trainer, synthetic_batch
-
-    def trainer(kind, fused):
-        torch.manual_seed(0)
-        model = build_retinanet_detector() if kind == 'retinanet' else build_baseline_detector('fcos')
-        model.bbox_head.fused_loss = fused
-        return Trainer(model.to(dev).train(), lr=0.0)                # lr 0: every leg times the same weights throughout
-    data = synthetic_batch(batch, device=dev, seed=0)
-    legs = dict(fcos_fused=trainer('fcos', True), fcos_tensor_path=trainer('fcos', False), retinanet_fused=trainer('retinanet', True))
-    times = {k: [] for k in legs}
-    for tr in legs.values():
-        for _ in range(warmup):
-            tr.train_step(data)
-    torch.cuda.synchronize()
-    for _ in range(steps):
-        for k, tr in legs.items():
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            tr.train_step(data)
-            b.record()
-            b.synchronize()
-            times[k].append(a.elapsed_time(b))
-    out = dict(table='step', model='fcos_r50_caffe_fpn_gn-head', precision='fp32', batch=batch, image='1333x800', steps=steps,
-               warmup=warmup)
-    for k, v in times.items():
-        med = statistics.median(v)
-        out[k] = dict(median_ms=round(med, 2), min_ms=round(min(v), 2), max_ms=round(max(v), 2), img_per_s=round(batch * 1e3 / med, 2))
-    out['fused_no_slower'] = out['fcos_fused']['median_ms'] <= out['fcos_tensor_path']['median_ms']
-    return out
-
-
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('tables', nargs='*', default=['kernel', 'head', 'step'])
-    ap.add_argument('--steps', type=int, default=20)
-    ap.add_argument('--warmup', type=int, default=5)
-    ap.add_argument('--reps', type=int, default=100)
-    ap.add_argument('--batch', type=int, default=4)
-    args = ap.parse_args()
-    assert torch.cuda.is_available(), 'bench_fcos.py measures on the GPU only'
-    dev = torch.device('cuda:0')
-    capi.lib()
-    for t in args.tables or ['kernel', 'head', 'step']:
-        if t == 'kernel':
-            print(json.dumps(bench_kernel(dev, args.reps, 10, args.batch)), flush=True)
-        elif t == 'head':
-            print(json.dumps(bench_head(dev, max(10, args.reps // 5), 3, args.batch)), flush=True)
-        elif t == 'step':
-            print(json.dumps(bench_step(dev, args.steps, args.warmup, args.batch)), flush=True)
-        else:
-            raise SystemExit(f'unknown table {t}')
+    return D.step_table(dev, 'fcos_r50_caffe_fpn_gn-head', (('fcos_fused', 'fcos', True), ('fcos_tensor_path', 'fcos', False),
+                                                            ('retinanet_fused', 'retinanet', True)),
+                        (('fcos_fused', 'fcos_tensor_path'), ), steps, warmup, batch)
 
 
 if __name__ == '__main__':
-    main()
+    D.main('bench_fcos.py', dict(kernel=(bench_kernel, D.KERNEL), head=(bench_head, D.HEAD), step=(bench_step, D.STEP)))

@@ -15,37 +15,23 @@ Warm-up first, device events around every timed call, medians.  One JSON line pe
 HTD_EXTRA_HIPCC=-DHTD_GHM_HIST_PLAIN and selected by HTD_AMD_LIB times the per-element form of the histogram (one LDS atomic per
 element instead of one per distinct bin of a wavefront).
 usage: bench_ghm.py [kernel] [matrix] [head] [step] [--steps K] [--warmup W] [--reps R] [--batch B]"""
-import argparse
 import ctypes
-import json
 import os
-import statistics
 import sys
 
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from htd_amd import capi  # noqa: E402
-from bench_retinanet import SIZES, alternated, timed  # noqa: E402
+import bench_dense as D  # noqa: E402
+from bench_dense import SIZES, alternated, capi  # noqa: E402
 
 
 def head_and_inputs(dev, batch, ghm=True):
-    from htd_amd import detector  # noqa: F401
     from htd_amd.configs import retinanet_config, retinanet_ghm_config
-    from htd_amd.registry import build_head
     from htd_amd.runner import synthetic_batch
-    cfg = retinanet_ghm_config() if ghm else retinanet_config()
-    spec = cfg.model.bbox_head.to_dict()
-    spec.update(train_cfg=cfg.train_cfg, test_cfg=cfg.test_cfg)
-    head = build_head(spec).to(dev)
-    data = synthetic_batch(batch, device=dev, seed=0)
-    g = torch.Generator().manual_seed(0)
-    cl = torch.channels_last
+    head, data = D.head_from_config(retinanet_ghm_config if ghm else retinanet_config, dev), synthetic_batch(batch, device=dev, seed=0)
     # logits of a freshly initialised head (prior 0.01: bias -4.6) with some spread, so most elements fall into bin 0
-    cls = [(torch.randn(batch, 720, h, w, generator=g) - 4.0).to(dev).contiguous(memory_format=cl) for h, w in SIZES]
-    reg = [(0.3 * torch.randn(batch, 36, h, w, generator=g)).to(dev).contiguous(memory_format=cl) for h, w in SIZES]
-    return head, data, cls, reg
+    return (head, data, *D.seeded_maps(((720, lambda t, l: t - 4.0), (36, lambda t, l: 0.3 * t)), batch, dev))
 
 
 def bench_kernel(dev, reps, warmup, batch):
@@ -152,80 +138,25 @@ class HostReads:
 def bench_head(dev, reps, warmup, batch):
     head, data, cls, reg = head_and_inputs(dev, batch)
 
-    def step(fused):
-        def run():
-            head.fused_loss = fused
-            c, r = [t.detach().requires_grad_() for t in cls], [t.detach().requires_grad_() for t in reg]
-            losses = head.loss(c, r, data['gt_bboxes'], data['gt_labels'], data['img_metas'])
-            (sum(losses['loss_cls']) + sum(losses['loss_bbox'])).backward()
-        return run
-    out = dict(table='head', batch=batch, anchors=9 * sum(h * w for h, w in SIZES))
-    out.update(alternated(dict(fused=step(True), tensor_path=step(False)), reps, warmup))
-    out['fused_no_slower'] = out['fused']['median_us'] <= out['tensor_path']['median_us']
-    for name, fused in (('fused', True), ('tensor_path', False)):
-        with HostReads() as hr:
-            step(fused)()
-        out[name]['host_reads'] = hr.n
-    head.fused_loss = True
-    return out
+    def run_loss():
+        c, r = [t.detach().requires_grad_() for t in cls], [t.detach().requires_grad_() for t in reg]
+        losses = head.loss(c, r, data['gt_bboxes'], data['gt_labels'], data['img_metas'])
+        (sum(losses['loss_cls']) + sum(losses['loss_bbox'])).backward()
+
+    def host_reads(out, step):
+        for name, fused in (('fused', True), ('tensor_path', False)):
+            with HostReads() as hr:
+                step(fused)()
+            out[name]['host_reads'] = hr.n
+    return D.head_table(head, run_loss, reps, warmup, after=host_reads, batch=batch, anchors=9 * sum(h * w for h, w in SIZES))
 
 
 def bench_step(dev, steps, warmup, batch):
-    from htd_amd.configs import build_retinanet_detector, build_retinanet_ghm_detector
-    from htd_amd.runner import Trainer, synthetic_batch
-
-    def trainer(build, fused):
-        torch.manual_seed(0)
-        model = build()
-        model.bbox_head.fused_loss = fused
-        return Trainer(model.to(dev).train(), lr=0.0)                # lr 0: every leg times the same weights throughout
-    data = synthetic_batch(batch, device=dev, seed=0)
-    legs = dict(ghm_fused=trainer(build_retinanet_ghm_detector, True), ghm_tensor_path=trainer(build_retinanet_ghm_detector, False),
-                focal_fused=trainer(build_retinanet_detector, True))
-    times = {k: [] for k in legs}
-    for tr in legs.values():
-        for _ in range(warmup):
-            tr.train_step(data)
-    torch.cuda.synchronize()
-    for _ in range(steps):
-        for k, tr in legs.items():
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            tr.train_step(data)
-            b.record()
-            b.synchronize()
-            times[k].append(a.elapsed_time(b))
-    out = dict(table='step', model='retinanet_ghm_r50_fpn', precision='fp32', batch=batch, image='1333x800', steps=steps, warmup=warmup)
-    for k, v in times.items():
-        med = statistics.median(v)
-        out[k] = dict(median_ms=round(med, 2), min_ms=round(min(v), 2), max_ms=round(max(v), 2), img_per_s=round(batch * 1e3 / med, 2))
-    out['fused_no_slower'] = out['ghm_fused']['median_ms'] <= out['ghm_tensor_path']['median_ms']
-    return out
-
-
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('tables', nargs='*', default=['kernel', 'matrix', 'head', 'step'])
-    ap.add_argument('--steps', type=int, default=20)
-    ap.add_argument('--warmup', type=int, default=5)
-    ap.add_argument('--reps', type=int, default=100)
-    ap.add_argument('--batch', type=int, default=4)
-    args = ap.parse_args()
-    assert torch.cuda.is_available(), 'bench_ghm.py measures on the GPU only'
-    dev = torch.device('cuda:0')
-    capi.lib()
-    for t in args.tables or ['kernel', 'matrix', 'head', 'step']:
-        if t == 'kernel':
-            print(json.dumps(bench_kernel(dev, args.reps, 10, args.batch)), flush=True)
-        elif t == 'matrix':
-            print(json.dumps(bench_matrix(dev, args.reps, 10, args.batch)), flush=True)
-        elif t == 'head':
-            print(json.dumps(bench_head(dev, max(10, args.reps // 5), 3, args.batch)), flush=True)
-        elif t == 'step':
-            print(json.dumps(bench_step(dev, args.steps, args.warmup, args.batch)), flush=True)
-        else:
-            raise SystemExit(f'unknown table {t}')
+    return D.step_table(dev, 'retinanet_ghm_r50_fpn', (('ghm_fused', 'retinanet_ghm', True), ('ghm_tensor_path', 'retinanet_ghm', False),
+                                                       ('focal_fused', 'retinanet', True)),
+                        (('ghm_fused', 'ghm_tensor_path'), ), steps, warmup, batch)
 
 
 if __name__ == '__main__':
-    main()
+    D.main('bench_ghm.py', dict(kernel=(bench_kernel, D.KERNEL), matrix=(bench_matrix, D.KERNEL), head=(bench_head, D.HEAD),
+                                step=(bench_step, D.STEP)))
